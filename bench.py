@@ -18,6 +18,10 @@ never touches the GPU) runs ``python -m torch.distributed.run --nproc-per-node N
 its return code.  Under ``rocprofv3`` call it as ``-- python3 bench.py ...`` (no ``env`` / shell hop after the profiler
 has initialised the GPU).
 
+A plain run builds the graph, runs W warm-up sweeps, times K sweeps and prints the line.  `--full` adds what the headline
+figure does not need: the CPU baselines, the dominant kernel timed alone on one stream and, with N > 1, the other split.
+`--dump-outputs DIR` (one GPU) writes a seeded sample of the state the last timed sweep left as float64 DIR/<name>.npy files.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -153,6 +157,30 @@ def python_baseline(n, T, budget_s=10.0):
     return out
 
 
+DUMP_SEED = 0                  # --dump-outputs: the sampled rows are the same in every run
+DUMP_BYTES = 60 << 20          # --dump-outputs: at most this much in all
+
+
+def dump_outputs(bp, out_dir):
+    """--dump-outputs: what the last sweep left for a caller of EPBP -- the f -> v and v -> f log-messages and the proposal
+    messages of a seeded sample of edges, the proposals and the particles of a seeded sample of variables -- as float64
+    `out_dir/<name>.npy`, with the sampled row numbers in edge_index.npy / variable_index.npy"""
+    import torch
+    E, V = bp.flat.E, bp.flat.V
+    per_edge = {'f2v': bp.f2v, 'v2f': bp.v2f, 'eta': bp.eta}
+    per_var = {'proposal': bp.q_dev, 'particles': bp.particles}
+    row_bytes = 8 * (2 + sum(a.shape[1] for a in list(per_edge.values()) + list(per_var.values())))
+    k = min(E, V, 1 << 14, DUMP_BYTES // row_bytes)
+    rng = np.random.default_rng(DUMP_SEED)
+    os.makedirs(out_dir, exist_ok=True)
+    for kind, count, arrays in (('edge', E, per_edge), ('variable', V, per_var)):
+        rows = np.sort(rng.choice(count, size=k, replace=False))
+        np.save(os.path.join(out_dir, kind + '_index.npy'), rows.astype(np.float64))
+        idx = torch.from_numpy(rows).to(bp.f2v.device)
+        for name, a in arrays.items():
+            np.save(os.path.join(out_dir, name + '.npy'), a.index_select(0, idx).cpu().numpy().astype(np.float64))
+
+
 def self_launch(n_ranks):
     """`--gpus N` without a launcher: start N ranks of this file under torch.distributed.run from a parent that has not
     touched the GPU (and never will); returns the launcher's exit code (non-zero if any rank failed)"""
@@ -172,7 +200,14 @@ def main():
     ap.add_argument('--edges', type=int, default=10_000_000)
     ap.add_argument('--particles', type=int, default=64)
     ap.add_argument('--grid', type=int, default=32)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baselines')
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed sweeps, also measure what the headline figure does not need: the CPU baselines (C oracle '
+                         'and pure-Python restatement), the dominant f->v kernel alone on one stream and, with N > 1, the other '
+                         'split (see --also)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='one GPU: after the timed sweeps, write a fixed seeded sample of the messages, proposals and particles the '
+                         'last one left to DIR/<name>.npy (float64, at most 60 MB)')
     ap.add_argument('--exchange', choices=('pairs', 'owner', 'ownercompute'), default=None,
                     help='multi-GPU runs, the split that `value` is quoted on (default: LHVI_BENCH_EXCHANGE or ownercompute): '
                          'ownercompute: VARIABLES partitioned, every message computed where its target lives, v->f rows of cut '
@@ -181,8 +216,8 @@ def main():
                          'rank and sent back (two smaller collectives)')
     ap.add_argument('--also', default=None,
                     help='multi-GPU runs: comma-separated other splits to build, time and free after the first one in the same '
-                         'launch (default: the other of ownercompute / pairs; "none" to skip); all of them are printed under '
-                         '"exchanges" with their phases_ms')
+                         'launch (default: with --full the other of ownercompute / pairs, else none; "none" to skip); all of them '
+                         'are printed under "exchanges" with their phases_ms')
     ap.add_argument('--proposal', choices=('simple', 'EP'), default='simple',
                     help="proposal rule of the sweep: 'simple' is what BASELINE.json's metric is quoted on; 'EP' is the reference's "
                          "default (EPBPLogVersion.py:20)")
@@ -190,6 +225,10 @@ def main():
 
     if args.gpus < 1:
         raise SystemExit('--gpus must be at least 1')
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit('--steps must be at least 1 and --warmup at least 0')
+    if args.dump_outputs and args.gpus != 1:
+        raise SystemExit('--dump-outputs needs --gpus 1')
     if 'WORLD_SIZE' not in os.environ and args.gpus > 1:
         sys.exit(self_launch(args.gpus))             # before anything imports torch or touches the GPU
     world = int(os.environ.get('WORLD_SIZE', '1'))
@@ -199,7 +238,7 @@ def main():
         raise SystemExit('--gpus %d does not match WORLD_SIZE=%d of the launcher' % (args.gpus, world))
     primary = args.exchange or os.environ.get('LHVI_BENCH_EXCHANGE', 'ownercompute')
     if args.also is None:
-        also = [x for x in ('ownercompute', 'pairs') if x != primary][:1]
+        also = [x for x in ('ownercompute', 'pairs') if x != primary][:1] if args.full else []
     else:
         also = [x for x in args.also.split(',') if x and x != 'none' and x != primary]
     for x in [primary] + also:
@@ -295,11 +334,14 @@ def main():
 
     runner = build(primary if world > 1 else None)
     elapsed, f2v_ms = time_runner(runner, primary if world > 1 else 'single GPU')
+    if args.dump_outputs:
+        phase('single GPU: writing the last sweep\'s outputs to %s' % args.dump_outputs)
+        dump_outputs(runner.bp, args.dump_outputs)
     # single GPU: the dominant kernel shares the CUs with the short f -> v kernels on a second stream (lhvi/pbp.py, overlap_f2v); a few
     # sweeps on ONE stream after the timed region give its duration alone, reported beside the timed one (never in `value`)
     f2v_alone_ms = None
     bp0 = getattr(runner, 'bp', None)
-    if world == 1 and bp0 is not None and getattr(bp0, 'overlap_f2v', False) and os.environ.get('LHVI_PBP_OVERLAP') != '0' \
+    if args.full and world == 1 and bp0 is not None and getattr(bp0, 'overlap_f2v', False) and os.environ.get('LHVI_PBP_OVERLAP') != '0' \
             and getattr(bp0, 'n_heavy', 0) >= getattr(bp0, 'overlap_min_heavy', 1 << 62):
         phase('single GPU: five sweeps on one stream (the dominant kernel alone)')
         bp0.overlap_f2v = False
@@ -435,7 +477,7 @@ def main():
             out['phases_ms'] = runner.phase_ms()      # sharded runs: HIP-event times of pack / interior / exchange wait / boundary
         if exchanges is not None:
             out['exchanges'] = exchanges              # every split timed in this launch (`value` is the first one's)
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             phase('CPU baseline: C oracle on a bounded sample')
             Es, sw, dt, edge_rate, cores = cpu_baseline(n, T)
             phase('CPU baseline: pure-Python restatement at 1e3 / 1e4 / 1e5 edges')

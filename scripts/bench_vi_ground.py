@@ -1,5 +1,6 @@
-import sys, time, json
-sys.path[:0] = ['/root/repo', '/root/repo/lifted-hybrid-variational-inference_amd']
+import os, sys, time, json
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd')]
 import numpy as np, torch
 from lhvi import _abi, synth
 from lhvi.vi import VarInference

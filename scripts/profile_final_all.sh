@@ -9,7 +9,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 cd $R
 if [ $part = 1 ]; then
-  timeout -k 10 400 python3 bench.py > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.log || exit 1
+  timeout -k 10 400 python3 bench.py --full > $O/${tag}_bench_default.json 2> $O/${tag}_bench_default.log || exit 1
   cp $O/${tag}_bench_default.json profiles/${tag}_bench_default.json
   cut -c1-300 $O/${tag}_bench_default.json
   bash scripts/profile_round.sh ${tag}_final || exit 1

@@ -303,12 +303,12 @@ def test_bench_rejects_a_launcher_of_another_size():
 
 @pytest.mark.gpu
 def test_bench_times_both_splits_in_one_launch():
-    """`python bench.py --gpus 2` without a launcher (gloo rehearsal backend, both ranks on the box's one GPU): the parent (no GPU
-    call) starts two ranks under torch.distributed.run; rank 0 prints ONE JSON line whose `value` is the default split's
+    """`python bench.py --gpus 2 --full` without a launcher (gloo rehearsal backend, both ranks on the box's one GPU): the parent
+    (no GPU call) starts two ranks under torch.distributed.run; rank 0 prints ONE JSON line whose `value` is the default split's
     (owner computes) and whose `exchanges` holds every split timed in this launch -- the other one (factor-partitioned rows
     between pairs) built, timed and freed after it -- each with its phase times, so that one node run compares them"""
     import json
-    r = _run_bench(['--gpus', '2', '--edges', '200000', '--steps', '3', '--warmup', '1', '--no-cpu-baseline'],
+    r = _run_bench(['--gpus', '2', '--edges', '200000', '--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--full'],
                    env={'LHVI_DIST_BACKEND': 'gloo'})
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
@@ -339,6 +339,33 @@ def test_bench_flag_picks_the_split_and_a_stuck_phase_exits_non_zero():
     r = _run_bench(['--gpus', '2', '--edges', '200000', '--steps', '2', '--warmup', '1', '--no-cpu-baseline'],
                    env={'LHVI_DIST_BACKEND': 'gloo', 'LHVI_BENCH_PHASE_TIMEOUT': '0.001'})
     assert r.returncode != 0 and 'STUCK in phase' in r.stderr
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_and_its_dumped_outputs(tmp_path):
+    """`bench.py --gpus 1` without --full: the headline line alone (no CPU baselines, no kernel timed on its own), `steps`
+    timed sweeps; `--dump-outputs DIR`: float64 .npy files under 64 MB in all, the same bits in two runs of the same command"""
+    import json
+    dirs = [os.path.join(str(tmp_path), 'run%d' % k) for k in range(2)]
+    for d in dirs:
+        r = _run_bench(['--gpus', '1', '--edges', '200000', '--steps', '3', '--warmup', '1', '--dump-outputs', d])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out['steps'] == 3 and out['unit'] == 'sweeps/s' and out['higher_is_better'] and out['dtype'] == 'f64'
+        assert out['ms_per_step'] > 0 and abs(out['value'] * out['ms_per_step'] - 1e3) < 1e-6 * 1e3
+        assert 'cpu_baseline' not in out and out['roofline']['alone'] is None
+        assert 'CPU baseline' not in r.stderr and '3 timed sweeps' in r.stderr
+    names = sorted(os.listdir(dirs[0]))
+    assert names == sorted(os.listdir(dirs[1]))
+    assert {'f2v.npy', 'v2f.npy', 'eta.npy', 'proposal.npy', 'particles.npy', 'edge_index.npy', 'variable_index.npy'} <= set(names)
+    total = 0
+    for name in names:
+        a, b = (np.load(os.path.join(d, name)) for d in dirs)
+        assert a.dtype == np.float64 and a.shape[0] > 0 and np.array_equal(a, b, equal_nan=True), name
+        total += os.path.getsize(os.path.join(dirs[0], name))
+    assert total <= 64 << 20
 
 
 @pytest.mark.gpu
