@@ -27,14 +27,15 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 11  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 12  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
                               *    lhvi_gabp_plan_t.n_hub_rows, lhvi_gabp_graph_*; lhvi_pbp_t gained v2f_wide / v2f_narrow / v2f_hub / v2f_mid16 / v2f_mid32, prop_hub / prop_partial, resample_vars, small16_desc / small32_desc; 16 ticket words; lhvi_pbp_boundary_reduce;
                               * 9: lhvi_vi_t gained fac_list / n_cc / n_tiny / n_grp3 / n_grp6 / n_rest3 / n_rest6 / edge_axis; lhvi_color_first_members, lhvi_color_segment_sums, lhvi_pbp_halo_pack / _unpack; lhvi_gabp_plan_t.rec;
                               * 10: lhvi_pbp_t gained halo_off / halo_buf, LHVI_PBP_NO_UNIQ, edge_canon may name rows beyond E; lhvi_pbp_map_brent, lhvi_pbp_quad;
-                              * 11: LHVI_PBP_V2F_RECORDS (v2f_wide as 8-word records), LHVI_PBP_WIDE_PAIRS, LHVI_PBP_SHARE_CUS */
+                              * 11: LHVI_PBP_V2F_RECORDS (v2f_wide as 8-word records), LHVI_PBP_WIDE_PAIRS, LHVI_PBP_SHARE_CUS;
+                              * 12: lhvi_vi_map_bfgs */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -571,6 +572,16 @@ int lhvi_adam_step(double* theta, double* m, double* s, const double* g, int64_t
                    double lr, double b1, double b2, double eps, int32_t clip_stride, double clip_min, void* stream);
 /* softmax over rows of `cols` valid entries (stride `stride`): VarInference.py:32-38 */
 int lhvi_softmax_rows(const double* tau, double* out, int64_t rows, int32_t cols, int32_t stride, void* stream);
+/* map(rv) (VarInference.py:355-376) of nq rows in ONE launch, a thread each (csrc/vi_map.hip).  row_var [nq]: variables of the
+ * solver's graph.  A hidden continuous row runs what the reference calls: scipy.optimize.minimize(-belief, x0 = the first component
+ * mean of largest belief), i.e. SciPy 1.15's BFGS with a forward-difference gradient, line_search_wolfe1 (MINPACK dcsrch) and
+ * line_search_wolfe2 as fallback -- the same iterates, decision for decision, so that the answer is scipy's and not merely a maximum.
+ * gtol / maxiter: minimize's options (1e-5, 200).  xout [nq] res.x; fout [nq] (optional) -res.fun, the belief there; nit / status
+ * [nq] (optional) res.nit / res.status (0 converged, 1 maxiter, 2 line search failed, 3 NaN).  A hidden discrete row: xout = the
+ * VALUE of the first state of largest sum_k w_k eta_d[v, k, s], fout that sum, status 0.  Observed rows (and indices outside
+ * [0, V)): NaN, status -1.  Reads p->K (<= 128), w, eta_c, eta_d, Dmax. */
+int lhvi_vi_map_bfgs(const lhvi_graph_t* g, const lhvi_vi_t* p, int64_t nq, const int32_t* row_var, double gtol, int32_t maxiter,
+                     double* xout, double* fout, int32_t* nit, int32_t* status, void* stream);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

@@ -102,7 +102,7 @@ PBP_SHARE_CUS = 32768
 PBP_POW2_GROUPS = 65536
 PBP_FUSED_RECORDS16 = 131072
 PBP_SKIP_CQ = 1024
-ABI_VERSION = 11            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 12            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -164,6 +164,7 @@ SIGNATURES = {
     'lhvi_vi_adam_run': (C.c_int, [_G, _P, _VI, C.POINTER(ViOptStruct), _i32, _vp, _vp, _sz, _vp]),
     'lhvi_adam_step': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f64, _f64, _f64, _f64, _i32, _f64, _vp]),
     'lhvi_softmax_rows': (C.c_int, [_vp, _vp, _i64, _i32, _i32, _vp]),
+    'lhvi_vi_map_bfgs': (C.c_int, [_G, _VI, _i64, _vp, _f64, _i32, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_color_workspace_bytes': (_sz, [_G]),
     'lhvi_color_refine_factors': (C.c_int, [_G, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),
     'lhvi_color_refine_rvs': (C.c_int, [_G, _vp, _vp, _vp, _vp, _vp, _sz, _i32, _vp]),

@@ -422,6 +422,8 @@ class _DeviceStage(_Variational):
         self.quad_x, self.quad_w = owner.quad_x, owner.quad_w
         self.reference_quirks = owner.reference_quirks
         self.var_threshold = owner.var_threshold
+        self.map_mode = owner.map_mode
+        self._device_map()                    # (an unknown mode fails here, before the round's work)
         self.time_log, self._dev, self._cache = [], None, {}
         self._obs_var_host = np.ascontiguousarray(obs_var, dtype=np.float64)     # (Gaussian observations are axes of T nodes: factor_lists)
         self._setup_flat(flat)

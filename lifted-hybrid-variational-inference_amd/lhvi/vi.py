@@ -102,6 +102,8 @@ class _Variational:
     tiny_kernel = True          # factors with a handful of grid nodes take the thread-per-(factor, k) kernel when there are >= 2^17
                                 # such items ('always': whatever their number; False: the group kernel)
     factor_lists = True         # the factors are split among the expectation kernels on the host (else: every kernel classifies them itself)
+    map_mode = 'scipy'          # what map() / map_rows() run: 'scipy' -- scipy.optimize.minimize per row on the host, like the reference;
+                                # 'device' -- the same BFGS iterates for every row in one launch (lhvi_vi_map_bfgs, map_rows_device)
 
     def _init_common(self, num_mixtures, num_quadrature_points):
         self.K = num_mixtures
@@ -393,10 +395,25 @@ class _Variational:
     def belief(self, x, rv):
         return self.rvs_belief((x,), (rv,))
 
+    def _device_map(self):
+        """True when map() / map_rows() answer from map_rows_device() (``map_mode``; objects that borrow ``map_rows`` without the
+        attribute run the host path)"""
+        mode = getattr(self, 'map_mode', 'scipy')
+        if mode == 'device':
+            return True
+        if mode != 'scipy':
+            raise ValueError("map_mode must be 'scipy' or 'device', not %r" % (mode,))
+        return False
+
     def map(self, rv):
         """VI:355-376"""
         if rv.value is not None:
             return rv.value
+        if self._device_map():
+            x = self.map_rows_device()[self._var_index(rv)]
+            if rv.domain.continuous:
+                return x
+            return next(s for s in rv.domain.values if s == x)          # (the domain's own object for the state value)
         if rv.domain.continuous:
             from scipy.optimize import minimize
             mus = self._host('eta_c')[self._var_index(rv)][:, 0]
@@ -421,7 +438,10 @@ class _Variational:
     def map_rows(self):
         """``map`` (VI:355-376, C2FVI:439-461) of every hidden ROW of the solver's graph -- one ``scipy.optimize.minimize`` per
         row instead of one per ground variable (the members of a cluster share its parameters, hence its answer).  Returns an
-        array [V]: the maximiser for a continuous row, the state VALUE for a discrete one, NaN for an observed one."""
+        array [V]: the maximiser for a continuous row, the state VALUE for a discrete one, NaN for an observed one.
+        ``map_mode = 'device'``: ``map_rows_device()``."""
+        if _Variational._device_map(self):
+            return self.map_rows_device()
         from scipy.optimize import minimize
         flat = self.flat
         out = np.full(flat.V, np.nan)
@@ -436,6 +456,29 @@ class _Variational:
                 p = [self._row_belief(v, i) for i in range(vals.size)]
                 out[v] = vals[int(np.argmax(p))]
         return out
+
+    def map_rows_device(self, gtol=1e-5, maxiter=200, info=False):
+        """``map_rows()`` in ONE launch (``lhvi_vi_map_bfgs``, csrc/vi_map.hip): a thread per row runs the reference's
+        ``minimize(-belief, x0)`` -- SciPy's BFGS, decision for decision -- so the array is the host path's, row for row.
+        ``gtol`` / ``maxiter``: minimize's BFGS options.  ``info=True`` also returns (fval, nit, status): the belief at the answer
+        (the chosen state's for a discrete row), scipy's ``nit`` and ``status`` (-1 on observed rows).  Cached until the
+        parameters change."""
+        key = ('map_device', float(gtol), int(maxiter))
+        if key not in self._cache:
+            torch = _abi.require_gpu()
+            V, dev = self.flat.V, self.dg.device
+            rows = self._dev.get('map_rows')
+            if rows is None:
+                rows = self._dev['map_rows'] = torch.arange(V, dtype=torch.int32, device=dev)
+            x = torch.empty(V, dtype=torch.float64, device=dev)
+            f = torch.empty(V, dtype=torch.float64, device=dev)
+            it = torch.empty(V, dtype=torch.int32, device=dev)
+            st = torch.empty(V, dtype=torch.int32, device=dev)
+            _abi.check(_abi.lib().lhvi_vi_map_bfgs(self.dg.g, self._struct(), V, _abi.ptr(rows), float(gtol), int(maxiter),
+                                                   _abi.ptr(x), _abi.ptr(f), _abi.ptr(it), _abi.ptr(st), _abi.stream_ptr()))
+            self._cache[key] = tuple(a.cpu().numpy() for a in (x, f, it, st))
+        x, f, it, st = self._cache[key]
+        return (x, (f, it, st)) if info else x
 
     def rvs_map(self, rvs):
         """VI:378-456: coordinate ascent on the joint mixture belief"""
