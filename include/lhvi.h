@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 12  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 13  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -35,7 +35,8 @@ extern "C" {
                               * 9: lhvi_vi_t gained fac_list / n_cc / n_tiny / n_grp3 / n_grp6 / n_rest3 / n_rest6 / edge_axis; lhvi_color_first_members, lhvi_color_segment_sums, lhvi_pbp_halo_pack / _unpack; lhvi_gabp_plan_t.rec;
                               * 10: lhvi_pbp_t gained halo_off / halo_buf, LHVI_PBP_NO_UNIQ, edge_canon may name rows beyond E; lhvi_pbp_map_brent, lhvi_pbp_quad;
                               * 11: LHVI_PBP_V2F_RECORDS (v2f_wide as 8-word records), LHVI_PBP_WIDE_PAIRS, LHVI_PBP_SHARE_CUS;
-                              * 12: lhvi_vi_map_bfgs */
+                              * 12: lhvi_vi_map_bfgs;
+                              * 13: lhvi_pbp_f2v selects the kernel families it launches with LHVI_PBP_F2V_* (replacing five bits that skipped kernels) */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -193,13 +194,8 @@ int lhvi_log_likelihood(const lhvi_graph_t* g, const lhvi_pots_t* pots, const do
 
 #define LHVI_PBP_EP 1u            /* proposal_approximation == 'EP' (else 'simple') */
 #define LHVI_PBP_EPBP_DISCRETE 2u /* EPBP applies importance weights to discrete rvs too (EPBP.py:157) */
-#define LHVI_PBP_SKIP_FAST 4u     /* lhvi_pbp_f2v: launch neither quadratic-family kernel (profiling aid) */
-#define LHVI_PBP_SKIP_GENERIC 8u  /* lhvi_pbp_f2v: do not launch the generic-potential kernel (profiling aid) */
 #define LHVI_PBP_SKIP_TERMS 16u   /* lhvi_pbp_f2v: the quadratic-family kernels skip their term loops -- results are
                                    * meaningless; isolates the per-edge load/store cost when tuning */
-#define LHVI_PBP_SKIP_HEAVY 32u   /* lhvi_pbp_f2v: do not launch the continuous x continuous (heavy_desc) kernel (profiling aid) */
-#define LHVI_PBP_SKIP_LIGHT 64u   /* lhvi_pbp_f2v: do not launch the kernels of the remaining fast edges (light_desc and fast_edges;
-                                   * profiling aid) */
 #define LHVI_PBP_LEAVE_ROOM 256u /* lhvi_pbp_f2v: the persistent kernels launch cus/8 workgroups fewer than fill the device, so that
                                    * another stream's kernels (RCCL's copy kernels of an overlapped exchange) find free slots at
                                    * any time instead of waiting for a persistent workgroup to retire.  Set by sharded runs. */
@@ -207,7 +203,6 @@ int lhvi_log_likelihood(const lhvi_graph_t* g, const lhvi_pots_t* pots, const do
                                    * in the continuous arguments for every state of the discrete ones, e.g. x[0] * eq_op(x[1], x[2]),
                                    * Demo/Data/HMLN/GeneratorPaperPopularity.py:28-40) to the quadratic-family kernels instead of the
                                    * generic interpreter kernel: set it for lhvi_pbp_classify / _describe / _describe_cq AND lhvi_pbp_f2v */
-#define LHVI_PBP_SKIP_CQ 1024u   /* lhvi_pbp_f2v: do not launch the kernel of the cq_desc list (profiling aid) */
 #define LHVI_PBP_BOUNDARY_TOTALS 2048u /* sharded runs: a boundary variable's one listed row of s->recv holds the finished total over all ranks
                                         * (lhvi_pbp_boundary_reduce); without it the rows are the peers' sums and the kernels add them */
 #define LHVI_PBP_NO_UNIQ 4096u   /* lhvi_pbp_resample_uniq with a resample_vars list: draw the particles only, leave uniq_out untouched (ghost variables of
@@ -218,13 +213,22 @@ int lhvi_log_likelihood(const lhvi_graph_t* g, const lhvi_pots_t* pots, const do
 #define LHVI_PBP_WIDE_PAIRS 16384u /* lhvi_pbp_f2v: the pair_desc list always through the one-entry-per-wavefront kernel, also when n <= 32 would let
                                    * four / two entries share a wavefront (testing aid: the two kernels give the same bits) */
 #define LHVI_PBP_SHARE_CUS 32768u /* lhvi_pbp_f2v: the persistent grids of the long kernels (heavy_desc, small16 / small32) take one workgroup per CU less than
-                                   * fits, so that the short kernels of the same half sweep, launched by a second call on ANOTHER stream (the pair /
-                                   * light / cq / generic lists: disjoint rows of f2v), find a wave slot and LDS on every CU and run beside them */
+                                   * fits, so that the kernels of the other families, launched by another call on ANOTHER stream (disjoint
+                                   * rows of f2v), find a wave slot and LDS on every CU and run beside them */
 #define LHVI_PBP_NO_GRID 128u    /* lhvi_pbp_f2v: integral points always by the direct form (one exponential per term), never by the
                                    * uniform-grid recurrence (testing / profiling aid) */
 #define LHVI_PBP_FUSED_RECORDS16 131072u /* lhvi_pbp_var_fused: desc holds SIXTEEN 32-bit words per variable (64-byte aligned) -- words 0-7 as documented
                                    * there, then 8 particles of the variable (s->np[v])  9 g->var_ptr[v]  10-15 its first six incident edges
                                    * (var_edge[var_ptr[v] + 0 .. 5]; unused ones 0) -- so that a variable's rows hang on one load behind its record */
+/* lhvi_pbp_f2v: the kernel families a call launches, in this order.  No family bit set: every family.  A half sweep split over
+ * several calls (lhvi/pbp.py::_launch_f2v) names each family in exactly one of them. */
+#define LHVI_PBP_F2V_HEAVY 262144u   /* heavy_desc */
+#define LHVI_PBP_F2V_SMALL 524288u   /* small16_desc and small32_desc */
+#define LHVI_PBP_F2V_PAIR 1048576u   /* pair_desc (through the pair_small or the pair kernel), or light_desc when there is no pair list */
+#define LHVI_PBP_F2V_FAST 2097152u   /* fast_edges, or every edge when the caller gives no work lists */
+#define LHVI_PBP_F2V_CQ 4194304u     /* cq_desc */
+#define LHVI_PBP_F2V_GENERIC 8388608u /* the generic-potential kernel: generic_edges, or every edge when the caller gives no work lists */
+#define LHVI_PBP_F2V_ALL (LHVI_PBP_F2V_HEAVY | LHVI_PBP_F2V_SMALL | LHVI_PBP_F2V_PAIR | LHVI_PBP_F2V_FAST | LHVI_PBP_F2V_CQ | LHVI_PBP_F2V_GENERIC)
 #define LHVI_PBP_POW2_GROUPS 65536u /* lhvi_pbp_f2v: the small16 / small32 lists always through lane groups of 16 / 32 lanes (four / two edges per
                                    * wavefront), also when s->n would let up to eight edges share one (narrower groups, two particles per lane; testing / profiling aid) */
 
@@ -339,8 +343,8 @@ typedef struct lhvi_pbp {
      * LHVI_PBP_POW2_GROUPS keeps four / two): with the particle counts of the
      * reference's demos (10-20) an edge per wavefront is bound by its own latencies, not by its terms.  Integral points on a uniform
      * grid (descriptor word 15) are tabulated by the recurrence along the grid inside the lane group, like the heavy kernel's (to
-     * rounding the same values as the direct form; LHVI_PBP_NO_GRID forces that one).  NULL: such edges stay in heavy_desc.  Skipped
-     * with LHVI_PBP_SKIP_HEAVY. */
+     * rounding the same values as the direct form; LHVI_PBP_NO_GRID forces that one).  NULL: such edges stay in heavy_desc.  Family
+     * LHVI_PBP_F2V_SMALL. */
     const void* small16_desc;
     int32_t n_small16;
     const void* small32_desc;
@@ -410,8 +414,8 @@ int lhvi_pbp_uniq(const lhvi_graph_t* g, int32_t n, const double* particles, con
 /* EPBP.message_rv_to_f + important_weight + log_message_balance: EPBP.py:156-174,204-215; HLBP.py:173-191,225-236 */
 int lhvi_pbp_v2f(const lhvi_graph_t* g, const lhvi_pbp_t* s, const double* f2v, double* v2f, void* stream);
 /* EPBP.message_f_to_rv at the new particles + integral points: EPBP.py:176-194,275-285; HLBP.py:193-215.
- * Up to four kernels on `stream`, one per work list of `s` (heavy_desc, light_desc, fast_edges, generic_edges); the SKIP
- * flags select among them.  With s->f2v_ticket set the call first resets those words on `stream` (a 32-byte memset). */
+ * One kernel per work list of `s` on `stream`, in the order of the LHVI_PBP_F2V_* families, which select among them.  With
+ * s->f2v_ticket set the heavy family first resets those words on `stream` (a memset). */
 int lhvi_pbp_f2v(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_t* s, const double* v2f, double* f2v, void* stream);
 /* update_proposal (sites eta [E][2] in/out, q [V][2] in/out): EPBP.py:83-154; HLBP.py:100-171 */
 int lhvi_pbp_proposal(const lhvi_graph_t* g, const lhvi_pbp_t* s, const double* f2v, double* eta, double* q, void* stream);

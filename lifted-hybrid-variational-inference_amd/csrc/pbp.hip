@@ -654,40 +654,21 @@ __device__ __forceinline__ double fast_term(double acc, const AB* __restrict__ s
                                             const double* __restrict__ tab, int j, double X1, double X2, double magic) {
     const AB r = sh[j];
     double t;
-    if (MODE == MODE_CONST) t = fma(r.b, X1, r.a);                     // + C = k * x^2 through `magic`
-    else if (MODE == MODE_VARK) t = fma(shk[j], X2, fma(r.b, X1, r.a));
+    if (MODE == MODE_VARK) t = fma(shk[j], X2, fma(r.b, X1, r.a));
     else t = fma(r.b, fma(r.b, X2, X1), r.a);
     return exp_accumulate(acc, t, magic, tab);
 }
 
 // every lane walks `jn` consecutive records starting at its own base (full rounds: the same base for all lanes; the
 // last partial round: one base per lane group) -> scalar loop control, LDS addresses with immediate offsets, two
-// (or four) independent exp chains per iteration
-template <int MODE, int UNROLL = 2>
+// independent exp chains per iteration (MODE_VARK / MODE_DISC; MODE_CONST runs fast_accumulate_floor)
+template <int MODE>
 __device__ __forceinline__ double fast_accumulate_uniform(const AB* __restrict__ sh, const double* __restrict__ shk,
                                                           const double* __restrict__ tab, int jn_, double X1, double X2, double C) {
     const int jn = __builtin_amdgcn_readfirstlane(jn_);
     const ExpShift sft = exp_shift(C);
     double acc0 = 0.0, acc1 = 0.0;
     int j = 0;
-    if (UNROLL == 4) {                  // four chains: fewer LDS round trips per term; worth its registers in the heavy kernel only
-        double acc2 = 0.0, acc3 = 0.0;
-        for (; j + 4 <= jn; j += 4) {
-#ifdef LHVI_HEAVY_STAGED
-            if (MODE == MODE_CONST) {
-                const AB r0 = sh[j], r1 = sh[j + 1], r2 = sh[j + 2], r3 = sh[j + 3];
-                exp_accumulate4(acc0, acc1, acc2, acc3, fma(r0.b, X1, r0.a), fma(r1.b, X1, r1.a), fma(r2.b, X1, r2.a),
-                                fma(r3.b, X1, r3.a), sft.magic, tab);
-                continue;
-            }
-#endif
-            acc0 = fast_term<MODE>(acc0, sh, shk, tab, j, X1, X2, sft.magic);
-            acc1 = fast_term<MODE>(acc1, sh, shk, tab, j + 1, X1, X2, sft.magic);
-            acc2 = fast_term<MODE>(acc2, sh, shk, tab, j + 2, X1, X2, sft.magic);
-            acc3 = fast_term<MODE>(acc3, sh, shk, tab, j + 3, X1, X2, sft.magic);
-        }
-        acc0 += acc2; acc1 += acc3;
-    }
     for (; j + 2 <= jn; j += 2) {
         acc0 = fast_term<MODE>(acc0, sh, shk, tab, j, X1, X2, sft.magic);
         acc1 = fast_term<MODE>(acc1, sh, shk, tab, j + 1, X1, X2, sft.magic);
@@ -718,6 +699,7 @@ __device__ __forceinline__ double fast_accumulate_floor(const AB* __restrict__ s
     int j = 0;
     round_down_on();
     if (UNROLL == 4) {
+        // (the four table gathers issued back to back ahead of the polynomials lost in the round-to-nearest form: 11.75 -> 12.13-12.69 ms, profiles/HISTORY.md)
         double acc2 = 0.0, acc3 = 0.0;
         for (; j + 4 <= jn; j += 4) {
             const AB r0 = sh[j], r1 = sh[j + 1], r2 = sh[j + 2], r3 = sh[j + 3];
@@ -879,67 +861,7 @@ __global__ void __launch_bounds__(BLOCK) pbp_f2v_fast_kernel(lhvi_graph_t g, lhv
 // behind WORK_CHUNK edges -- and a workgroup that reaches its CU late (another kernel's workgroups held the slot) simply
 // finds less left to claim.  Without a ticket every wave strides over the list: a late workgroup then still owes its
 // full static share.
-#ifndef LHVI_PBP_TAIL_PER_WAVE
-#define LHVI_PBP_TAIL_PER_WAVE 0            // entries per wave of a part's tail zone (claimed one at a time); 0: chunks to the end.
-                                            // Measured on the 8-rank rehearsal (profiles/r05_experiments.md): 0 -> 0.875 ms per heavy launch,
-                                            // 2 -> 0.948, 8 -> 1.20: a claim per entry costs more than the shorter tail returns
-#endif
-#if LHVI_PBP_TAIL_PER_WAVE > 0
-template <int WORK_CHUNK, int WAVES_PER_BLOCK = BLOCK / WAVE>
-struct WorkCursor {
-    uint32_t* ticket;       // nullptr: static striding
-    int item, limit, left, stride, pending, lo, body, mid;
-    // A claim always advances the counter by WORK_CHUNK.  The first `body` positions of a part are real entries, claimed
-    // WORK_CHUNK at a time; behind them every claim stands for ONE entry of the part's tail zone [mid, limit): a wave that
-    // comes late then owes one entry, not a whole chunk -- a launch ends with the tail of a single entry per wave (what
-    // matters when a shard's list gives a wave only a few chunks), for one atomic per entry on ~2 entries per wave only.
-    __device__ __forceinline__ int claim(int lane) const {
-        int v = 0;
-        if (lane == 0) v = (int)atomicAdd(ticket, (uint32_t)WORK_CHUNK);
-        return v;                                           // a position, valid in lane 0
-    }
-    __device__ __forceinline__ int entry_of(int pos) const { return pos < body ? lo + pos : mid + (pos - body) / WORK_CHUNK; }
-    __device__ __forceinline__ int chunk_of(int pos) const { return pos < body ? WORK_CHUNK - 1 : 0; }       // entries left after the first
-    // with tickets the list is cut into one contiguous range per XCD (workgroup i runs on XCD i mod 8, and each XCD has
-    // its own L2: its waves then walk one region of the descriptors, particles and messages), each with its own counter
-    __device__ __forceinline__ bool start(uint32_t* base, int nitems, int lane) {
-        stride = gridDim.x * WAVES_PER_BLOCK;
-        left = 0; pending = 0; lo = 0; limit = nitems; body = 0; mid = 0;
-        ticket = base;
-        if (ticket) {
-            const int parts = min((int)gridDim.x, LHVI_PBP_TICKET_COUNTERS);
-            const int part = blockIdx.x % parts;
-            const int per = ((nitems + parts - 1) / parts + WORK_CHUNK - 1) / WORK_CHUNK * WORK_CHUNK;
-            lo = min(part * per, nitems);
-            limit = min(lo + per, nitems);
-            const int waves = (gridDim.x + parts - 1) / parts * WAVES_PER_BLOCK;          // waves that draw from this counter
-            const int tail = min(limit - lo, LHVI_PBP_TAIL_PER_WAVE * waves);
-            body = (limit - lo - tail) / WORK_CHUNK * WORK_CHUNK;
-            mid = lo + body;
-            ticket = base + part;
-            const int first = __builtin_amdgcn_readfirstlane(claim(lane));
-            item = entry_of(first);
-            left = chunk_of(first);
-            pending = claim(lane);
-        } else {
-            item = blockIdx.x * WAVES_PER_BLOCK + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-        }
-        return item < limit;
-    }
-    __device__ __forceinline__ int next() const {           // the entry after `item` (>= limit: none)
-        if (!ticket) return item + stride;
-        return left > 0 ? item + 1 : entry_of(__builtin_amdgcn_readfirstlane(pending));
-    }
-    __device__ __forceinline__ void advance(int nxt, int lane) {     // move to `nxt` = next()
-        if (ticket) {
-            if (left > 0) --left;
-            else { left = chunk_of(__builtin_amdgcn_readfirstlane(pending)); pending = claim(lane); }
-        }
-        item = nxt;
-    }
-};
-#else
-// (no tail zone: the cursor of rounds 2-4, without the position arithmetic of the form above)
+// (a tail zone of one-entry claims lost: 0.875 -> 0.948 ms per heavy launch, profiles/r05_experiments.md item 1)
 template <int WORK_CHUNK, int WAVES_PER_BLOCK = BLOCK / WAVE>
 struct WorkCursor {
     uint32_t* ticket;       // nullptr: static striding
@@ -982,7 +904,6 @@ struct WorkCursor {
         item = nxt;
     }
 };
-#endif
 
 struct HeavyData { double y, m, x0, x1; };
 
@@ -996,9 +917,8 @@ struct HeavyData { double y, m, x0, x1; };
 #ifndef LHVI_HEAVY_UNROLL
 #define LHVI_HEAVY_UNROLL 4
 #endif
-#ifndef LHVI_HEAVY_FLOOR
-#define LHVI_HEAVY_FLOOR 1          // term loops in the floor form (exp_accumulate_floor); 0: the round-to-nearest form
-#endif
+// (term loops in the floor form, exp_accumulate_floor: 11.79 -> 11.14-11.20 ms per launch against the round-to-nearest form,
+// profiles/r03_experiments.md)
 constexpr int HEAVY_BLOCK = LHVI_HEAVY_BLOCK;
 
 // ---- integral points on a uniform grid: sum_j exp(a_j + b_j x_t) for t < 32 with lane = partner particle j ------------
@@ -1225,13 +1145,9 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
                 mine.a = (d.ay * y + d.by) * y + d.c + h.m;
                 mine.b = d.axy * y + d.bx;
             }
-#if LHVI_HEAVY_FLOOR
             AB scaled;                                     // the term loops read the records in units of the table step
             scaled.a = mine.a * LHVI_EXP_INV_STEP; scaled.b = mine.b * LHVI_EXP_INV_STEP;
             sh[lane] = scaled;
-#else
-            sh[lane] = mine;
-#endif
         }
         LHVI_WAVE_SYNC();
         if (grid_path) {
@@ -1246,32 +1162,15 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
         if (grid_path) {
             double gv = exp_core(fma(mine.b, d.gx0, mine.a), sh_tab);
             const double q = exp_core(mine.b * d.gh, sh_tab);
-#ifdef LHVI_DIAG_SITE_MOMENTS          // timing aid (never defined in the product build): what forming the 'simple' rule's site in this epilogue would cost
-            double mz = 0.0, ma = 0.0, mb = 0.0;
-#endif
+            // (forming the 'simple' rule's site moments in this epilogue would cost 10.67 -> 11.26 ms, profiles/r03_experiments.md)
             for (int t0 = 0; t0 < d.T; t0 += 32) {
                 const double sum = grid_sums32(gv, q, lane);
                 const int t = t0 + grid_owned_point(lane);
                 if (t < d.T && !(lane & 1)) {
                     const double xt = fma((double)t, d.gh, d.gx0);
                     out[n + t] = sum > 0.0 ? fma(kconst * xt, xt, log_table(sum, sh_log)) : -700.0;
-#ifdef LHVI_DIAG_SITE_MOMENTS
-                    const double w = sum * exp_core(kconst * xt * xt, sh_tab);      // = exp(message at x_t)
-                    mz += w; ma += w * xt; mb += w * (xt * xt);
-#endif
                 }
             }
-#ifdef LHVI_DIAG_SITE_MOMENTS
-            {
-                mz = wave_sum(mz); ma = wave_sum(ma); mb = wave_sum(mb);
-                const double rz = rcp_newton(mz);
-                const double mu = ma * rz;
-                double sig = mb * rz - mu * mu;
-                sig = fmax(sig, s.var_threshold * 4.0);
-                // (stored only under a condition no run meets: the arithmetic has to happen, the site array stays the proposal kernel's)
-                if (lane == 0 && mz < -1.0) { out[0] = mu; out[1] = sig; }
-            }
-#endif
         } else if (eligible) {
             // an exponent too close to the double range somewhere on the grid: the direct form, points fetched here
 #pragma nounroll
@@ -1282,11 +1181,7 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
                 const bool valid = pl < rem;
                 const double X1 = valid ? g.dom_val[d.gb + t0 + pl] : 0.0, C = kconst * X1 * X1;
                 const int chunk = (s.flags & LHVI_PBP_SKIP_TERMS) ? 0 : (nj + split - 1) >> (6 - lw);
-#if LHVI_HEAVY_FLOOR
                 double acc = fast_accumulate_floor<LHVI_HEAVY_UNROLL>(sh + sub * chunk, sh_tab, chunk, X1, C);
-#else
-                double acc = fast_accumulate_uniform<MODE_CONST, LHVI_HEAVY_UNROLL>(sh + sub * chunk, nullptr, sh_tab, chunk, X1, 0.0, C);
-#endif
                 for (int off = width; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
                 if (valid && sub == 0) out[n + t0 + pl] = acc > 0.0 ? log_table(acc, sh_log) : -700.0;
             }
@@ -1302,11 +1197,7 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
             const double xv = r == 0 ? x0 : x1;
             const double X1 = valid ? xv : 0.0, C = kconst * X1 * X1;
             const int chunk = (s.flags & LHVI_PBP_SKIP_TERMS) ? 0 : (nj + split - 1) >> (6 - lw);   // flag 16: tuning aid, skips the term loop
-#if LHVI_HEAVY_FLOOR
             double acc = fast_accumulate_floor<LHVI_HEAVY_UNROLL>(sh + sub * chunk, sh_tab, chunk, X1, C);
-#else
-            double acc = fast_accumulate_uniform<MODE_CONST, LHVI_HEAVY_UNROLL>(sh + sub * chunk, nullptr, sh_tab, chunk, X1, 0.0, C);
-#endif
             for (int off = width; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
             if (valid && sub == 0) out[p < np ? p : n + (p - np)] = acc > 0.0 ? log_table(acc, sh_log) : -700.0;
         }
@@ -1326,15 +1217,9 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
 // cross-lane reduction is needed at all, and every load, store and wait is shared by 64 / W edges.  Same term arithmetic as the
 // heavy kernel's direct form (fast_accumulate_floor): an edge gets the same message from either kernel up to the order of the sum
 // when the heavy kernel splits a short round across lane groups.
-#ifndef LHVI_SMALL_HOIST
-#define LHVI_SMALL_HOIST 2          // 0: round 4's loads (a global round trip per descriptor piece and per round); 1: two round trips per step;
-#endif                              // 2: + the next step's descriptor touched a step ahead (scripts/diag/small_hoist.sh: 2.71 / 2.55 / 2.51 ms at n = 16)
-#ifndef LHVI_SMALL_GRID
-#define LHVI_SMALL_GRID 1         // integral points on a uniform grid by the recurrence along the grid (0: one exponential per point and particle)
-#endif
-#ifndef LHVI_SMALL_PAD
-#define LHVI_SMALL_PAD 1          // a group's block of W 16-byte records starts one record further than W records after the one before it:
-#endif                            // unpadded, record j of every group lies in the same four banks
+// (measured at n = 16, profiles/r05_experiments.md item 7: two global round trips per step and the next descriptor touched a step
+// ahead against one round trip per descriptor piece and per round, 2.71 -> 2.51 ms; integral points by the recurrence along the grid
+// against one exponential per point and particle, 2.57 -> 1.97 ms; padded record blocks, 2.55 -> 2.51 ms)
 #ifndef LHVI_SMALL_WAVES
 #define LHVI_SMALL_WAVES 6
 #endif
@@ -1355,7 +1240,8 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
                                                             double* __restrict__ f2v, const FastDesc* __restrict__ descs, int nitems) {
     using Geo = SmallGeom<W>;
     constexpr int G = Geo::G;                                // edges per wavefront
-    constexpr int GS = PPL * W + LHVI_SMALL_PAD;              // records between two groups' blocks (padded: see LHVI_SMALL_PAD)
+    constexpr int GS = PPL * W + 1;                          // records between two groups' blocks (padded by one: else record j of every group
+                                                             // lies in the same four banks)
     // (a group width that is not a power of two: the partial sums of the grid recurrence use the records' space once the
     // direct rounds are through with them -- DS operations of a wavefront execute in order)
     constexpr int SH_AB = G * GS > Geo::BUF_AB ? G * GS : Geo::BUF_AB;
@@ -1378,7 +1264,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
     for (int step = blockIdx.x * (BLOCK / WAVE) + wid; step < nsteps; step += nwaves) {
         const int idx = step * G + grp;
         const bool live = idx < nitems && lane_ok;
-#if LHVI_SMALL_HOIST
         // One round trip for the descriptor (all 128 bytes at once, whatever the branches below use of it), one for everything it
         // points to: the partner's particles and message and the output points of the first three rounds (all of them for
         // n + T <= 3 W), loaded without branches from addresses clamped into their rows.  A round that loads its own points, or a
@@ -1390,11 +1275,9 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
 #pragma unroll
             for (int k = 0; k < (int)(sizeof(FastDesc) / 16); ++k) u.q[k] = dp[k];
         }
-#if LHVI_SMALL_HOIST >= 2
         // the next step's descriptor (one 128-byte line, streamed from HBM) is touched now, so that its read at the head of the
         // next step finds it in the cache; the word is consumed at the end of this step
         const int touch = reinterpret_cast<const int*>(descs + min((step + nwaves) * G + grp, nitems - 1))[0];
-#endif
         const FastDesc& d = u.d;
         const int e = d.e, tv = d.tv, nj = d.nj, np = d.np, T = d.T, gb = d.gb;
         const double pval = d.pval, kx = d.kx;
@@ -1413,17 +1296,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
             xs[r] = *src;
         }
         const bool hidden_partner = is_hidden(pval);
-#else
-        static_assert(PPL == 1, "the round-4 loads know one particle per lane");
-        const FastDesc& d = descs[live ? idx : nitems - 1];  // (a group past the end repeats the last entry and stores nothing)
-        const int e = d.e, tv = d.tv, nj = d.nj, np = d.np, T = d.T, gb = d.gb;
-        const double pval = d.pval, kx = d.kx;
-        const int npts = np + T;
-        // staging: lane = partner particle of its group's edge
-        const bool hidden_partner = is_hidden(pval);
-        double yl[1] = {pval}, ml[1] = {0.0};
-        if (gl < nj && hidden_partner) { yl[0] = s.old_particles[(int64_t)d.pv * n + gl]; ml[0] = v2f[(int64_t)d.pce * n + gl]; }
-#endif
         double ua[PPL], ub[PPL];
         AB rec[PPL];
 #pragma unroll
@@ -1436,7 +1308,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
             }
             rec[pp].a = ua[pp] * LHVI_EXP_INV_STEP; rec[pp].b = ub[pp] * LHVI_EXP_INV_STEP;      // (records in units of the table step: floor form)
         }
-#if LHVI_SMALL_GRID
         // Integral points on a uniform grid: the recurrence of the heavy kernel inside the lane group (small_grid_sums32), when every
         // exponent of the edge stays far inside the double range over the whole grid -- a property of the edge alone, so an edge
         // gets the same bits whatever shares its wavefront.  A group that fails the test takes the direct rounds for all its points.
@@ -1455,9 +1326,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
         }
         const int lim = gok ? np : npts;                           // points of this group's edge that the direct rounds serve
         const bool any_grid = __ballot(gok && live) != 0;
-#else
-        const int lim = npts;
-#endif
         // the longest record list and the most output points of the wave's edges (wave-uniform loop bounds)
         int jmax = 0, pmax = 0;
 #pragma unroll
@@ -1473,7 +1341,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
             for (int pp = 0; pp < PPL; ++pp) sh[grp * GS + gl + pp * W] = rec[pp];
         }
         LHVI_WAVE_SYNC();
-#if LHVI_SMALL_HOIST
         // the three prefetched rounds written out: each waits for ITS points only (loads return in order), not -- as a loop whose
         // later rounds load their own points makes the compiler assume -- for everything in flight, the previous round's stores included
         // (the three loads were issued together and arrive together: taking all of them here costs nothing, and no later round then
@@ -1491,10 +1358,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
         }
 #pragma unroll 1
         for (int p0 = 3 * W; p0 < pmax; p0 += W) {
-#else
-#pragma unroll 1
-        for (int p0 = 0; p0 < pmax; p0 += W) {
-#endif
             const int p = p0 + gl;
             const bool valid = live && p < lim;
             double x = 0.0;
@@ -1502,7 +1365,6 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
             const double acc = fast_accumulate_floor<4, true>(mine_recs, sh_tab, jmax, x, kx * x * x);
             if (valid) out[p < np ? p : n + (p - np)] = acc > 0.0 ? log_table(acc, sh_log) : -700.0;
         }
-#if LHVI_SMALL_GRID
         if (any_grid) {
             double gv[PPL], q[PPL];
 #pragma unroll
@@ -1560,10 +1422,7 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(PPL 
                 }
             }
         }
-#endif
-#if LHVI_SMALL_HOIST >= 2
         asm volatile("" :: "v"(touch));
-#endif
     }
 }
 
@@ -1667,9 +1526,6 @@ struct PairDesc {
 static_assert(sizeof(PairDesc) == LHVI_PBP_DESC_BYTES, "PairDesc is part of the ABI (LHVI_PBP_DESC_BYTES)");
 
 struct PairData { double x0, x1, m0, m1, y, mj; };
-#ifndef LHVI_PAIR_AHEAD
-#define LHVI_PAIR_AHEAD 1          // (two entries ahead costs a wave slot to the scalar registers: 1.12 -> 1.18 ms, scripts/diag/pair_ahead.sh)
-#endif
 
 __device__ __forceinline__ PairData pair_fetch(const PairDesc& d, const lhvi_graph_t& g, const lhvi_pbp_t& s,
                                                const double* __restrict__ v2f, int lane) {
@@ -1700,28 +1556,19 @@ __global__ void __launch_bounds__(BLOCK) pbp_f2v_pair_kernel(lhvi_graph_t g, lhv
     const int lane = threadIdx.x & 63;
     const int last = nitems - 1;
     const int n = s.n, S = s.n + s.T;
-    // static striding, descriptors TWO entries ahead: an iteration is short (a few hundred instructions), so a descriptor requested at
-    // its head and needed at once for the next entry's loads -- as in the heavy kernel, whose iterations are fifty times longer --
-    // would put a scalar load's full latency (the list streams from HBM) into every iteration
+    // static striding, the next entry's descriptor requested at the head of this one (two entries ahead costs a wave slot to the
+    // scalar registers: 1.12 -> 1.18 ms, profiles/r05_experiments.md item 7)
     const int stride = gridDim.x * (BLOCK / WAVE);
     int item = blockIdx.x * (BLOCK / WAVE) + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     if (item >= nitems) return;
     struct { int32_t e_c, e_d, np_c, T, ns; double val_c, A0, b0, c0, A1, b1, c1; } d;
     PairDesc dn = descs[item];
-#if LHVI_PAIR_AHEAD >= 2
-    PairDesc dn2 = descs[__builtin_amdgcn_readfirstlane(min(item + stride, last))];
-#endif
     PairData h = pair_fetch(dn, g, s, v2f, lane);
     for (;;) {
         d.e_c = dn.e_c; d.e_d = dn.e_d; d.np_c = dn.np_c; d.T = dn.T; d.ns = dn.ns; d.val_c = dn.val_c;
         d.A0 = dn.A0; d.b0 = dn.b0; d.c0 = dn.c0; d.A1 = dn.A1; d.b1 = dn.b1; d.c1 = dn.c1;
         const bool more = item + stride < nitems;
-#if LHVI_PAIR_AHEAD >= 2
-        dn = dn2;
-        dn2 = descs[__builtin_amdgcn_readfirstlane(min(item + 2 * stride, last))];
-#else
         dn = descs[__builtin_amdgcn_readfirstlane(min(item + stride, last))];
-#endif
         const PairData cur = h;
         if (more) h = pair_fetch(dn, g, s, v2f, lane);
         if (d.e_c >= 0) {
@@ -1755,9 +1602,6 @@ __global__ void __launch_bounds__(BLOCK) pbp_f2v_pair_kernel(lhvi_graph_t g, lhv
     }
 }
 
-#ifndef LHVI_PAIR_SMALL
-#define LHVI_PAIR_SMALL 1
-#endif
 // PAIRS with FEW particles (every variable of the run has at most W = 16, 20 or 32: lhvi_pbp_t.n <= W): floor(64 / W) list entries per
 // wavefront, a lane group of W lanes each -- the one-entry-per-wave kernel above keeps 48 of 64 lanes busy for two exponentials
 // and then waits for its own loads.  Same expressions per output point, and the sums over the continuous variable's particles
@@ -2857,11 +2701,8 @@ __global__ void __launch_bounds__(BLOCK) pbp_resample_uniq_kernel(lhvi_graph_t g
             // (a half whose own variable needs no draw repeats the other's blocks: the swap below then leaves that row intact)
             const int mine = (lane >> 5) ? (cont[1] ? vv[1] : vv[0]) : (cont[0] ? vv[0] : vv[1]);
             double zc, zs;
-#ifdef LHVI_DIAG_NO_PHILOX                                     // timing aid (scripts/diag/resample_time.py): never defined in the product build
-            zc = 1e-3 * lane + mine; zs = -zc;
-#else
+            // (the listed sampler without the masks below: 0.80 -> 0.67 ms, without the draws too: 0.50 ms, profiles/r03_experiments.md)
             philox_normal_pair(seed, gid ? (uint64_t)gid[mine] : (uint64_t)mine, (uint32_t)(lane & 31), iteration, sh_log, zc, zs);
-#endif
             // v_permlane32_swap a, b: a's upper half <-> b's lower half: a = (cos | sin) of the first variable, b of the second
             auto plo = __builtin_amdgcn_permlane32_swap(__double2loint(zc), __double2loint(zs), false, false);
             auto phi = __builtin_amdgcn_permlane32_swap(__double2hiint(zc), __double2hiint(zs), false, false);
@@ -2888,11 +2729,6 @@ __global__ void __launch_bounds__(BLOCK) pbp_resample_uniq_kernel(lhvi_graph_t g
                 xlo[h] = __double2loint(x); xhi[h] = __double2hiint(x);
             }
         }
-#ifdef LHVI_DIAG_NO_UNIQ                                           // timing aid, as above
-#pragma unroll
-        for (int h = 0; h < 2; ++h) if (cont[h] && lane < n) uniq[(int64_t)vv[h] * n + lane] = (uint8_t)(lane < cnt[h]);
-        continue;
-#endif
         if (LISTED && (s.flags & LHVI_PBP_NO_UNIQ)) continue;      // particles only (ghost variables: nobody reads their masks here)
         if (!(cont[0] || cont[1])) continue;
         // first-occurrence masks of the (up to two) drawn rows, in step so that the LDS round trips are paid once.  Pass 1 only
@@ -3047,12 +2883,9 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
             hold_chunk(c);
 #pragma unroll
             for (int i = 0; i < CH; ++i) ee[i] = __shfl(my_e, first_lane + i);
+            // (rows read as from a slot-ordered table: 1.90 -> 1.94 ms at n = 10, 3.06 -> 2.95 at n = 20, profiles/r05_experiments.md item 16)
 #pragma unroll
-#ifdef LHVI_DIAG_FUSED_SLOT_ROWS          // timing aid (never defined in the product build): the rows of a variable read as if the table were in slot order
-            for (int i = 0; i < CH; ++i) mm[i] = f2v[(int64_t)(lo + min(c * CH + i, max(deg - 1, 0))) * S + (valid ? j : 0)];
-#else
             for (int i = 0; i < CH; ++i) mm[i] = f2v[(int64_t)ee[i] * S + (valid ? j : 0)];        // (beyond the row: edge 0's row, never used)
-#endif
         };
         for (int c = 0; c < nch; ++c) {
             load_rows(c);
@@ -3119,14 +2952,8 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
             }
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
-#ifdef LHVI_DIAG_FUSED_SLOT_ROWS
-                const int ks = min(c * CH + (p0 + i) * SL + sub, max(deg - 1, 0));
-                const double* msg = f2v + (int64_t)(lo + ks) * S + n;
-                b0[i] = eta[2 * (lo + ks)]; b1[i] = eta[2 * (lo + ks) + 1];
-#else
                 const double* msg = f2v + (int64_t)ee[i] * S + n;
                 b0[i] = eta[2 * ee[i]]; b1[i] = eta[2 * ee[i] + 1];
-#endif
                 g0[i] = msg[t0]; g1[i] = msg[t1];
             }
 #pragma unroll
@@ -3360,48 +3187,51 @@ int lhvi_pbp_f2v(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_
     static const int gen_per_cu = blocks_per_cu((const void*)pbp_f2v_generic_kernel<true>);
     static const int gen_slim_per_cu = blocks_per_cu((const void*)pbp_f2v_generic_kernel<false>);
     const int share = (s->flags & LHVI_PBP_SHARE_CUS) ? 1 : 0;          // a workgroup per CU left to the kernels of another stream
-    const int heavy_blocks = max(heavy_per_cu - share, 1), side_blocks = 8;
     // LEAVE_ROOM (sharded runs): every persistent grid stays cus/8 workgroups short of filling the device, so a collective's
     // copy kernels on another stream can become resident while these waves run (no kernel here ever waits on another
     // workgroup, so a full device could only delay such a kernel, never block it -- but a delayed collective is an exposed one)
     const int spare = (s->flags & LHVI_PBP_LEAVE_ROOM) ? max(cus / 8, 1) : 0;
-    // work ticket of the heavy kernel: reset on this stream right before the launch.  Chunks of 8 pay when every wave gets
-    // several of them; a short list (a small graph, the interior part of a shard) keeps one entry per wave and strides
-    const bool run_heavy = !(s->flags & LHVI_PBP_SKIP_FAST) && s->heavy_desc && s->n_heavy > 0 && !(s->flags & LHVI_PBP_SKIP_HEAVY);
-    constexpr int HWPB = HEAVY_BLOCK / WAVE;
-    const int heavy_grid = min((s->n_heavy + HWPB - 1) / HWPB, max(cus * heavy_blocks - spare * (BLOCK / WAVE) / HWPB, 1));
-    lhvi_pbp_t sh = *s;
-    if (sh.f2v_ticket && (int64_t)s->n_heavy < (int64_t)heavy_grid * HWPB * 8 * 4) sh.f2v_ticket = nullptr;
-    if (s->f2v_ticket && run_heavy && hipMemsetAsync(s->f2v_ticket, 0, LHVI_PBP_TICKET_WORDS * sizeof(uint32_t), as_stream(stream)) != hipSuccess)
-        return LHVI_E_LAUNCH;
-    if (!(s->flags & LHVI_PBP_SKIP_FAST)) {
-        if (s->heavy_desc && s->n_heavy > 0 && !(s->flags & LHVI_PBP_SKIP_HEAVY))
-            hipLaunchKernelGGL(pbp_f2v_heavy_kernel, dim3(heavy_grid), dim3(HEAVY_BLOCK), 0, as_stream(stream),
-                               *g, sh, v2f, f2v, reinterpret_cast<const FastDesc*>(s->heavy_desc), s->n_heavy,
-                               s->f2v_ticket ? s->f2v_ticket + LHVI_PBP_TICKET_COUNTERS : (uint32_t*)nullptr);
-        if (!(s->flags & LHVI_PBP_SKIP_HEAVY)) {
-            // lane groups as narrow as the particle count allows: 10 / 12 lanes, or 8 with two particles per lane, for the small16 list;
-            // 10 / 12 / 16 lanes with two particles per lane for small32
-            // (no variable holds more than s->n particles; LHVI_PBP_POW2_GROUPS keeps the 16- / 32-lane kernels)
-            const bool narrow = !(s->flags & LHVI_PBP_POW2_GROUPS);
-            if (s->small16_desc && s->n_small16 > 0) {
-                // (measured, scripts/diag/narrow_groups.sh + profiles/r05_experiments.md item 19: ten lanes beat two particles per lane in
-                // groups of five at n = 10 -- 1.42 against 1.46 ms, the five-lane build needs 107 registers and 34 KB of LDS -- and lose to
-                // groups of six at n = 12: 1.64 against 1.54 ms)
-                if (narrow && s->n <= 10) launch_f2v_small<10>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);
-                else if (narrow && s->n <= 12) launch_f2v_small<6, 2>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);
-                else if (narrow) launch_f2v_small<8, 2>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);   // 13-16 particles: eight edges per wavefront
-                else launch_f2v_small<16>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);
-            }
-            if (s->small32_desc && s->n_small32 > 0) {
-                // (two particles per lane: groups of 10 / 12 / 16 lanes for up to 20 / 24 / 32 particles)
-                if (narrow && s->n <= 20) launch_f2v_small<10, 2>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
-                else if (narrow && s->n <= 24) launch_f2v_small<12, 2>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
-                else if (narrow) launch_f2v_small<16, 2>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
-                else launch_f2v_small<32>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
-            }
+    // the short kernels: four items per workgroup, at most 8 workgroups per CU
+    auto short_grid = [&](int items, int per_cu) { return dim3(min((items + 3) / 4, max(cus * min(per_cu, 8) - spare, 1))); };
+    const uint32_t families = s->flags & LHVI_PBP_F2V_ALL;
+    auto want = [families](uint32_t family) { return families == 0 || (families & family) != 0; };
+    if (want(LHVI_PBP_F2V_HEAVY) && s->heavy_desc && s->n_heavy > 0) {
+        // work ticket of the heavy kernel: reset on this stream right before the launch.  Chunks of 8 pay when every wave gets
+        // several of them; a short list (a small graph, the interior part of a shard) keeps one entry per wave and strides
+        constexpr int HWPB = HEAVY_BLOCK / WAVE;
+        const int heavy_grid = min((s->n_heavy + HWPB - 1) / HWPB, max(cus * max(heavy_per_cu - share, 1) - spare * (BLOCK / WAVE) / HWPB, 1));
+        lhvi_pbp_t sh = *s;
+        if (sh.f2v_ticket && (int64_t)s->n_heavy < (int64_t)heavy_grid * HWPB * 8 * 4) sh.f2v_ticket = nullptr;
+        if (s->f2v_ticket && hipMemsetAsync(s->f2v_ticket, 0, LHVI_PBP_TICKET_WORDS * sizeof(uint32_t), as_stream(stream)) != hipSuccess)
+            return LHVI_E_LAUNCH;
+        hipLaunchKernelGGL(pbp_f2v_heavy_kernel, dim3(heavy_grid), dim3(HEAVY_BLOCK), 0, as_stream(stream),
+                           *g, sh, v2f, f2v, reinterpret_cast<const FastDesc*>(s->heavy_desc), s->n_heavy,
+                           s->f2v_ticket ? s->f2v_ticket + LHVI_PBP_TICKET_COUNTERS : (uint32_t*)nullptr);
+    }
+    if (want(LHVI_PBP_F2V_SMALL)) {
+        // lane groups as narrow as the particle count allows: 10 / 12 lanes, or 8 with two particles per lane, for the small16 list;
+        // 10 / 12 / 16 lanes with two particles per lane for small32
+        // (no variable holds more than s->n particles; LHVI_PBP_POW2_GROUPS keeps the 16- / 32-lane kernels)
+        const bool narrow = !(s->flags & LHVI_PBP_POW2_GROUPS);
+        if (s->small16_desc && s->n_small16 > 0) {
+            // (measured, scripts/diag/narrow_groups.sh + profiles/r05_experiments.md item 19: ten lanes beat two particles per lane in
+            // groups of five at n = 10 -- 1.42 against 1.46 ms, the five-lane build needs 107 registers and 34 KB of LDS -- and lose to
+            // groups of six at n = 12: 1.64 against 1.54 ms)
+            if (narrow && s->n <= 10) launch_f2v_small<10>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);
+            else if (narrow && s->n <= 12) launch_f2v_small<6, 2>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);
+            else if (narrow) launch_f2v_small<8, 2>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);   // 13-16 particles: eight edges per wavefront
+            else launch_f2v_small<16>(g, s, v2f, f2v, s->small16_desc, s->n_small16, cus, share, spare, stream);
         }
-        if (s->pair_desc && s->n_pair > 0 && !(s->flags & (LHVI_PBP_SKIP_LIGHT | LHVI_PBP_WIDE_PAIRS)) && s->n <= 32 && LHVI_PAIR_SMALL) {
+        if (s->small32_desc && s->n_small32 > 0) {
+            // (two particles per lane: groups of 10 / 12 / 16 lanes for up to 20 / 24 / 32 particles)
+            if (narrow && s->n <= 20) launch_f2v_small<10, 2>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
+            else if (narrow && s->n <= 24) launch_f2v_small<12, 2>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
+            else if (narrow) launch_f2v_small<16, 2>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
+            else launch_f2v_small<32>(g, s, v2f, f2v, s->small32_desc, s->n_small32, cus, share, spare, stream);
+        }
+    }
+    if (want(LHVI_PBP_F2V_PAIR)) {
+        if (s->pair_desc && s->n_pair > 0 && !(s->flags & LHVI_PBP_WIDE_PAIRS) && s->n <= 32) {
             // (every variable has at most s->n particles: four / three / two entries per wavefront.  Groups of 10 / 12 lanes for n <= 10 / 12
             // were measured too: 0.52 / 0.51 ms against 0.47-0.51 in groups of 16 -- the shuffles of their summation tree cost what six
             // or five entries per wavefront save; groups of 20 lanes for n <= 20: 0.65 against 0.77 ms in groups of 32)
@@ -3409,32 +3239,32 @@ int lhvi_pbp_f2v(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_
             if (s->n <= 16) launch_f2v_pair_small<16>(g, s, v2f, f2v, cus, spare, stream);
             else if (narrow_pairs && s->n <= 20) launch_f2v_pair_small<20>(g, s, v2f, f2v, cus, spare, stream);
             else launch_f2v_pair_small<32>(g, s, v2f, f2v, cus, spare, stream);
-        } else if (s->pair_desc && s->n_pair > 0 && !(s->flags & LHVI_PBP_SKIP_LIGHT)) {
+        } else if (s->pair_desc && s->n_pair > 0) {
             static const int pair_per_cu = blocks_per_cu((const void*)pbp_f2v_pair_kernel);
-            hipLaunchKernelGGL(pbp_f2v_pair_kernel, dim3(min((s->n_pair + 3) / 4, max(cus * min(pair_per_cu, side_blocks) - spare, 1))), dim3(BLOCK), 0,
-                               as_stream(stream), *g, *s, v2f, f2v, reinterpret_cast<const PairDesc*>(s->pair_desc), s->n_pair);
-        } else if (s->light_desc && s->n_light > 0 && !(s->flags & LHVI_PBP_SKIP_LIGHT))
-            hipLaunchKernelGGL(pbp_f2v_light_kernel, dim3(min((s->n_light + 3) / 4, max(cus * min(light_per_cu, side_blocks) - spare, 1))), dim3(BLOCK), 0, as_stream(stream),
+            hipLaunchKernelGGL(pbp_f2v_pair_kernel, short_grid(s->n_pair, pair_per_cu), dim3(BLOCK), 0, as_stream(stream),
+                               *g, *s, v2f, f2v, reinterpret_cast<const PairDesc*>(s->pair_desc), s->n_pair);
+        } else if (s->light_desc && s->n_light > 0)
+            hipLaunchKernelGGL(pbp_f2v_light_kernel, short_grid(s->n_light, light_per_cu), dim3(BLOCK), 0, as_stream(stream),
                                *g, *s, v2f, f2v, reinterpret_cast<const FastDesc*>(s->light_desc), s->n_light);
-        if (nfast > 0 && !(s->flags & LHVI_PBP_SKIP_LIGHT))
-            hipLaunchKernelGGL(pbp_f2v_fast_kernel, dim3(min((nfast + 3) / 4, max(cus * min(fast_per_cu, side_blocks) - spare, 1))), dim3(BLOCK), 0, as_stream(stream),
-                               *g, *pots, *s, v2f, f2v, reinterpret_cast<const FastDesc*>(s->fast_desc), pots->param);
     }
-    if (s->cq_desc && s->n_cq > 0 && !(s->flags & LHVI_PBP_SKIP_CQ)) {
+    if (want(LHVI_PBP_F2V_FAST) && nfast > 0)
+        hipLaunchKernelGGL(pbp_f2v_fast_kernel, short_grid(nfast, fast_per_cu), dim3(BLOCK), 0, as_stream(stream),
+                           *g, *pots, *s, v2f, f2v, reinterpret_cast<const FastDesc*>(s->fast_desc), pots->param);
+    if (want(LHVI_PBP_F2V_CQ) && s->cq_desc && s->n_cq > 0) {
         static const int cq_per_cu = blocks_per_cu((const void*)pbp_f2v_cq_kernel);
-        hipLaunchKernelGGL(pbp_f2v_cq_kernel, dim3(min((s->n_cq + 3) / 4, max(cus * min(cq_per_cu, side_blocks) - spare, 1))), dim3(BLOCK), 0,
-                           as_stream(stream), *g, *s, v2f, f2v, reinterpret_cast<const CqDesc*>(s->cq_desc), s->n_cq);
+        hipLaunchKernelGGL(pbp_f2v_cq_kernel, short_grid(s->n_cq, cq_per_cu), dim3(BLOCK), 0, as_stream(stream),
+                           *g, *s, v2f, f2v, reinterpret_cast<const CqDesc*>(s->cq_desc), s->n_cq);
     }
-    if (!(s->flags & LHVI_PBP_SKIP_GENERIC) && ngen > 0) {
+    if (want(LHVI_PBP_F2V_GENERIC) && ngen > 0) {
         int pts_log2 = s->generic_edges ? s->generic_pts_log2 : 6;
         if (pts_log2 < 0 || pts_log2 > 6) pts_log2 = 6;
         const int groups = (ngen + (64 >> pts_log2) - 1) / (64 >> pts_log2);
         if (pots->interpreted == 0)
-            hipLaunchKernelGGL(pbp_f2v_generic_kernel<false>, dim3(min((groups + 3) / 4, max(cus * min(gen_slim_per_cu, side_blocks) - spare, 1))), dim3(BLOCK), 0,
-                               as_stream(stream), *g, *pots, *s, v2f, f2v, pts_log2);
+            hipLaunchKernelGGL(pbp_f2v_generic_kernel<false>, short_grid(groups, gen_slim_per_cu), dim3(BLOCK), 0, as_stream(stream),
+                               *g, *pots, *s, v2f, f2v, pts_log2);
         else
-            hipLaunchKernelGGL(pbp_f2v_generic_kernel<true>, dim3(min((groups + 3) / 4, max(cus * min(gen_per_cu, side_blocks) - spare, 1))), dim3(BLOCK), 0,
-                               as_stream(stream), *g, *pots, *s, v2f, f2v, pts_log2);
+            hipLaunchKernelGGL(pbp_f2v_generic_kernel<true>, short_grid(groups, gen_per_cu), dim3(BLOCK), 0, as_stream(stream),
+                               *g, *pots, *s, v2f, f2v, pts_log2);
     }
     return check_launch();
 }

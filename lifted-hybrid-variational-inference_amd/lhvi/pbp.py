@@ -25,6 +25,16 @@ import numpy as np
 from . import _abi
 from .flat import flatten
 
+# Schedules of the f -> v half sweep (_ParticleSweep._launch_f2v): the lhvi_pbp_f2v calls in issue order, each as (stream, kernel
+# families, further flags, timed by f2v_events).  Every schedule names each family exactly once.
+_F2V_LONG = _abi.PBP_F2V_HEAVY | _abi.PBP_F2V_SMALL
+_F2V_SHORT = _abi.PBP_F2V_PAIR | _abi.PBP_F2V_FAST | _abi.PBP_F2V_CQ | _abi.PBP_F2V_GENERIC
+F2V_SCHEDULES = {
+    'one': (('main', _abi.PBP_F2V_ALL, 0, False),),
+    'timed': (('main', _F2V_LONG, 0, True), ('main', _F2V_SHORT, 0, False)),
+    'overlap': (('side', _F2V_SHORT, 0, False), ('main', _F2V_LONG, _abi.PBP_SHARE_CUS, True)),
+}
+
 
 class _ParticleSweep:
     var_threshold = 3
@@ -516,56 +526,50 @@ class _ParticleSweep:
             self._generate_sample()
             self._launch_f2v(self._struct(), f2v_events)
 
+    def _f2v_schedule(self, timed=False):
+        """the F2V_SCHEDULES key of this state's f -> v half sweep; `timed`: f2v_events are given"""
+        want = os.environ.get('LHVI_PBP_OVERLAP')                     # (tuning aid: scripts/diag/f2v_overlap.sh)
+        if (self.overlap_f2v or want == '1') and want != '0' and self.n_heavy >= self.overlap_min_heavy:
+            # the long kernels of the half sweep on this stream, one workgroup per CU short of a full device; the short kernels
+            # (pair / light, fast, cq, generic: other rows of f2v) on a second stream beside them.  The heavy kernel is bound
+            # by VALU issue and the LDS and indifferent to 6 or 7 waves per SIMD; the pair kernel waits for its loads most of its
+            # 1.1 ms -- side by side the second one costs next to nothing.
+            return 'overlap'
+        return 'timed' if timed else 'one'
+
     def _launch_f2v(self, s, f2v_events=None):
-        """the f -> v half sweep (`lhvi_pbp_f2v`).  `f2v_events`: (start, end) events recorded around the heavy kernel: the
-        call is then split with the SKIP flags into three, one kernel each, on the same stream."""
+        """the f -> v half sweep (`lhvi_pbp_f2v`) by the schedule of _f2v_schedule.  `f2v_events`: (start, end) events recorded
+        on this stream around the long kernels (heavy and small lists); the other families then run in a call of their own."""
         l, g, p, st = _abi.lib(), self.dg.g, self.dg.p, _abi.stream_ptr()
         if not getattr(self, '_has_f_side', True):
             raise _abi.LhviError('this state was set up for the v -> f half only (sides="v")')
         args = (_abi.ptr(self.v2f), _abi.ptr(self.f2v))
-        want = os.environ.get('LHVI_PBP_OVERLAP')                     # (tuning aid: scripts/diag/f2v_overlap.sh)
-        if (self.overlap_f2v or want == '1') and want != '0' and self.n_heavy >= self.overlap_min_heavy:
-            # the long kernel(s) of the half sweep on this stream, one workgroup per CU short of a full device; the short kernels
-            # (pair / light / cq / fast, then generic: other rows of f2v) on a second stream beside them.  The heavy kernel is bound
-            # by VALU issue and the LDS and indifferent to 6 or 7 waves per SIMD; the pair kernel waits for its loads most of its
-            # 1.1 ms -- side by side the second one costs next to nothing.
+        calls = F2V_SCHEDULES[self._f2v_schedule(bool(f2v_events))]
+        side = any(stream == 'side' for stream, _, _, _ in calls)
+        if side:
             torch = _abi.require_gpu()
             main = torch.cuda.current_stream()
             if getattr(self, '_side', None) is None:
                 self._side = torch.cuda.Stream(device=self.dg.device)
                 self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
-            base = s.flags
             self._fork.record(main)
             self._side.wait_event(self._fork)
-            with torch.cuda.stream(self._side):
-                sst = _abi.stream_ptr()
-                s.flags = base | _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_HEAVY
-                _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, sst))
-                s.flags = base | _abi.PBP_SKIP_FAST
-                _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, sst))
+        base = s.flags
+        for stream, families, extra, timed in calls:
+            s.flags = base | families | extra
+            if stream == 'side':
+                with torch.cuda.stream(self._side):
+                    _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, _abi.stream_ptr()))
                 self._join.record(self._side)
-            s.flags = base | _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_LIGHT | _abi.PBP_SHARE_CUS
-            if f2v_events:
+                continue
+            if timed and f2v_events:
                 f2v_events[0].record()
             _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, st))
-            if f2v_events:
+            if timed and f2v_events:
                 f2v_events[1].record()
+        s.flags = base
+        if side:
             main.wait_event(self._join)
-            s.flags = base
-            return
-        if f2v_events:
-            base = s.flags
-            s.flags = base | _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_LIGHT
-            f2v_events[0].record()
-            _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, st))
-            f2v_events[1].record()
-            s.flags = base | _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_HEAVY
-            _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, st))
-            s.flags = base | _abi.PBP_SKIP_FAST
-            _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, st))
-            s.flags = base
-        else:
-            _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, st))
 
     # ---- dict views with the reference's keys ------------------------------------------------------
     def _host(self, name):

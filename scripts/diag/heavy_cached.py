@@ -19,7 +19,7 @@ l, st, g, p = _abi.lib(), _abi.stream_ptr(), bp.dg.g, bp.dg.p
 
 
 def timed(name):
-    s = bp._struct(); s.flags |= _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_LIGHT | _abi.PBP_SKIP_CQ
+    s = bp._struct(); s.flags |= _abi.PBP_F2V_HEAVY | _abi.PBP_F2V_SMALL
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(5)]
     for a, b in ev:
         a.record(); _abi.check(l.lhvi_pbp_f2v(g, p, s, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)); b.record()

@@ -37,7 +37,7 @@ def var_half(stream_ptr, frac=1.0):
 
 def heavy(stream_ptr, share, frac=1.0, off=0.0):
     s = bp._struct()
-    s.flags |= _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_LIGHT | (_abi.PBP_SHARE_CUS if share else 0)
+    s.flags |= _abi.PBP_F2V_HEAVY | _abi.PBP_F2V_SMALL | (_abi.PBP_SHARE_CUS if share else 0)
     n0 = int(bp.n_heavy * off)
     s.heavy_desc, s.n_heavy = bp.heavy_desc.data_ptr() + n0 * 128, int(bp.n_heavy * frac)
     _abi.check(l.lhvi_pbp_f2v(g, p, s, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), stream_ptr))

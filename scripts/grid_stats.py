@@ -23,7 +23,7 @@ for sweep in (1, 5, 20):
     while bp._draws - 1 < sweep:
         run.sweep()
     s = bp._struct()
-    s.flags |= _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_LIGHT
+    s.flags |= _abi.PBP_F2V_HEAVY | _abi.PBP_F2V_SMALL
     ms = {}
     res = {}
     for name, extra in (('grid', 0), ('direct', _abi.PBP_NO_GRID)):

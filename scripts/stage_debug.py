@@ -32,8 +32,8 @@ _abi.check(l.lhvi_pbp_resample(bp.dg.g, bp._struct(), None, 5, 0, _abi.ptr(bp.pa
 say('uniq'); _abi.check(l.lhvi_pbp_uniq(bp.dg.g, n, _abi.ptr(bp.particles), _abi.ptr(bp.np_dev), _abi.ptr(bp.uniq), st)); torch.cuda.synchronize(); say(' ok')
 say('v2f'); _abi.check(l.lhvi_pbp_v2f(bp.dg.g, bp._struct(), _abi.ptr(bp.f2v), _abi.ptr(bp.v2f), st)); torch.cuda.synchronize(); say(' ok')
 say('proposal'); _abi.check(l.lhvi_pbp_proposal(bp.dg.g, bp._struct(), _abi.ptr(bp.f2v), _abi.ptr(bp.eta), _abi.ptr(bp.q_dev), st)); torch.cuda.synchronize(); say(' ok')
-s = bp._struct(); s.flags |= _abi.PBP_SKIP_GENERIC
+s = bp._struct(); s.flags |= _abi.PBP_F2V_ALL & ~_abi.PBP_F2V_GENERIC
 say('f2v fast'); _abi.check(l.lhvi_pbp_f2v(bp.dg.g, bp.dg.p, s, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)); torch.cuda.synchronize(); say(' ok')
-s = bp._struct(); s.flags |= _abi.PBP_SKIP_FAST
+s = bp._struct(); s.flags |= _abi.PBP_F2V_GENERIC
 say('f2v generic'); _abi.check(l.lhvi_pbp_f2v(bp.dg.g, bp.dg.p, s, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)); torch.cuda.synchronize(); say(' ok')
 say('done')

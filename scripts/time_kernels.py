@@ -35,15 +35,15 @@ tot = 0
 tot += timed('v2f', lambda: _abi.check(l.lhvi_pbp_v2f(g, s, _abi.ptr(bp.f2v), _abi.ptr(bp.v2f), st)))
 tot += timed('proposal', lambda: _abi.check(l.lhvi_pbp_proposal(g, s, _abi.ptr(bp.f2v), _abi.ptr(bp.eta), _abi.ptr(bp.q_dev), st)))
 tot += timed('resample+uniq', lambda: _abi.check(l.lhvi_pbp_resample_uniq(g, s, None, 1, 3, _abi.ptr(bp.particles), _abi.ptr(bp.uniq), st)))
-sf = bp._struct(); sf.flags |= _abi.PBP_SKIP_GENERIC
+sf = bp._struct(); sf.flags |= _abi.PBP_F2V_ALL & ~_abi.PBP_F2V_GENERIC
 tot += timed('f2v fast', lambda: _abi.check(l.lhvi_pbp_f2v(g, p, sf, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)))
-sh = bp._struct(); sh.flags |= _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_LIGHT
+sh = bp._struct(); sh.flags |= _abi.PBP_F2V_HEAVY | _abi.PBP_F2V_SMALL
 timed('  f2v heavy', lambda: _abi.check(l.lhvi_pbp_f2v(g, p, sh, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)))
-sl = bp._struct(); sl.flags |= _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_HEAVY
+sl = bp._struct(); sl.flags |= _abi.PBP_F2V_PAIR | _abi.PBP_F2V_FAST | _abi.PBP_F2V_CQ
 timed('  f2v light', lambda: _abi.check(l.lhvi_pbp_f2v(g, p, sl, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)))
-sn = bp._struct(); sn.flags |= _abi.PBP_SKIP_GENERIC | _abi.PBP_SKIP_TERMS
+sn = bp._struct(); sn.flags |= (_abi.PBP_F2V_ALL & ~_abi.PBP_F2V_GENERIC) | _abi.PBP_SKIP_TERMS
 timed('f2v fast (no term loop)', lambda: _abi.check(l.lhvi_pbp_f2v(g, p, sn, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)))
-sg = bp._struct(); sg.flags |= _abi.PBP_SKIP_FAST
+sg = bp._struct(); sg.flags |= _abi.PBP_F2V_GENERIC
 tot += timed('f2v generic', lambda: _abi.check(l.lhvi_pbp_f2v(g, p, sg, _abi.ptr(bp.v2f), _abi.ptr(bp.f2v), st)))
 print('joint terms %.4g wave-terms %.4g' % (run.f2v_joint_terms(), run.f2v_joint_terms() / 64))
 print('sum %.3f ms -> %.1f sweeps/s at 10M edges' % (tot, 1e3 / (tot * 1e7 / flat.E)))

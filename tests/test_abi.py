@@ -66,6 +66,33 @@ def test_structs_match_header_layout(built):
         assert names == [f[0] for f in struct._fields_], cname
 
 
+def test_f2v_schedules_launch_every_kernel_family_once():
+    """every schedule of the f -> v half sweep (lhvi/pbp.py::F2V_SCHEDULES) names each kernel family of lhvi_pbp_f2v in exactly
+    one of its calls; the family bits are the header's and no other flag's"""
+    from lhvi import _abi
+    from lhvi.pbp import F2V_SCHEDULES
+    header = open(os.path.join(ROOT, 'include', 'lhvi.h')).read()
+    families = [getattr(_abi, 'PBP_F2V_' + name) for name in ('HEAVY', 'SMALL', 'PAIR', 'FAST', 'CQ', 'GENERIC')]
+    flags = {name: int(v) for name, v in re.findall(r'#define\s+LHVI_PBP_([A-Z0-9_]+)\s+(\d+)u\b', header)}
+    for name in ('HEAVY', 'SMALL', 'PAIR', 'FAST', 'CQ', 'GENERIC'):
+        assert flags.pop('F2V_' + name) == getattr(_abi, 'PBP_F2V_' + name), name
+    assert all(f & (f - 1) == 0 for f in families) and sum(families) == _abi.PBP_F2V_ALL    # six distinct bits
+    assert not any(v & _abi.PBP_F2V_ALL for v in flags.values())
+    assert sorted(F2V_SCHEDULES) == ['one', 'overlap', 'timed']
+    for name, calls in F2V_SCHEDULES.items():
+        masks = [fam for _, fam, _, _ in calls]
+        for i, m in enumerate(masks):
+            assert m and not (m & ~_abi.PBP_F2V_ALL), name
+            for other in masks[i + 1:]:
+                assert not (m & other), name
+        covered = 0
+        for m in masks:
+            covered |= m
+        assert covered == _abi.PBP_F2V_ALL, name
+        assert not any(extra & _abi.PBP_F2V_ALL for _, _, extra, _ in calls), name
+        assert sum(timed for _, _, _, timed in calls) <= 1 and all(stream in ('main', 'side') for stream, _, _, _ in calls), name
+
+
 def test_no_cpu_fallback_without_gpu():
     from conftest import has_gpu
     if has_gpu():

@@ -1105,31 +1105,55 @@ def test_packed_pair_kernel_equals_the_one_entry_per_wave_kernel(api, n):
     assert bool(torch.isfinite(a.f2v).all())
 
 
-def test_f2v_half_sweep_on_two_streams_gives_the_same_bits(api, monkeypatch):
-    """``EPBP.overlap_f2v``: the heavy kernel on the caller's stream (LHVI_PBP_SHARE_CUS: a workgroup per CU left free) and the pair /
-    generic kernels beside it on a second stream write disjoint rows of f2v -- every array of the state after whole sweeps equals
-    the one-stream run's bit for bit, and the next v -> f half waits for both streams"""
+def _f2v_schedule_run(api, monkeypatch, graph, schedule):
+    """whole sweeps with the f -> v half sweep issued by one schedule of lhvi/pbp.py::F2V_SCHEDULES; `graph` 'mrf': heavy and pair
+    lists, 'hmln': the paper-popularity MLN, whose conditionally quadratic formulas fill the cq list"""
     import torch
     from lhvi import synth
     from lhvi.pbp import EPBP
-    runs = []
-    for overlap in ('1', '0'):
-        monkeypatch.setenv('LHVI_PBP_OVERLAP', overlap)
+    monkeypatch.setenv('LHVI_PBP_OVERLAP', '1' if schedule == 'overlap' else '0')
+    if graph == 'mrf':
         flat = synth.hybrid_mrf_flat(V=30000, deg=4, seed=8, frac_discrete=0.3)
-        bp = EPBP(None, n=64, proposal_approximation='EP', sampler='device', seed=9)
-        bp.overlap_min_heavy = 1
-        bp._setup(None, flat=flat)
+    else:
+        flat, _ = synth.paper_popularity_flat(150, 4, seed=2)
+    bp = EPBP(None, n=64, proposal_approximation='EP', sampler='device', seed=9)
+    bp.overlap_min_heavy = 0
+    bp._setup(None, flat=flat)
+    if graph == 'mrf':
         assert bp.n_heavy > 0 and bp.n_pair > 0
-        _init(api, bp)
-        for _ in range(5):
-            bp.sweep(last=False)
-        bp.sweep(last=True)
-        torch.cuda.synchronize()
-        runs.append(bp)
-    a, b = runs
-    assert getattr(a, '_side', None) is not None and getattr(b, '_side', None) is None
-    for name in ('f2v', 'v2f', 'q_dev', 'eta', 'particles'):
-        assert torch.equal(getattr(a, name), getattr(b, name)), name
+    else:
+        assert bp.n_cq > 0
+    _init(api, bp)
+    events = (torch.cuda.Event(), torch.cuda.Event()) if schedule == 'timed' else None
+    for _ in range(5):
+        bp.sweep(last=False, f2v_events=events)
+    bp.sweep(last=True)
+    torch.cuda.synchronize()
+    assert bp._f2v_schedule(events is not None) == schedule
+    return bp
+
+
+def test_f2v_half_sweep_on_two_streams_gives_the_same_bits(api, monkeypatch):
+    """``EPBP.overlap_f2v``: the heavy kernel on the caller's stream (LHVI_PBP_SHARE_CUS: a workgroup per CU left free) and the pair /
+    fast / cq / generic kernels beside it on a second stream write disjoint rows of f2v -- every array of the state after whole sweeps
+    equals the one-stream run's bit for bit, and the next v -> f half waits for both streams"""
+    import torch
+    for graph in ('mrf', 'hmln'):
+        a, b = (_f2v_schedule_run(api, monkeypatch, graph, schedule) for schedule in ('overlap', 'one'))
+        assert getattr(a, '_side', None) is not None and getattr(b, '_side', None) is None
+        for name in ('f2v', 'v2f', 'q_dev', 'eta', 'particles'):
+            assert torch.equal(getattr(a, name), getattr(b, name)), (graph, name)
+
+
+def test_f2v_timed_split_gives_the_same_bits_as_one_call(api, monkeypatch):
+    """``f2v_events`` on one stream: the heavy and small lists in a call of their own between the two events, the other families in
+    a second call -- every array of the state after whole sweeps equals the one-call run's bit for bit"""
+    import torch
+    for graph in ('mrf', 'hmln'):
+        a, b = (_f2v_schedule_run(api, monkeypatch, graph, schedule) for schedule in ('timed', 'one'))
+        assert getattr(a, '_side', None) is None
+        for name in ('f2v', 'v2f', 'q_dev', 'eta', 'particles'):
+            assert torch.equal(getattr(a, name), getattr(b, name)), (graph, name)
 
 
 def test_v2f_hub_kernel_matches_the_one_wave_path(api):
