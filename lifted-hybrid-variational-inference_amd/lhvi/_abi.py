@@ -280,18 +280,60 @@ def upload(arrays, device=None):
     return out
 
 
-def device_potentials(flat):
+def pinned_rows(flat, obs_var=None):
+    """bool [P]: formula rows whose conditional-quadratic block cannot stand for the formula on this graph.  The block is indexed
+    by the STATE of each discrete-role argument (``cq_log_phi``), the formula reads its VALUE; the two agree only when every
+    such argument is hidden or observed exactly on one of its states.  A row is pinned when some factor using it has a
+    discrete-role argument that is a Gaussian observation (``obs_var > 0``: the evaluators feed quadrature nodes around its
+    value) or observed at a value that is none of its states."""
+    kind, off, par = flat.pot_kind, flat.pot_off, flat.pot_param
+    out = np.zeros(int(kind.size), dtype=bool)
+    if not flat.E or not par.size:
+        return out
+    val, cont = flat.var_value, flat.var_cont
+    bad = np.zeros(flat.V, dtype=bool)
+    obs_d = np.flatnonzero(~np.isnan(val) & ~cont)
+    if obs_d.size:
+        lo, n = flat.dom_ptr[flat.var_dom[obs_d]].astype(np.int64), flat.var_nstates[obs_d].astype(np.int64)
+        tt = np.arange(int(n.max()))[None, :]
+        states = flat.dom_val[np.minimum(lo[:, None] + tt, flat.dom_val.size - 1)]
+        bad[obs_d] = ~((tt < n[:, None]) & (states == val[obs_d][:, None])).any(axis=1)
+        if obs_var is not None:
+            bad[obs_d] |= np.asarray(obs_var, dtype=np.float64)[obs_d] > 0
+    e = np.flatnonzero(bad[flat.edge_var])
+    if not e.size:
+        return out
+    f = flat.edge_fac[e].astype(np.int64)
+    i = flat.fac_pot[f].astype(np.int64)
+    lo, hi = off[i].astype(np.int64), off[i + 1].astype(np.int64)
+    head = np.where((kind[i] == 8) & (hi - lo > 2), par[np.minimum(lo + 2, par.size - 1)], 0.0).astype(np.int64)
+    sel = head > 0
+    # role of the argument in the block [CQ_MAGIC, arity, Nd, Nc, role[arity], ...]: >= 0 for a discrete one
+    role = par[lo[sel] + head[sel] + 4 + (e[sel] - flat.fac_ptr[f[sel]])]
+    out[i[sel][role >= 0]] = True
+    return out
+
+
+def device_potentials(flat, obs_var=None):
     """(pot_off, pot_param, interpreted) as they go to the device.  The host table keeps every formula's bytecode (the CPU oracle
     interprets it); on the device a formula with a conditional-quadratic block is evaluated through the block alone
     (``cq_log_phi``, csrc/potential.hpp), so its row travels as ``[w, 0, 3, block]`` -- no program: the table is a fraction of the
-    size (the variational kernels keep it in LDS).  `interpreted` = rows the device has to interpret (``lhvi_pots_t.interpreted``)."""
+    size (the variational kernels keep it in LDS).  A row pinned by the evidence (``pinned_rows``: `obs_var` = the variances of
+    Gaussian observations, or None) travels as ``[w, ncode, 0, program]`` instead: no block, so the evaluators interpret the
+    formula at the argument values and ``cq_analyze`` sends its edges to the generic f -> v kernel.  `interpreted` = rows the
+    device has to interpret (``lhvi_pots_t.interpreted``)."""
     def build():
         kind, off, par = flat.pot_kind, flat.pot_off, flat.pot_param
+        pinned = pinned_rows(flat, obs_var)
         rows, interpreted = [], 0
         for i in range(int(kind.size)):
             row = par[off[i]:off[i + 1]]
             if kind[i] == 8 and row.size > 2 and row[2] != 0:
-                row = np.concatenate([[row[0], 0.0, 3.0], row[int(row[2]):]])
+                if pinned[i]:
+                    row = np.concatenate([row[:2], [0.0], row[3:3 + 2 * int(row[1])]])
+                    interpreted += 1
+                else:
+                    row = np.concatenate([[row[0], 0.0, 3.0], row[int(row[2]):]])
             elif kind[i] in (8, 9):
                 interpreted += 1
             rows.append(row)
@@ -299,19 +341,21 @@ def device_potentials(flat):
         np.cumsum([r.size for r in rows], out=new_off[1:])
         new_par = np.concatenate(rows) if rows else np.zeros(0)
         return new_off, np.ascontiguousarray(new_par, dtype=np.float64), interpreted
-    return flat._cached('device_potentials', (flat.pot_kind, flat.pot_off, flat.pot_param), build)
+    return flat._cached('device_potentials', (flat.pot_kind, flat.pot_off, flat.pot_param, flat.var_value, obs_var), build)
 
 
 class DeviceGraph:
     """A ``FlatGraph`` resident in HBM plus the two C structs that point into it."""
 
-    def __init__(self, flat, device=None):
+    def __init__(self, flat, device=None, obs_var=None):
+        """`obs_var` [V]: variances of Gaussian observations (C2FVarInference's evidence clusters), or None: it decides which formula
+        rows keep their program on the device (``device_potentials``)"""
         require_gpu()
         self.flat = flat
         host = {name: getattr(flat, name) for name in
                 ('fac_ptr', 'edge_var', 'edge_fac', 'var_ptr', 'var_edge', 'fac_pot', 'var_value', 'var_dom',
                  'dom_cont', 'dom_lo', 'dom_hi', 'dom_ptr', 'dom_val', 'pot_kind')}
-        host['pot_off'], host['pot_param'], interpreted = device_potentials(flat)
+        host['pot_off'], host['pot_param'], interpreted = device_potentials(flat, obs_var)
         self.pot_param_words = int(host['pot_param'].size)
         has_alias = flat._cached('has_alias', (flat.edge_canon,),
                                  lambda: bool((flat.edge_canon != np.arange(flat.E, dtype=np.int32)).any()))
@@ -349,8 +393,8 @@ class DeviceGraph:
         p = PotsStruct()
         p.P = int(flat.pot_kind.size)
         p.kind, p.off, p.param = ptr(t['pot_kind']), ptr(t['pot_off']), ptr(t['pot_param'])
-        # formulas the device has to interpret (lhvi_pots_t.interpreted): hard formulas, and soft ones without a
-        # conditional-quadratic block (word 2 of the row, lhvi/mln.py::device_spec)
+        # formulas the device has to interpret (lhvi_pots_t.interpreted): hard formulas, soft ones without a conditional-quadratic
+        # block (word 2 of the row, lhvi/mln.py::device_spec), and soft ones whose block the evidence pins (pinned_rows)
         p.interpreted = int(interpreted)
         self.p = p
 

@@ -82,7 +82,9 @@ class _FormulaPotential(Potential):
     def device_spec(self, domains):
         """parameter row ``[w, ncode, cq_off, (op, val) * ncode, conditional-quadratic block]`` (csrc/potential.hpp): ``cq_off`` =
         offset of the block from the start of the row, 0 when the formula has none -- with it the device evaluates the formula
-        as a table lookup and at most six multiply-adds, never through the bytecode (which the CPU oracle keeps interpreting)"""
+        as a table lookup and at most six multiply-adds, not through the bytecode (which the CPU oracle keeps interpreting),
+        unless the evidence of a graph pins the row (``_abi.pinned_rows``: a discrete argument Gaussian-observed or observed off
+        its states), which then travels with its program and without the block (``_abi.device_potentials``)"""
         program = self._program_for(domains)
         tail = self._cq_tail(program, domains)
         return self.kind, [float(self.w), float(len(program) // 2), float(3 + len(program) if tail else 0)] + program + tail
@@ -101,8 +103,10 @@ class MLNPotential(_FormulaPotential):
         return e ** (truth * self.w)
 
     def _cq_tail(self, program, domains):
-        """conditional-quadratic view of the formula (``expr.cq_block``), appended behind the bytecode: the evaluators
-        ignore it, the f -> v work-list builder routes such factors to the quadratic-family kernels (csrc/pbp.hip)"""
+        """conditional-quadratic view of the formula (``expr.cq_block``), appended behind the bytecode: the device
+        evaluators use it in place of the bytecode (``cq_log_phi``, csrc/potential.hpp: coefficients picked by the STATE index of
+        each discrete argument), and the f -> v work-list builder routes such factors to the quadratic-family kernels
+        (csrc/pbp.hip, csrc/cq.hpp)"""
         roles = [None if d.continuous else tuple(d.values) for d in domains]
         states = 1
         for r in roles:

@@ -63,7 +63,7 @@ def factor_lists(flat, K, T, obs_var=None, tiny_kernel=True):
     lg = np.concatenate([[0.0], np.cumsum(np.log2(axis_len.astype(np.float64)))])
     nodes = lg[flat.fac_ptr[1:]] - lg[flat.fac_ptr[:-1]]
     tiny = ~cc & small & (arity >= 1) & (nodes <= np.log2(_abi.VI_TINY_NODES) + 1e-9) & (K <= _abi.VI_TINY_K) & bool(tiny_kernel)
-    if _abi.device_potentials(flat)[1].size > _abi.VI_TINY_PAR:
+    if _abi.device_potentials(flat, obs_var)[1].size > _abi.VI_TINY_PAR:
         tiny[:] = False                   # (the kernel keeps every parameter row of the device table in LDS)
     if tiny_kernel != 'always' and int(tiny.sum()) * K < TINY_MIN_ITEMS:
         tiny[:] = False                   # too few items to fill the device with single threads: the 8-lane groups finish sooner
@@ -120,7 +120,7 @@ class _Variational:
 
     def _setup_flat(self, flat):
         """device state for a ready-made FlatGraph (large graphs built without Python objects)"""
-        self.flat, self.dg = flat, _abi.DeviceGraph(flat)
+        self.flat, self.dg = flat, _abi.DeviceGraph(flat, obs_var=getattr(self, '_obs_var_host', None))
         torch = _abi.require_gpu()
         disc = flat.var_hidden & ~flat.var_cont
         self._cont, self._disc = flat.var_hidden & flat.var_cont, disc

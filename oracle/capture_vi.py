@@ -122,11 +122,12 @@ def model_rgm_c2fvi(cg, C=6, B=4):
     return g
 
 
-def model_hmln_c2fvi(cg, P=5, T=3, seed=43):
+def model_hmln_c2fvi(cg, P=5, T=3, seed=43, paper_in=None):
     """the paper-popularity template (see capture_pbp.model_hmln_small) with popularity evidence of at most two values per
     atom type: papers p0..p3 at 2 / 3 (std 0.5: a Gaussian observation until the last round), topics t0, t1 at 1 / 9
     (split before the first round), p4 and t2 hidden; PaperIn(p, t0) = PaperIn(p, t1) = 1 for the observed papers.  Exercises Gaussian observations
-    next to discrete hidden variables (gradient_category_tau, C2FVarInference.py:207-239)"""
+    next to discrete hidden variables (gradient_category_tau, C2FVarInference.py:207-239).  `paper_in`: the PaperIn evidence
+    of the observed papers instead, {(paper index, topic index): value}"""
     import RelationalGraph as RR
     RG, RM, modelio = cg.RG, cg.RM, cg.modelio
     rng = np.random.RandomState(seed)
@@ -150,9 +151,13 @@ def model_hmln_c2fvi(cg, P=5, T=3, seed=43):
     for i in range(P - 1):
         data[('PaperPopularity', 'p%d' % i)] = 2.0 if i % 2 == 0 else 3.0
     data[('TopicPopularity', 't0')], data[('TopicPopularity', 't1')] = 1.0, 9.0
-    for i in range(P - 1):          # the same boolean evidence around every observed paper / topic: they stay exchangeable
-        data[('PaperIn', 'p%d' % i, 't0')] = 1
-        data[('PaperIn', 'p%d' % i, 't1')] = 1
+    if paper_in is None:
+        for i in range(P - 1):          # the same boolean evidence around every observed paper / topic: they stay exchangeable
+            data[('PaperIn', 'p%d' % i, 't0')] = 1
+            data[('PaperIn', 'p%d' % i, 't1')] = 1
+    else:
+        for (i, j), v in paper_in.items():
+            data[('PaperIn', 'p%d' % i, 't%d' % j)] = v
     g, rvs_dict = rel_g.add_evidence(data)
     rvs = list(rvs_dict.values())
     idx = {id(rv): i for i, rv in enumerate(rvs)}
@@ -188,10 +193,11 @@ def _c2f_state(cg, vi, g):
     return st
 
 
-def capture_c2fvi(cg, name, g, K, T, seed, iterations, lr, update_obs_its=10, log_fe=True):
+def capture_c2fvi(cg, name, g, K, T, seed, iterations, lr, update_obs_its=10, log_fe=True, gaussian_obs=True):
     import C2FVarInference as RC
     vi = RC.VarInference(g, K, T)
     vi.update_obs_its = update_obs_its
+    vi.gaussian_obs = gaussian_obs
     snaps = []
     orig_adam, orig_init = vi.ADAM_update, vi.init_param
 
@@ -240,7 +246,7 @@ def capture_c2fvi(cg, name, g, K, T, seed, iterations, lr, update_obs_its=10, lo
     rec['map'] = np.array([float(vi.map(rv)) for rv in rvs])
     rec['meta'] = json.dumps({'model': cg.modelio.dump_model(g), 'K': K, 'T': T, 'seed': seed, 'iterations': iterations,
                               'lr': lr, 'update_obs_its': update_obs_its, 'solver': 'C2FVarInference', 'log_fe': log_fe,
-                              'kmeans_orders': orders})
+                              'kmeans_orders': orders, 'gaussian_obs': gaussian_obs})
     path = os.path.join(cg.OUT, 'vi_%s.npz' % name)
     np.savez_compressed(path, **rec)
     print('wrote', path, os.path.getsize(path), 'bytes', 'rounds', len(rounds),
@@ -275,3 +281,37 @@ def capture_c2f_loglik(cg):
     every update -- the quantity of the reference's published HMLN logs (Demo/HMLN/HMLNTimeLog.py:57)"""
     capture_c2fvi(cg, 'c2f_rgm_k2_loglik', model_rgm_c2fvi(cg), 2, 3, 44, 20, 0.1, log_fe=False)
     capture_c2fvi(cg, 'c2f_hmln_k2_loglik', model_hmln_c2fvi(cg), 2, 3, 45, 20, 0.2, log_fe=False)
+
+
+# PaperIn evidence: 0, 1 and values that are neither -- a soft truth value the reference plugs into the formula as it is
+# (C2FVarInference.py:108-111), where a state-indexed table reads state 0 or past it.  One value per (paper group, topic group)
+# keeps the observed papers p0..p3 exchangeable (their popularity cluster is a Gaussian observation while it holds), and the
+# observed topics t0, t1 too; p4 is the paper of hidden popularity, t2 the topic
+def _paper_in(observed, hidden_topic, hidden_paper):
+    rec = {}
+    for j in (0, 1):
+        for i in range(4):
+            rec[(i, j)] = observed
+        rec[(4, j)] = hidden_paper
+    for i in range(4):
+        rec[(i, 2)] = hidden_topic
+    return rec
+
+
+PAPER_IN_MIXED = _paper_in(0.5, 1, 0)
+PAPER_IN_MEAN = _paper_in(0.25, 1, 0)
+
+
+def capture_c2f_off_state(cg):
+    """paper popularity with PaperIn evidence off the boolean states: the formula, not a state-indexed table, decides.  The
+    reference clusters discrete evidence by value (CompressedGraphWithObs.py:209-224), so a boolean evidence cluster never has
+    spread; what reaches the expectations is its value itself -- with Gaussian observations of the popularity clusters
+    (c2f_hmln_mixed_k2) and without (c2f_hmln_mean_k2: every evidence cluster at its mean)"""
+    for name, paper_in, gobs in (('c2f_hmln_mixed_k2', PAPER_IN_MIXED, True), ('c2f_hmln_mean_k2', PAPER_IN_MEAN, False)):
+        g = model_hmln_c2fvi(cg, paper_in=paper_in)
+        disc = [i for i, rv in enumerate(g.rvs) if rv.value is not None and not rv.domain.continuous]
+        rec = capture_c2fvi(cg, name, g, 2, 3, 46, 30, 0.2, gaussian_obs=gobs)
+        off = rec['round_value'][:, disc]
+        assert ((off != 0) & (off != 1)).any(axis=1).all(), 'every round must carry boolean evidence off its states'
+        if gobs:
+            assert (np.nan_to_num(rec['round_variance']) > 0).any(), 'some evidence cluster must be a Gaussian observation'

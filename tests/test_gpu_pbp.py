@@ -819,6 +819,68 @@ def test_conditionally_quadratic_routing_equals_the_generic_kernel(api, solver, 
     np.testing.assert_allclose(fa[ce, n:], o.f2v[ce, n:], rtol=RTOL, atol=ATOL)
 
 
+def test_epbp_with_a_boolean_observed_off_its_states_matches_the_oracle(api):
+    """EPBP with the conditionally quadratic routing on, on paper popularity with one PaperIn atom observed at 0.5: the
+    reference plugs the value into x[0] * eq_op(x[1], x[2]) as it is (EPBPLogVersion.py:184-188), where the block would read
+    state 0's coefficients.  The row keeps its bytecode on the device and no block (lhvi/_abi.py::pinned_rows), so
+    cq_analyze sends the factor's edges to the generic list; two sweeps against the C oracle, then the query kernels"""
+    import torch
+    from lhvi import _abi
+    from lhvi.pbp import EPBP
+    from oracle import oracle
+    n, its = 12, 2
+    g, table = paper_popularity(40, 5, seed=5)
+    runs = {}
+    for off_state in (False, True):
+        if off_state:
+            key = next(k for k, rv in sorted(table.items()) if k[0] == 'PaperIn' and rv.value is not None and
+                       (table[('PaperPopularity', k[1])].value is None or table[('TopicPopularity', k[2])].value is None))
+            table[key].value = 0.5
+        rng = np.random.default_rng(17)
+        draws = []
+
+        def sampler(k, flat, q):
+            if k == len(draws):
+                cont = flat.var_hidden & flat.var_cont
+                lo, hi = flat.dom_lo[flat.var_dom], flat.dom_hi[flat.var_dom]
+                out = np.zeros((flat.V, n))
+                out[cont] = np.clip(rng.standard_normal((int(cont.sum()), n)) * np.sqrt(q[cont, 1:2]) + q[cont, 0:1],
+                                    lo[cont, None], hi[cont, None])
+                draws.append(out)
+            return draws[k]
+        bp = EPBP(g, n=n, proposal_approximation='simple', sampler=sampler)
+        bp.run(its)
+        runs[off_state] = bp
+    on, off = runs[False], runs[True]
+    assert on.flags & api.PBP_CQ and off.flags & api.PBP_CQ
+    # all evidence on its states: nothing pinned, the device table is the block-only one and the cq kernels serve the formula
+    assert not _abi.pinned_rows(on.flat).any() and on.dg.p.interpreted == 0 and on.n_cq > 0
+    flat = off.flat
+    pinned = _abi.pinned_rows(flat)
+    f = next(i for i, fa in enumerate(flat.factors) if table[key] in fa.nb)
+    assert pinned[flat.fac_pot[f]] and off.dg.p.interpreted == int(pinned.sum())
+    assert off.n_cq < on.n_cq
+    edges = np.arange(flat.fac_ptr[f], flat.fac_ptr[f + 1])
+    hid = edges[flat.var_hidden[flat.edge_var[edges]]]
+    assert hid.size and np.isin(hid, off.generic_edges.cpu().numpy()).all()
+    o = oracle.PbpOracle(flat, n, ep=False, epbp=True, var_threshold=3)
+    o.run(its, draws)
+    hid_e = flat.var_hidden[flat.edge_var] & (flat.edge_canon == np.arange(flat.E))
+    npe = off.np_host[flat.edge_var]
+    live = hid_e[:, None] & (np.arange(n)[None, :] < npe[:, None])
+    ce = hid_e & flat.var_cont[flat.edge_var]
+    got = off.f2v.cpu().numpy()
+    np.testing.assert_allclose(got[:, :n][live], o.f2v[:, :n][live], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(got[ce, n:], o.f2v[ce, n:], rtol=RTOL, atol=ATOL)
+    np.testing.assert_allclose(off.v2f.cpu().numpy()[live], o.v2f[live], rtol=RTOL, atol=ATOL)
+    # the query kernels (f2v_point_generic): log beliefs of every hidden continuous variable on a grid
+    cont = np.flatnonzero(flat.var_hidden & flat.var_cont)
+    x = np.zeros((flat.V, n))
+    x[cont] = np.linspace(0.0, 10.0, n)[None, :] + 0.1 * (cont % 7)[:, None]
+    lb = off.belief_rv_all(_abi.to_dev(x)).cpu().numpy()
+    np.testing.assert_allclose(lb[cont], o.belief_points(cont, x[cont]), rtol=RTOL, atol=ATOL)
+
+
 def test_batched_kl_of_tabulated_beliefs(api):
     """utils.kl_tables: trapezoid of kl_continuous' integrand for every variable at once (device), against the host quad"""
     from math import exp, pi, sqrt

@@ -154,6 +154,34 @@ def test_device_log_likelihood_matches_host(api, golden_dir, name):
             assert got == pytest.approx(want, rel=1e-12, abs=1e-10)
 
 
+@pytest.mark.parametrize('name', ['c2f_hmln_mixed_k2', 'c2f_hmln_mean_k2'])
+def test_device_log_likelihood_with_discrete_evidence_off_its_states(api, golden_dir, name):
+    """lhvi_log_likelihood on paper popularity with PaperIn evidence at 0.5 / 0.25 against the host loop over the factor
+    objects: the pinned formula row is interpreted at the value (a block would read state 0's coefficients)"""
+    from lhvi import utils
+    from lhvi.flat import flatten
+    z, meta = load_vi(golden_dir, name)
+    g, rvs, factors = modelio.load_model(meta['model'], API)
+    flat = flatten(g, require_device_potentials=True)
+    assert any(rv.value not in (None, 0, 1) for rv in flat.rvs if not rv.domain.continuous)
+    dg = api.DeviceGraph(flat)
+    assert api.pinned_rows(flat).any() and dg.p.interpreted == int(api.pinned_rows(flat).sum())
+    rng = np.random.default_rng(2)
+    for trial in range(3):
+        assignment = {}
+        for rv in flat.rvs:
+            if rv.value is not None:
+                assignment[rv] = rv.value
+            elif rv.domain.continuous:
+                assignment[rv] = float(rng.uniform(-2, 6))
+            else:
+                assignment[rv] = rv.domain.values[int(rng.integers(len(rv.domain.values)))]
+        x = np.array([assignment[rv] for rv in flat.rvs], dtype=np.float64)
+        vals = [float(f.potential.get(tuple(assignment[rv] for rv in f.nb))) for f in flat.factors]
+        want = -float(np.sum(np.log(vals)))
+        assert utils.log_likelihood_flat(dg, x) == pytest.approx(want, rel=1e-12, abs=1e-10)
+
+
 def test_device_evaluators_match_reference_values(api, golden_dir):
     """lhvi_log_likelihood on the device-resident flat graph against utils.log_likelihood values computed by the reference
     (tests/golden/utils.json: chain, Kalman, paper-popularity HMLN, RGM/0, and a vanishing factor -> -inf), and the batched
@@ -179,7 +207,8 @@ def test_device_evaluators_match_reference_values(api, golden_dir):
         assert got[i] == pytest.approx(c['kl_continuous'], rel=1e-6, abs=1e-9)
 
 
-@pytest.mark.parametrize('name', ['c2f_rgm_k2', 'c2f_hmln_k2', 'c2f_robot_k2', 'c2f_rkf_tree_k1', 'c2f_rkf_cycle_k1'])
+@pytest.mark.parametrize('name', ['c2f_rgm_k2', 'c2f_hmln_k2', 'c2f_robot_k2', 'c2f_rkf_tree_k1', 'c2f_rkf_cycle_k1',
+                                  'c2f_hmln_mixed_k2', 'c2f_hmln_mean_k2'])
 def test_c2f_var_inference_matches_reference(api, golden_dir, name):
     """C2FVarInference on the device (coarse-to-fine lifting with Gaussian observation clusters, csrc/vi.hip through
     lhvi_vi_t.obs_var) against the reference: every round's partition / inherited parameters / ADAM moments, the free
@@ -191,10 +220,11 @@ def test_c2f_var_inference_matches_reference(api, golden_dir, name):
     g, rvs, factors = modelio.load_model(meta['model'], API)
     vi = C2FVI(g, meta['K'], meta['T'])
     vi.update_obs_its = meta['update_obs_its']
+    vi.gaussian_obs = meta.get('gaussian_obs', True)
     vi.kmeans_member_order = kmeans_order_of(meta)      # the set order the reference's k-means happened to walk (robot fixture)
     vi.init = (z['eta_c0'], z['tau_d0'])
     seen = []
-    vi.observer = c2fvi_round_checker(z, rvs, seen)
+    vi.observer = c2fvi_round_checker(z, rvs, seen, vi.gaussian_obs)
     vi.run(meta['iterations'], lr=meta['lr'])
     assert seen == list(range(meta['iterations'] // meta['update_obs_its']))
     res = vi._result
@@ -266,7 +296,7 @@ def test_fused_adam_loop_equals_the_per_array_calls(api, golden_dir, name):
     assert (fa == fb if exact else np.allclose(fa, fb, rtol=1e-12)) and a.t == b.t == 7
 
 
-@pytest.mark.parametrize('name', ['c2f_rgm_k2', 'c2f_hmln_k2'])
+@pytest.mark.parametrize('name', ['c2f_rgm_k2', 'c2f_hmln_k2', 'c2f_hmln_mixed_k2', 'c2f_hmln_mean_k2'])
 def test_c2fvi_on_arrays_equals_the_object_path(api, golden_dir, name):
     """``run_c2fvi_flat`` (ground FlatGraph in: refinement to the fixed point and re-lifting on the device, clustered_evidence in
     closed form, parameters per cluster) against ``run_c2fvi`` on the objects and through it against the reference's run:
@@ -277,6 +307,7 @@ def test_c2fvi_on_arrays_equals_the_object_path(api, golden_dir, name):
     z, meta = load_vi(golden_dir, name)
     g, rvs, factors = modelio.load_model(meta['model'], API)
     vi = c2fvi.VarInference(g, meta['K'], meta['T'])
+    vi.gaussian_obs = meta.get('gaussian_obs', True)
     opts = dict(vi._options(), update_obs_its=meta['update_obs_its'])
     rounds = []
     res = c2fvi.run_c2fvi_flat(flatten(g, require_device_potentials=True), c2fvi._DeviceEngine(vi), meta['K'], meta['iterations'],
@@ -286,7 +317,8 @@ def test_c2fvi_on_arrays_equals_the_object_path(api, golden_dir, name):
     for r, st in enumerate(rounds):
         assert oracle.canonical_labels(st['rvc']) == z['round_rv_label'][r].tolist(), 'rv partition of round %d' % r
         assert oracle.canonical_labels(st['fc']) == z['round_f_label'][r].tolist(), 'factor partition of round %d' % r
-        np.testing.assert_allclose(st['obs_var'][st['rvc']][ev], z['round_variance'][r][ev], rtol=1e-12, atol=1e-300)
+        np.testing.assert_allclose(st['obs_var'][st['rvc']][ev], z['round_variance'][r][ev] if vi.gaussian_obs else 0.0, rtol=1e-12,
+                                   atol=1e-300)
         np.testing.assert_allclose(st['flat'].var_value[st['rvc']][ev], z['round_value'][r][ev], rtol=1e-14)
         live = ev & (z['round_variance'][r] > 0)
         tracked = np.array([int(st['rvc'][i]) in st['tracked'] for i in range(len(rvs))], dtype=np.int8)
@@ -406,20 +438,62 @@ def test_random_hybrid_graphs_through_every_factor_kernel(api, seed, K, T, quirk
     assert _random_hybrid_check(seed, K, T, quirks, require_every_kernel=True) is None
 
 
-def _random_hybrid_check(seed, K, T, quirks, require_every_kernel):
+@pytest.mark.parametrize('seed,K,T,quirks,disc_gobs,off_state', [(0, 2, 3, True, True, False), (1, 1, 3, False, False, True),
+                                                                  (2, 2, 3, False, True, True), (4, 2, 5, True, True, True)])
+def test_random_hybrid_graphs_with_discrete_evidence_off_its_states(api, seed, K, T, quirks, disc_gobs, off_state):
+    """the random hybrid graphs with discrete arguments of conditionally quadratic formulas that a state-indexed block cannot
+    serve: Gaussian observations of discrete variables (quadrature nodes around the value) and discrete evidence between two
+    states.  Their rows keep the bytecode on the device (lhvi/_abi.py::pinned_rows); every kernel gets such factors and
+    agrees with the C oracle, which interprets every formula at its argument values"""
+    assert _random_hybrid_check(seed, K, T, quirks, require_every_kernel=True, disc_gobs=disc_gobs, off_state=off_state) is None
+
+
+def _mln_only_discrete(flat):
+    """discrete variables that only MLN formulas read (a table lookup of an off-state value is no valid input anywhere)"""
+    from lhvi.potentials import POT_MLN
+    kind = flat.pot_kind[flat.fac_pot[flat.edge_fac]]
+    other = np.zeros(flat.V, dtype=bool)
+    other[flat.edge_var[kind != POT_MLN]] = True
+    return np.flatnonzero(~flat.var_cont & ~other & (np.diff(flat.var_ptr) > 0))
+
+
+def _random_hybrid_check(seed, K, T, quirks, require_every_kernel, disc_gobs=False, off_state=False):
     """random hybrid graphs (observed discrete states, three- and four-state variables, formulas
     with comparisons / abs / divisions / squares, dict-keyed tables, Gaussian observations on some observed continuous variables):
     gradient and free energy through (a) the tiny-grid kernel, (b) the group kernel, (c) the thread-per-factor kernels of rounds
-    1-3, against the C oracle and against each other"""
-    from lhvi import c2fvi
+    1-3, against the C oracle and against each other.  Opt in: `off_state` -- every other discrete variable that only MLN formulas
+    read is observed between two of its states (0.5, 1.5, 2.5 on the two-, three-, four-state domains); `disc_gobs` -- the others
+    are Gaussian observations (observed on a state, obs_var > 0)"""
+    from lhvi import _abi, c2fvi
     from lhvi.flat import flatten
     from oracle import oracle
     rng = np.random.default_rng(100 + seed)
     g = _random_hybrid_graph(rng, one_discrete_domain=quirks)
     flat = flatten(g, require_device_potentials=True)
+    special = np.zeros(0, dtype=np.int64)
+    if off_state or disc_gobs:
+        cand = _mln_only_discrete(flat)
+        between = {2: 0.5, 3: 1.5, 4: 2.5}
+        for v in cand[::2] if off_state else ():
+            flat.rvs[v].value = between[len(flat.rvs[v].domain.values)]
+        for v in cand[1::2] if disc_gobs else ():
+            if flat.rvs[v].value is None:
+                flat.rvs[v].value = flat.rvs[v].domain.values[int(v) % len(flat.rvs[v].domain.values)]
+        special = np.concatenate([cand[::2] if off_state else cand[:0], cand[1::2] if disc_gobs else cand[:0]])
+        flat = flatten(g, require_device_potentials=True)
     obs_c = np.flatnonzero(~flat.var_hidden & flat.var_cont)
     obs_var = np.zeros(flat.V)
     obs_var[obs_c[::2]] = rng.uniform(0.3, 1.5, obs_c[::2].size)       # every other observed continuous variable: a Gaussian observation
+    if disc_gobs:
+        obs_var[cand[1::2]] = rng.uniform(0.05, 0.5, cand[1::2].size)
+    pinned = _abi.pinned_rows(flat, obs_var)
+    # factors with such an argument in a discrete role of a block (their rows are pinned)
+    edge_special = np.isin(flat.edge_var, special)
+    fac_special = np.zeros(flat.F, dtype=bool)
+    fac_special[flat.edge_fac[edge_special]] = True
+    fac_special &= pinned[flat.fac_pot]
+    if off_state or disc_gobs:
+        assert fac_special.sum() >= 3, 'the graph has too few factors with discrete evidence off its states'
     owner = c2fvi.VarInference.__new__(c2fvi.VarInference)
     owner._init_common(K, T)
     owner.reference_quirks = quirks
@@ -447,6 +521,12 @@ def _random_hybrid_check(seed, K, T, quirks, require_every_kernel):
             assert st._fac_counts[1] > 20 and st._fac_counts[0] > 0, st._fac_counts
         if label == 'group' and require_every_kernel:
             assert st._fac_counts[1] == 0 and st._fac_counts[2] > 20, st._fac_counts
+        if (off_state or disc_gobs) and require_every_kernel:
+            assert st.dg.p.interpreted >= int(pinned.sum()) > 0
+            if lists:                               # the kernel's own segment of the factor list holds such factors
+                order, c = d['fac_list'].cpu().numpy(), st._fac_counts
+                seg = order[c[0]:c[0] + c[1]] if label == 'tiny' else order[c[0] + c[1]:c[0] + c[1] + c[2] + c[3]]
+                assert fac_special[seg].any(), (label, st._fac_counts)
     cont, disc = flat.var_hidden & flat.var_cont, flat.var_hidden & ~flat.var_cont
     for label, (g_w, g_c, g_d, fe) in outs.items():
         np.testing.assert_allclose(fe[0], want[3], rtol=1e-9, err_msg=label)

@@ -81,7 +81,8 @@ def test_device_map_equals_scipy_after_the_golden_trajectory(api, golden_dir, na
         assert vi.map(rvs[i]) == pytest.approx(z['map'][i], rel=1e-5, abs=1e-5)
 
 
-@pytest.mark.parametrize('name', ['c2f_rgm_k2', 'c2f_hmln_k2', 'c2f_robot_k2', 'c2f_rkf_tree_k1', 'c2f_rkf_cycle_k1'])
+@pytest.mark.parametrize('name', ['c2f_rgm_k2', 'c2f_hmln_k2', 'c2f_robot_k2', 'c2f_rkf_tree_k1', 'c2f_rkf_cycle_k1',
+                                  'c2f_hmln_mixed_k2', 'c2f_hmln_mean_k2'])
 def test_device_map_equals_scipy_after_the_c2fvi_golden_run(api, golden_dir, name):
     from lhvi.c2fvi import VarInference as C2FVI
     from test_oracle_vi import kmeans_order_of
@@ -89,6 +90,7 @@ def test_device_map_equals_scipy_after_the_c2fvi_golden_run(api, golden_dir, nam
     g, rvs, factors = modelio.load_model(meta['model'], API)
     vi = C2FVI(g, meta['K'], meta['T'])
     vi.update_obs_its = meta['update_obs_its']
+    vi.gaussian_obs = meta.get('gaussian_obs', True)
     vi.kmeans_member_order = kmeans_order_of(meta)
     vi.init = (z['eta_c0'], z['tau_d0'])
     vi.run(meta['iterations'], lr=meta['lr'])

@@ -716,3 +716,200 @@ def test_lift_flat_equals_flatten_of_the_cluster_objects(model):
     row = lambda t, i: (int(t.pot_kind[i]), tuple(t.pot_param[t.pot_off[i]:t.pot_off[i + 1]]))
     assert [row(a, i) for i in a.fac_pot] == [row(b, i) for i in b.fac_pot]
     assert [c.id for c in a.rvs] == list(range(a.V)) and [c.id for c in a.factors] == list(range(a.F))
+
+
+# ---- the device potential table: which formula rows travel as their conditional-quadratic block alone ---------------------
+def _block_only_table(flat):
+    """the device table without pinning: every formula row with a block as ``[w, 0, 3, block]``, everything else as on the host"""
+    rows, interpreted = [], 0
+    for i in range(int(flat.pot_kind.size)):
+        row = flat.pot_param[flat.pot_off[i]:flat.pot_off[i + 1]]
+        if flat.pot_kind[i] == P.POT_MLN and row.size > 2 and row[2] != 0:
+            row = np.concatenate([[row[0], 0.0, 3.0], row[int(row[2]):]])
+        elif flat.pot_kind[i] in (P.POT_MLN, P.POT_MLN_HARD):
+            interpreted += 1
+        rows.append(row)
+    off = np.concatenate([[0], np.cumsum([r.size for r in rows])]).astype(np.int32)
+    return off, np.concatenate(rows).astype(np.float64), interpreted
+
+
+def _cq_log_phi(block, x, idx):
+    """host restatement of cq_log_phi (csrc/potential.hpp): coefficients by the state index of each discrete-role argument"""
+    arity, nd = int(block[1]), int(block[2])
+    role, dims = block[4:4 + arity], block[4 + arity:4 + arity + nd]
+    cfg, uv = 0, [0.0, 0.0]
+    for a in range(arity):
+        r = int(role[a])
+        if r >= 0:
+            cfg = cfg * int(dims[r]) + idx[a]
+        else:
+            uv[-1 - r] = x[a]
+    c = block[4 + arity + nd + 6 * cfg:4 + arity + nd + 6 * cfg + 6]
+    u, v = uv
+    return (c[0] * u + c[1] * v + c[3]) * u + (c[2] * v + c[4]) * v + c[5]
+
+
+def _paper_in_graph(b_values, obs_var_b=None):
+    """x0 * eq_op(x1, x2) (weight 0.7) over (boolean, real, real) for each boolean value in `b_values` (None = hidden), and
+    eq_op(x0, 1) (weight 0.3) over every real; returns (flat, obs_var with `obs_var_b` on the booleans)"""
+    db, dr = G.Domain((0, 1)), G.Domain((-5, 5), continuous=True, integral_points=np.linspace(-5, 5, 8))
+    f3, f1 = M.MLNPotential(lambda x: x[0] * M.eq_op(x[1], x[2]), w=0.7), M.MLNPotential(lambda x: M.eq_op(x[0], 1), w=0.3)
+    rvs, fs = [], []
+    for i, bv in enumerate(b_values):
+        b, u, v = G.RV(db, bv), G.RV(dr, None), G.RV(dr, 1.5 if i % 2 else None)
+        rvs += [b, u, v]
+        fs += [G.F(f3, [b, u, v]), G.F(f1, [u])]
+    g = G.Graph()
+    g.rvs, g.factors = rvs, fs
+    g.init_nb()
+    flat = flatten(g, require_device_potentials=True)
+    obs_var = np.zeros(flat.V)
+    if obs_var_b is not None:
+        for i in range(len(b_values)):
+            obs_var[flat.var_index[rvs[3 * i]]] = obs_var_b
+    return flat, obs_var
+
+
+@pytest.mark.parametrize('b_values, gobs, pinned', [
+    ((1, 0, None), None, False),          # on its states: the block serves
+    ((1, 0.5, None), None, True),         # a boolean at 0.5: the block would read state 0
+    ((1, 2, 0), None, True),              # a boolean at 2: the block would read past its two entries
+    ((1, 0.3, 0), None, True),
+    ((1, 0, None), 0.4, True),            # Gaussian observations of the boolean: quadrature nodes around its value
+    ((None, None), 0.4, False),           # (obs_var of a hidden variable means nothing)
+])
+def test_device_potentials_pin_formula_rows_at_discrete_evidence_off_its_states(b_values, gobs, pinned):
+    """a formula row keeps its program on the device (``[w, ncode, 0, program]``: no block, so the evaluators interpret it and
+    cq_analyze sends its edges to the generic kernel) when a factor using it has a discrete-role argument that is Gaussian-observed
+    or observed at none of its states; `interpreted` counts the row.  Other rows are as before"""
+    from lhvi import _abi
+    flat, obs_var = _paper_in_graph(b_values, gobs)
+    ov = obs_var if gobs is not None else None
+    off, par, interpreted = _abi.device_potentials(flat, ov)
+    off0, par0, int0 = _block_only_table(flat)
+    got = _abi.pinned_rows(flat, ov)
+    row3 = int(flat.fac_pot[0])                                  # x0 * eq_op(x1, x2)
+    assert got.tolist() == [i == row3 and pinned for i in range(flat.pot_kind.size)]
+    for i in range(flat.pot_kind.size):
+        dev, host = par[off[i]:off[i + 1]], flat.pot_param[flat.pot_off[i]:flat.pot_off[i + 1]]
+        if got[i]:
+            ncode = int(host[1])
+            assert dev.tolist() == host[:2].tolist() + [0.0] + host[3:3 + 2 * ncode].tolist()
+            assert host[2] != 0 and dev.size < host.size
+        else:
+            assert dev.tobytes() == par0[off0[i]:off0[i + 1]].tobytes()
+    assert interpreted == int0 + int(got.sum())
+    if not pinned:
+        assert off.tobytes() == off0.tobytes() and par.tobytes() == par0.tobytes()
+    # the cache key follows var_value and obs_var
+    if gobs is None and pinned:
+        flat.var_value = np.where(np.isin(flat.var_value, (0.5, 2, 0.3)) & ~flat.var_cont, 1.0, flat.var_value)
+        assert _abi.device_potentials(flat)[1].tobytes() == _block_only_table(flat)[1].tobytes()
+    if gobs is not None and pinned:
+        assert _abi.device_potentials(flat, None)[1].tobytes() == par0.tobytes()
+        assert _abi.device_potentials(flat, obs_var)[2] == int0 + 1
+
+
+def _table_cases(golden_dir):
+    """(label, flat, obs_var) of the models whose device tables must not change: paper popularity (host-built and the C2F
+    fixture's ground graph, with the Gaussian observations of its first round), robot mapping, RGM, hybrid, random hybrid"""
+    from lhvi import synth
+    import test_gpu_vi
+    from test_oracle_vi import load_vi
+    out = [('paper popularity', synth.paper_popularity_flat(40, 5, seed=1, points=20)[0], None)]
+    for name in ('c2f_hmln_k2', 'c2f_robot_k2', 'rgm_small_k2', 'c2f_rgm_k2', 'hybrid_k2'):
+        z, meta = load_vi(golden_dir, name)
+        g, rvs, factors = modelio.load_model(meta['model'], API)
+        flat = flatten(g, require_device_potentials=True)
+        ov = None
+        if 'round_variance' in z:
+            ov = np.nan_to_num(z['round_variance'][0])[[rvs.index(rv) for rv in flat.rvs]]
+        out.append((name, flat, ov))
+    for seed in range(3):
+        g = test_gpu_vi._random_hybrid_graph(np.random.default_rng(100 + seed), one_discrete_domain=bool(seed % 2))
+        out.append(('random hybrid %d' % seed, flatten(g, require_device_potentials=True), None))
+    return out
+
+
+def test_device_tables_of_models_without_off_state_evidence_are_unchanged(golden_dir):
+    """on every model whose discrete evidence sits on its states and is no Gaussian observation, the device table is the
+    block-only one byte for byte (with and without the Gaussian observations of continuous clusters)"""
+    from lhvi import _abi
+    for label, flat, ov in _table_cases(golden_dir):
+        want = _block_only_table(flat)
+        for obs_var in (None, ov):
+            off, par, interpreted = _abi.device_potentials(flat, obs_var)
+            assert not _abi.pinned_rows(flat, obs_var).any(), label
+            assert off.tobytes() == want[0].tobytes() and par.tobytes() == want[1].tobytes() and interpreted == want[2], label
+    assert any(_block_only_table(flat)[2] < int(np.isin(flat.pot_kind, (P.POT_MLN, P.POT_MLN_HARD)).sum())
+               for _, flat, _ in _table_cases(golden_dir))      # (block-only rows do occur)
+
+
+def _off_state_cases(golden_dir):
+    """flats with discrete evidence off its states or Gaussian-observed: the two C2F fixtures, random hybrid graphs"""
+    import test_gpu_vi
+    from test_oracle_vi import load_vi
+    out = []
+    for name in ('c2f_hmln_mixed_k2', 'c2f_hmln_mean_k2'):
+        z, meta = load_vi(golden_dir, name)
+        g, rvs, factors = modelio.load_model(meta['model'], API)
+        flat = flatten(g, require_device_potentials=True)
+        out.append((name, flat, None))
+    for seed in range(4):
+        rng = np.random.default_rng(100 + seed)
+        g = test_gpu_vi._random_hybrid_graph(rng, one_discrete_domain=bool(seed % 2))
+        flat = flatten(g, require_device_potentials=True)
+        cand = test_gpu_vi._mln_only_discrete(flat)
+        for v in cand[::2]:
+            flat.rvs[v].value = {2: 0.5, 3: 1.5, 4: 2.5}[len(flat.rvs[v].domain.values)]
+        for v in cand[1::2]:
+            if flat.rvs[v].value is None:
+                flat.rvs[v].value = flat.rvs[v].domain.values[0]
+        flat = flatten(g, require_device_potentials=True)
+        obs_var = np.zeros(flat.V)
+        obs_var[cand[1::2]] = 0.3
+        out.append(('random hybrid %d' % seed, flat, obs_var))
+    return out
+
+
+def test_block_only_rows_serve_only_hidden_or_on_state_discrete_arguments(golden_dir):
+    """property of the device table: for every row still sent as its block alone, each factor using it has only hidden or
+    on-state discrete-role arguments that are no Gaussian observations -- and at those states the block (a host restatement
+    of cq_log_phi) equals the interpreted program at random continuous points to 1e-12"""
+    from lhvi import _abi
+    rng = np.random.default_rng(7)
+    n_pinned = n_checked = 0
+    for label, flat, obs_var in _off_state_cases(golden_dir):
+        off, par, interpreted = _abi.device_potentials(flat, obs_var)
+        pinned = _abi.pinned_rows(flat, obs_var)
+        n_pinned += int(pinned.sum())
+        assert interpreted == _block_only_table(flat)[2] + int(pinned.sum()), label
+        for f in range(flat.F):
+            i = int(flat.fac_pot[f])
+            dev = par[off[i]:off[i + 1]]
+            if flat.pot_kind[i] != P.POT_MLN or dev[2] == 0:
+                continue
+            host = flat.pot_param[flat.pot_off[i]:flat.pot_off[i + 1]]
+            program, block = host[3:3 + 2 * int(host[1])], dev[3:]
+            assert dev[1] == 0 and dev[2] == 3 and block.tobytes() == host[int(host[2]):].tobytes()
+            scope = flat.edge_var[flat.fac_ptr[f]:flat.fac_ptr[f + 1]]
+            role = block[4:4 + scope.size]
+            for _ in range(3):
+                x, idx = np.zeros(scope.size), [0] * scope.size
+                for a, v in enumerate(scope):
+                    states = flat.dom_val[flat.dom_ptr[flat.var_dom[v]]:flat.dom_ptr[flat.var_dom[v] + 1]]
+                    if role[a] >= 0:
+                        val = flat.var_value[v]
+                        if np.isnan(val):
+                            idx[a] = int(rng.integers(states.size))
+                        else:
+                            assert obs_var is None or obs_var[v] == 0, (label, f)
+                            assert (states == val).any(), (label, f)
+                            idx[a] = int(np.flatnonzero(states == val)[0])
+                        x[a] = states[idx[a]]
+                    else:
+                        x[a] = flat.var_value[v] if not np.isnan(flat.var_value[v]) else rng.uniform(-4, 4)
+                want = host[0] * expr.run(list(program), x)
+                assert _cq_log_phi(block, x, idx) == pytest.approx(want, rel=1e-12, abs=1e-12), (label, f)
+                n_checked += 1
+    assert n_pinned > 0 and n_checked > 100

@@ -70,6 +70,8 @@ def test_vi_oracle_matches_reference(golden_dir, name):
 
 # ---- C2FVarInference (coarse-to-fine lifted VI with Gaussian observation clusters) -----------------------------------
 C2F_CASES = ['c2f_rgm_k2', 'c2f_hmln_k2', 'c2f_robot_k2', 'c2f_rkf_tree_k1', 'c2f_rkf_cycle_k1']
+# paper popularity with boolean evidence off its states (PaperIn at 0.5 / 0.25): the formula decides, not a state-indexed table
+C2F_OFF_STATE_CASES = ['c2f_hmln_mixed_k2', 'c2f_hmln_mean_k2']
 C2F_OPTS = dict(k_mean_k=2, k_mean_its=10, output_its=0, min_obs_var=0, gaussian_obs=True)
 
 
@@ -149,10 +151,15 @@ def test_c2fvi_logs_the_map_likelihood_like_the_reference(golden_dir):
         assert not np.allclose(res['fe_log'], [0.0] * len(z['fe_log']))
 
 
-def c2fvi_round_checker(z, rvs, seen):
+def c2fvi_opts(meta):
+    """the schedule's options for a fixture: C2F_OPTS with its gaussian_obs (recorded since the off-state fixtures; True before)"""
+    return dict(C2F_OPTS, gaussian_obs=meta.get('gaussian_obs', True))
+
+
+def c2fvi_round_checker(z, rvs, seen, gaussian_obs=True):
     """observer for lhvi.c2fvi.run_c2fvi: the state right before every round's ADAM updates against what the reference
     held at that point -- partitions (exact), evidence clusters' value / variance and clustered_evidence membership,
-    inherited parameters and ADAM moments, update counter"""
+    inherited parameters and ADAM moments, update counter.  Without Gaussian observations every obs_var is 0."""
     cont = np.array([rv.value is None and rv.domain.continuous for rv in rvs])
     disc = np.array([rv.value is None and not rv.domain.continuous for rv in rvs])
     ev = np.array([rv.value is not None for rv in rvs])
@@ -164,7 +171,7 @@ def c2fvi_round_checker(z, rvs, seen):
         np.testing.assert_allclose(flat.var_value[rvc][ev], z['round_value'][r][ev], rtol=1e-15)
         np.testing.assert_allclose(np.array([np.var([rvs[m].value for m in np.flatnonzero(rvc == rvc[i])]) for i in np.flatnonzero(ev)]),
                                    z['round_variance'][r][ev], rtol=1e-13, atol=1e-300)
-        np.testing.assert_allclose(st['obs_var'][rvc][ev], z['round_variance'][r][ev], rtol=1e-13, atol=1e-300)
+        np.testing.assert_allclose(st['obs_var'][rvc][ev], z['round_variance'][r][ev] if gaussian_obs else 0.0, rtol=1e-13, atol=1e-300)
         tracked = np.array([int(rvc[i]) in st['tracked'] for i in range(len(rvs))], dtype=np.int8)
         # (membership matters only for clusters that can still split: more than one member with different values)
         live = ev & (z['round_variance'][r] > 0)
@@ -206,7 +213,7 @@ def check_c2fvi_result(z, rvs, res):
     np.testing.assert_allclose(res['params']['w_tau'], z['final_w_tau'], rtol=1e-7, atol=1e-10)
 
 
-@pytest.mark.parametrize('name', C2F_CASES)
+@pytest.mark.parametrize('name', C2F_CASES + C2F_OFF_STATE_CASES)
 def test_c2fvi_oracle_matches_reference(golden_dir, name):
     """the coarse-to-fine schedule of lhvi.c2fvi driven by the CPU oracle (Gaussian observation clusters in every
     expectation, oracle/c/vi_oracle.c) against the reference's C2FVarInference: every round's partition and inherited
@@ -217,9 +224,22 @@ def test_c2fvi_oracle_matches_reference(golden_dir, name):
     g, rvs, factors = modelio.load_model(meta['model'], API)
     seen = []
     res = c2fvi.run_c2fvi(g, OracleViEngine(meta['K'], meta['T']), OracleRefiner(g), meta['K'], meta['iterations'], meta['lr'],
-                          dict(C2F_OPTS, update_obs_its=meta['update_obs_its'], kmeans_member_order=kmeans_order_of(meta)),
-                          init=(z['eta_c0'], z['tau_d0']), observer=c2fvi_round_checker(z, rvs, seen))
+                          dict(c2fvi_opts(meta), update_obs_its=meta['update_obs_its'], kmeans_member_order=kmeans_order_of(meta)),
+                          init=(z['eta_c0'], z['tau_d0']), observer=c2fvi_round_checker(z, rvs, seen, meta.get('gaussian_obs', True)))
     assert seen == list(range(meta['iterations'] // meta['update_obs_its']))
     # the fixture does exercise Gaussian observations (the RKF well data is binary: its first split already leaves exact evidence)
     assert (np.nan_to_num(z['round_variance']) > 0).any() or 'rkf' in name
     check_c2fvi_result(z, rvs, res)
+
+
+@pytest.mark.parametrize('name', C2F_OFF_STATE_CASES)
+def test_c2fvi_off_state_fixtures_hold_what_they_are_for(golden_dir, name):
+    """every round of the off-state fixtures holds boolean evidence that is none of its states, next to an evidence cluster with
+    spread (a Gaussian observation when the fixture runs with gaussian_obs, a cluster at its mean otherwise)"""
+    z, meta = load_vi(golden_dir, name)
+    g, rvs, factors = modelio.load_model(meta['model'], API)
+    disc = np.array([rv.value is not None and not rv.domain.continuous for rv in rvs])
+    v = z['round_value'][:, disc]
+    assert ((v != 0) & (v != 1)).any(axis=1).all()
+    assert (np.nan_to_num(z['round_variance']) > 0).any()
+    assert meta['gaussian_obs'] is (name == 'c2f_hmln_mixed_k2')
