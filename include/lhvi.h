@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 14  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 15  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -37,7 +37,8 @@ extern "C" {
                               * 11: LHVI_PBP_V2F_RECORDS (v2f_wide as 8-word records), LHVI_PBP_WIDE_PAIRS, LHVI_PBP_SHARE_CUS;
                               * 12: lhvi_vi_map_bfgs;
                               * 13: lhvi_pbp_f2v selects the kernel families it launches with LHVI_PBP_F2V_* (replacing five bits that skipped kernels);
-                              * 14: lhvi_mws_t, lhvi_mws_init / lhvi_mws_flips, lhvi_lbfgsb_host, lhvi_wall_clock_khz */
+                              * 14: lhvi_mws_t, lhvi_mws_init / lhvi_mws_flips, lhvi_lbfgsb_host, lhvi_wall_clock_khz;
+                              * 15: lhvi_exact_t, lhvi_exact_*, LHVI_E_NOT_PD */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -46,6 +47,7 @@ extern "C" {
 #define LHVI_E_LAUNCH (-2)     /* hipLaunch failed; see lhvi_last_hip_error() */
 #define LHVI_E_UNSUPPORTED (-3)/* e.g. arity > LHVI_MAX_ARITY, n not supported */
 #define LHVI_E_NODEVICE (-4)   /* no HIP device visible */
+#define LHVI_E_NOT_PD (-5)     /* exact baseline: a precision matrix is not positive definite */
 
 /* potential kinds (pot_kind[]); parameter layouts are documented in csrc/potential.hpp */
 #define LHVI_POT_GENERIC 0
@@ -645,6 +647,57 @@ int lhvi_lbfgsb_host(int32_t n, double* x, double (*fun)(const double*, void*), 
                      int32_t* nfev, int32_t* status);
 /* the device wall clock's rate (wall_clock64 ticks per millisecond) of the current device */
 int lhvi_wall_clock_khz(int32_t* khz);
+
+/* ---- Exact hybrid-Gaussian baseline (gibbs/hybrid_gaussian_mrf.py, enumeration half; csrc/exact.hip, csrc/exact.hpp) -------
+ * p(x_d, x_c) = p(x_d) N(x_c; mu(x_d), J(x_d)^-1): every joint state of the discrete variables is one "configuration",
+ * numbered in C order of the table [v_1 .. v_Nd] (first variable most significant).  The caller (lhvi/exact.py) flattens the
+ * factors, in factor order, into two descriptor lists of int32 words:
+ *   quadratic (LogQuadratic: nd = 0; LogHybridQuadratic): [nd, nc, off, (variable, local stride) * nd, continuous variable * nc]
+ *     with quad_par[off + local * (nc * nc + nc + 1)] = A [nc][nc], b [nc], c of the local discrete state;
+ *   table (LogTable): [nd, off, (variable, local stride) * nd] with tab_par[off + local] the log potential.
+ * All doubles. */
+#define LHVI_EXACT_MAX_NC 64
+typedef struct lhvi_exact {
+    int32_t Nd, Nc;
+    int64_t M;                  /* prod(dstates), 1 when Nd = 0 */
+    const int32_t* dstates;     /* [Nd] */
+    const int64_t* dstride;     /* [Nd] stride of the variable in the configuration index */
+    int32_t n_quad;
+    const int32_t* quad_ptr;    /* [n_quad + 1] into quad_desc */
+    const int32_t* quad_desc;
+    const double* quad_par;
+    int32_t n_tab;
+    const int32_t* tab_ptr;     /* [n_tab + 1] into tab_desc */
+    const int32_t* tab_desc;
+    const double* tab_par;
+} lhvi_exact_t;
+
+/* LDS of one workgroup of lhvi_exact_configs (one wavefront, 64 / lanes configurations); 0 for an invalid `lanes` */
+size_t lhvi_exact_lds_bytes(int32_t Nc, int32_t Nd, int32_t lanes);
+/* configurations [cfg_begin, cfg_begin + cfg_count): logp [M] = log p~(x_d) (:57-65), means [M][Nc], vars [M][Nc] = diag(J^-1),
+ * covs [M][Nc][Nc] = J^-1 or NULL; rows indexed by the configuration.  lanes: lanes per configuration, a power of two <= 64;
+ * the results do not depend on it.  bad [1]: the caller sets it to UINT64_MAX; a configuration whose J = -(A + A^T) has a
+ * pivot <= 0 lowers it to its index (atomic min), and its outputs are meaningless (the caller raises, LHVI_E_NOT_PD).
+ * LHVI_E_UNSUPPORTED: Nc > LHVI_EXACT_MAX_NC or more than 64 KiB of LDS. */
+int lhvi_exact_configs(const lhvi_exact_t* m, int64_t cfg_begin, int64_t cfg_count, int32_t lanes, double* logp, double* means,
+                       double* vars, double* covs, uint64_t* bad, void* stream);
+/* logZ [1] = log sum exp logp (max pass, then a sum in a fixed order), table [M] = exp(logp - logZ); ws: 2048 doubles */
+int lhvi_exact_normalize(int64_t M, const double* logp, double* table, double* logZ, double* ws, void* stream);
+/* get_drv_marg (:98-109) of every discrete variable: marg [n_states = sum dstates], variable-major */
+int lhvi_exact_marginals(const lhvi_exact_t* m, int32_t n_states, const double* table, double* marg, void* stream);
+/* per-variable mixture records mix [Nc][M][3] = (log w_k - 1/2 log(2 pi var_kj), mean_kj, 1 / var_kj) (get_crv_marg :76-95) */
+int lhvi_exact_mix_prepare(int32_t Nc, int64_t M, const double* table, const double* means, const double* vars, double* mix,
+                           void* stream);
+/* out [Nc][npts][3] = log density of variable j's mixture at x [Nc][npts] (utils.get_scalar_gm_log_prob), and its first and
+ * second derivative in x */
+int lhvi_exact_mixture(int32_t Nc, int64_t M, const double* mix, int32_t npts, const double* x, double* out, void* stream);
+/* safeguarded Newton on the log density of variable j from each of x [Nc][S] (in / out), clipped to [lo[j], hi[j]]; vmin [Nc]:
+ * smallest component variance (gradient-step scale where the second derivative is not negative); out_logf [Nc][S] */
+int lhvi_exact_map_polish(int32_t Nc, int64_t M, const double* mix, int32_t S, double* x, const double* lo, const double* hi,
+                          const double* vmin, int32_t max_iter, double* out_logf, void* stream);
+/* one configuration on the HOST through the device's code (csrc/exact.hpp); every pointer of m and every output is host
+ * memory; mean, var, cov may be NULL.  LHVI_E_NOT_PD when J is not positive definite. */
+int lhvi_exact_config_host(const lhvi_exact_t* m, int64_t cfg, double* logp, double* mean, double* var, double* cov);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

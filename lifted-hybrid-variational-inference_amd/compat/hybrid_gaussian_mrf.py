@@ -1,0 +1,4 @@
+"""Drop-in alias of the reference module of the same name (gibbs/hybrid_gaussian_mrf.py): re-exports the
+enumeration half from lhvi.exact.  Block Gibbs sampling is not part of this package."""
+from lhvi.exact import (convert_to_bn, get_crv_marg, get_drv_marg, get_drv_marg_map,  # noqa: F401
+                        get_rv_marg_map_from_bn_params)

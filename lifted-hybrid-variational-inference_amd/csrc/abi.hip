@@ -14,6 +14,7 @@ const char* lhvi_strerror(int code) {
         case LHVI_E_LAUNCH: return "HIP launch failed";
         case LHVI_E_UNSUPPORTED: return "unsupported configuration";
         case LHVI_E_NODEVICE: return "no HIP device";
+        case LHVI_E_NOT_PD: return "precision matrix not positive definite";
         default: return "unknown error";
     }
 }

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 14            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 15            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -120,6 +120,15 @@ class MwsStruct(C.Structure):
                [(n, C.c_void_p) for n in ('rp_init', 'rp_clause', 'rp_walk', 'rp_walk_k', 'rp_noise', 'rp_post', 'out_score',
                                           'out_unsat', 'out_winner', 'out_accept', 'out_val')]
 
+
+class ExactStruct(C.Structure):
+    _fields_ = [('Nd', C.c_int32), ('Nc', C.c_int32), ('M', C.c_int64), ('dstates', C.c_void_p), ('dstride', C.c_void_p),
+                ('n_quad', C.c_int32), ('quad_ptr', C.c_void_p), ('quad_desc', C.c_void_p), ('quad_par', C.c_void_p),
+                ('n_tab', C.c_int32), ('tab_ptr', C.c_void_p), ('tab_desc', C.c_void_p), ('tab_par', C.c_void_p)]
+
+
+E_NOT_PD = -5               # LHVI_E_NOT_PD
+EXACT_MAX_NC = 64           # LHVI_EXACT_MAX_NC
 
 # the objective of lhvi_lbfgsb_host: double fun(const double* x, void* ctx)
 LBFGSB_FUN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_void_p)
@@ -190,6 +199,14 @@ SIGNATURES = {
     'lhvi_mws_flips': (C.c_int, [_G, _P, C.POINTER(MwsStruct), _i32, _i32, _vp]),
     'lhvi_lbfgsb_host': (C.c_int, [_i32, _vp, LBFGSB_FUN, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_wall_clock_khz': (C.c_int, [_vp]),
+    'lhvi_exact_lds_bytes': (_sz, [_i32, _i32, _i32]),
+    'lhvi_exact_configs': (C.c_int, [C.POINTER(ExactStruct), _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_exact_normalize': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_exact_marginals': (C.c_int, [C.POINTER(ExactStruct), _i32, _vp, _vp, _vp]),
+    'lhvi_exact_mix_prepare': (C.c_int, [_i32, _i64, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_exact_mixture': (C.c_int, [_i32, _i64, _vp, _i32, _vp, _vp, _vp]),
+    'lhvi_exact_map_polish': (C.c_int, [_i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'lhvi_exact_config_host': (C.c_int, [C.POINTER(ExactStruct), _i64, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

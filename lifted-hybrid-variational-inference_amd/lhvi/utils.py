@@ -104,3 +104,37 @@ def log_likelihood_flat(dg, x):
     out = torch.empty(1, dtype=torch.float64, device=dg.device)
     _abi.check(l.lhvi_log_likelihood(dg.g, dg.p, _abi.ptr(xd), _abi.ptr(out), _abi.ptr(ws), nbytes, _abi.stream_ptr()))
     return float(out.item())
+
+
+def set_log_potential_funs(factors, skip_existing=True):
+    """``osi/utils.py:188-205``: set ``factor.log_potential_fun`` from ``factor.potential.to_log_potential()``, one object per
+    distinct potential (the potentials' own hash / eq), skipping a group whose factors all have one unless told otherwise"""
+    groups = {}
+    for f in factors:
+        groups.setdefault(f.potential, []).append(f)
+    for pot, like in groups.items():
+        if skip_existing and all(f.log_potential_fun is not None for f in like):
+            continue
+        lp = pot.to_log_potential()
+        for f in like:
+            f.log_potential_fun = lp
+
+
+def set_nbrs_idx_in_factors(factors, Vd_idx, Vc_idx):
+    """``osi/utils.py:417-429``: ``factor.disc_nb_idx / cont_nb_idx`` = positions of the factor's discrete / continuous
+    neighbours in Vd / Vc, in scope order"""
+    for f in factors:
+        f.disc_nb_idx = tuple(Vd_idx[rv] for rv in f.nb if rv.domain_type[0] == 'd')
+        f.cont_nb_idx = tuple(Vc_idx[rv] for rv in f.nb if rv.domain_type[0] == 'c')
+
+
+def get_conditional_quadratic(A, b, c, obs_args_vals):
+    """``osi/utils.py:249-276``: the quadratic over the remaining arguments x of [x y]'A[x y] + b'[x y] + c with the arguments
+    ``obs_args_vals`` = {index: value} fixed: (A_xx, A_xy y + A_yx' y + b_x, y'A_yy y + b_y'y + c)"""
+    A, b = np.asarray(A, dtype=np.float64), np.asarray(b, dtype=np.float64)
+    yi = np.array(list(obs_args_vals.keys()), dtype=int)
+    y = np.array([obs_args_vals[i] for i in yi], dtype=np.float64)
+    xi = np.setdiff1d(np.arange(len(b)), yi)
+    b_cond = A[np.ix_(xi, yi)] @ y + A[np.ix_(yi, xi)].T @ y + b[xi]
+    c_cond = np.dot(y, A[np.ix_(yi, yi)] @ y) + np.dot(b[yi], y) + c
+    return A[np.ix_(xi, xi)], b_cond, c_cond

@@ -1,0 +1,254 @@
+"""CPU suite of the exact hybrid-Gaussian baseline (lhvi/exact.py): the host flattening of every model, the device's
+per-configuration code run on the host (lhvi_exact_config_host) against the recorded reference values, the error for a
+precision matrix that is not positive definite, the compat alias, and the failure without a GPU.
+
+Tolerances (docs/kernels_exact.md): log table, logZ, means, variances, covariances rtol 1e-10 against the reference (both
+sides are backward-stable solves of the same matrix: c n cond(J) u with n <= 32, cond <= 500 asserted at capture)."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+import exact_models as em
+from lhvi import _abi, exact
+from lhvi.graph import F, RV, Domain
+from lhvi.potentials import LogHybridQuadratic, LogQuadratic, LogTable
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd')
+RTOL = 1e-10
+
+
+def numpy_config(factors, dstates, Nc, config):
+    """convert_to_bn's loop body (:30-65) restated on this package's classes: (log p~, mu, Sig)"""
+    A, b, c, t = np.zeros((Nc, Nc)), np.zeros(Nc), 0.0, 0.0
+    for f in factors:
+        lp = f.log_potential_fun
+        xd = tuple(config[i] for i in f.disc_nb_idx)
+        if isinstance(lp, LogTable):
+            t += lp(xd)
+            continue
+        A_, b_, c_ = (lp.A, lp.b, lp.c) if isinstance(lp, LogQuadratic) else lp.get_quadratic_params_given_x_d(xd)
+        sc = f.cont_nb_idx
+        for i in range(len(sc)):
+            for j in range(len(sc)):
+                A[sc[i], sc[j]] += A_[i, j]
+            b[sc[i]] += b_[i]
+        c += c_
+    Sig = np.linalg.inv(-2. * A)
+    mu = Sig @ b
+    return t + (Nc / 2 * np.log(2 * np.pi) + 0.5 * np.linalg.slogdet(Sig)[1] + 0.5 * mu @ b + c), mu, Sig
+
+
+def test_flatten_ref_hybrid2_descriptors():
+    model = em.build('ref_hybrid2')
+    em.set_indices(model)
+    m = exact.flatten_factors(model['factors'], [3, 2], 2)
+    assert (m.Nd, m.Nc, m.M) == (2, 2, 6) and list(m.dstride) == [2, 1]
+    # hybrid factor: one discrete argument (variable 0, local stride 1), two continuous; then the unary quadratic
+    assert list(m.quad_ptr) == [0, 7, 11]
+    assert list(m.quad_desc) == [1, 2, 0, 0, 1, 0, 1, 0, 1, 21, 0]
+    assert m.quad_par.size == 3 * 7 + 3
+    np.testing.assert_array_equal(m.quad_par[7:14], [-0.5, 0, 0, -0.5, 0., 1., -0.5])
+    assert list(m.tab_ptr) == [0, 4, 10]
+    assert list(m.tab_desc) == [1, 0, 0, 1, 2, 3, 0, 2, 1, 1]
+    np.testing.assert_array_equal(m.tab_par, [-0.1, 0, 2., 2., 0, -0.1, 1, 0, 0.2])
+
+
+@pytest.mark.parametrize('name', ['rand_3_2', 'rand_8_8', 'rand_12_16'])
+def test_flatten_strides_and_sharing(name):
+    model = em.build(name)
+    em.set_indices(model)
+    dstates = [rv.dstates for rv in model['Vd']]
+    m = exact.flatten_factors(model['factors'], dstates, len(model['Vc']))
+    assert m.M == int(np.prod(dstates))
+    rng = np.random.RandomState(0)
+    for _ in range(20):
+        cfg = [rng.randint(d) for d in dstates]
+        assert int(np.dot(cfg, m.dstride)) == int(np.ravel_multi_index(cfg, dstates))
+    assert m.n_quad + m.n_tab == len(model['factors'])
+    # a shared log potential is stored once
+    twice = exact.flatten_factors(model['factors'] + model['factors'], dstates, len(model['Vc']))
+    assert twice.quad_par.size == m.quad_par.size and twice.n_quad == 2 * m.n_quad
+
+
+@pytest.mark.parametrize('name', ['ref_hybrid2', 'rand_3_2', 'rand_8_8', 'rand_12_16'])
+def test_host_configuration_equals_numpy_restatement(name):
+    """flattening + the device's arithmetic against the reference's loop body in NumPy on the same objects"""
+    model = em.build(name)
+    em.set_indices(model)
+    dstates = [rv.dstates for rv in model['Vd']]
+    Nc = len(model['Vc'])
+    m = exact.flatten_factors(model['factors'], dstates, Nc)
+    rng = np.random.RandomState(1)
+    for cfg in sorted(set([0, m.M - 1] + list(rng.randint(m.M, size=12)))):
+        config = np.unravel_index(cfg, dstates)
+        want_lp, want_mu, want_sig = numpy_config(model['factors'], dstates, Nc, config)
+        lp, mu, var, cov = exact.config_host(m, cfg, cov=True)
+        em.assert_log_close(lp, want_lp, RTOL, 'log p~')
+        np.testing.assert_allclose(mu, want_mu, rtol=RTOL, atol=1e-12)
+        np.testing.assert_allclose(cov, want_sig, rtol=RTOL, atol=1e-12)
+        np.testing.assert_array_equal(var, np.diagonal(cov))
+        np.testing.assert_array_equal(cov, cov.T)
+
+
+@pytest.mark.parametrize('name', em.NAMES)
+def test_host_configurations_match_reference(name):
+    """lhvi_exact_config_host on every recorded configuration of every fixture (evidence and the automatic MLN conversion
+    included) within the tolerances of the module docstring"""
+    gold = em.load_golden(name)
+    _, s = em.solver(name)
+    m = s.model
+    assert list(m.dstates) == list(gold['dstates'])
+    assert gold['max_cond'] <= 500
+    lps = []
+    for row, cfg in enumerate(gold['cfg']):
+        lp, mu, var, cov = exact.config_host(m, int(cfg), cov=True)
+        lps.append(lp + s.log_const)
+        np.testing.assert_allclose(mu, gold['means'][row], rtol=RTOL, atol=1e-12)
+        np.testing.assert_allclose(var, gold['variances'][row], rtol=RTOL)
+        if 'covs_tril' in gold:
+            np.testing.assert_allclose(em.tril(cov), gold['covs_tril'][row], rtol=RTOL, atol=1e-13)
+    lps = np.array(lps)
+    if name in em.FULL:
+        mx = lps.max()
+        em.assert_log_close(mx + np.log(np.exp(lps - mx).sum()), gold['logZ'], RTOL, 'logZ')
+    em.assert_log_close(lps - gold['logZ'], np.log(gold['table']), RTOL, 'log table')
+
+
+def test_mln_conversion_equals_hand_conversion():
+    """osi/hybrid_mln_test_0.py:89-99 by expr.conditional_quadratic: the hybrid blocks coefficient for coefficient, the table
+    up to the rounding of the hand conversion's log(exp(w f))"""
+    hand = em.build('ref_mln0', hand=True)
+    _, s = em.solver('ref_mln0')
+    auto = [f.log_potential_fun for f in s.factors]
+    want = [f.log_potential_fun for f in hand['factors']]
+    assert isinstance(auto[0], LogHybridQuadratic) and isinstance(auto[1], LogTable) and isinstance(auto[2], LogQuadratic)
+    for k in ('A', 'b', 'c'):
+        np.testing.assert_array_equal(np.asarray(getattr(auto[0], k)), np.asarray(getattr(want[0], k)))
+    np.testing.assert_allclose(auto[1].table, want[1].table, rtol=0, atol=1e-16)
+    assert s.factors[0].disc_nb_idx == (0,) and s.factors[0].cont_nb_idx == (0, 1)
+
+
+def test_conversion_errors_name_the_factor():
+    from lhvi.mln import MLNHardPotential, MLNPotential
+    dc, db = Domain((-10, 10), continuous=True), Domain((0, 1))
+    x, y, z, d = RV(dc), RV(dc), RV(dc), RV(db)
+    cubic = F(MLNPotential(lambda a: a[0] * a[1] * a[1] * a[1], w=1.0), nb=[d, x])
+    with pytest.raises(exact.NotConditionallyQuadratic, match='factor #%d' % cubic.id):
+        exact.ExactHybridGaussian(factors=[cubic], Vd=[d], Vc=[x])
+    three = F(MLNPotential(lambda a: -(a[0] - a[1]) ** 2 - a[2] ** 2, w=1.0), nb=[x, y, z])
+    with pytest.raises(exact.NotConditionallyQuadratic, match='factor #%d' % three.id):
+        exact.ExactHybridGaussian(factors=[three], Vd=[], Vc=[x, y, z])
+    with pytest.raises(NotImplementedError):
+        exact.ExactHybridGaussian(factors=[F(MLNHardPotential(lambda a: a[0]), nb=[d])], Vd=[d], Vc=[])
+
+
+def not_pd_model():
+    """two binary variables, two continuous: -(x - y)^2 / 2 is singular on its own, the hybrid term on (d1, x) adds
+    -x^2 / 2 in state 0 and takes x^2 / 4 away in state 1, where J becomes indefinite: configurations (0, 1) and (1, 1)"""
+    db, dc = Domain((0, 1)), Domain((-10, 10), continuous=True)
+    d0, d1, x, y = RV(db), RV(db), RV(dc), RV(dc)
+    factors = [F(nb=(x, y), log_potential_fun=LogQuadratic(-0.5 * np.array([[1., -1.], [-1., 1.]]), np.zeros(2), 0.)),
+               F(nb=(d1, x), log_potential_fun=LogHybridQuadratic(np.array([[[-0.5]], [[0.25]]]), np.zeros((2, 1)), np.zeros(2))),
+               F(nb=(d0,), log_potential_fun=LogTable(np.array([0.1, 0.2])))]
+    return factors, [d0, d1], [x, y]
+
+
+def test_not_positive_definite_reports_the_lowest_configuration():
+    factors, Vd, Vc = not_pd_model()
+    s = exact.ExactHybridGaussian(factors=factors, Vd=Vd, Vc=Vc)
+    for cfg in (0, 2):
+        exact.config_host(s.model, cfg)
+    for cfg, states in ((1, '(0, 1)'), (3, '(1, 1)')):
+        with pytest.raises(ValueError, match='not positive definite.*%s' % states.replace('(', r'\(').replace(')', r'\)')):
+            exact.config_host(s.model, cfg)
+    rc = _abi.lib().lhvi_exact_config_host(s.model.host_struct(), 1, None, None, None, None)
+    assert rc == _abi.E_NOT_PD and _abi.lib().lhvi_strerror(rc) == b'precision matrix not positive definite'
+
+
+def test_compat_alias_exports_the_reference_names():
+    code = ('import sys; sys.path[:] = [%r, %r] + [p for p in sys.path if "site-packages" in p or "dist-packages" in p or '
+            '"python3" in p and "repo" not in p]\n'
+            'import hybrid_gaussian_mrf as h, lhvi.exact as e, utils\n'
+            'for n in ("convert_to_bn", "get_crv_marg", "get_drv_marg", "get_drv_marg_map", "get_rv_marg_map_from_bn_params"):\n'
+            '    assert getattr(h, n) is getattr(e, n), n\n'
+            'assert utils.set_nbrs_idx_in_factors and utils.set_log_potential_funs and utils.get_conditional_quadratic\n'
+            'print("ok")') % (os.path.join(PKG, 'compat'), PKG)
+    out = subprocess.run([sys.executable, '-c', code], capture_output=True, text=True, cwd='/')
+    assert out.returncode == 0, out.stderr
+    assert out.stdout.strip() == 'ok'
+
+
+def test_helpers_equal_numpy():
+    rng = np.random.RandomState(3)
+    t = rng.rand(3, 2, 2)
+    t /= t.sum()
+    np.testing.assert_allclose(exact.get_drv_marg(t, 1), t.sum(axis=(0, 2)))
+    assert exact.get_drv_marg_map(t, 0) == np.argmax(t.sum(axis=(1, 2)))
+    mu, cov = rng.randn(3, 2, 2, 4), rng.randn(3, 2, 2, 4, 4)
+    w, m, v = exact.get_crv_marg(t, mu, cov, 2)
+    assert w.shape == m.shape == v.shape == (12,)
+    np.testing.assert_array_equal(v, cov[..., 2, 2].ravel())
+
+
+def test_set_log_potential_funs_shares_objects():
+    from lhvi.potentials import X2Potential
+    from lhvi.utils import set_log_potential_funs
+    dc = Domain((-10, 10), continuous=True)
+    a, b = F(X2Potential(1., 2.), nb=[RV(dc)]), F(X2Potential(1., 2.), nb=[RV(dc)])
+    set_log_potential_funs([a, b])
+    assert a.log_potential_fun is b.log_potential_fun and isinstance(a.log_potential_fun, LogQuadratic)
+    keep = a.log_potential_fun
+    set_log_potential_funs([a, b])
+    assert a.log_potential_fun is keep
+    set_log_potential_funs([a, b], skip_existing=False)
+    assert a.log_potential_fun is not keep
+
+
+def test_limits_raise_before_any_launch():
+    dc = Domain((-10, 10), continuous=True)
+    Vc = [RV(dc) for _ in range(exact.MAX_NC + 1)]
+    factors = [F(nb=(rv,), log_potential_fun=LogQuadratic(-np.ones((1, 1)), np.zeros(1), 0.)) for rv in Vc]
+    s = exact.ExactHybridGaussian(factors=factors, Vd=[], Vc=Vc)
+    from conftest import has_gpu
+    with pytest.raises(ValueError if has_gpu() else _abi.LhviError):
+        s.run()
+    assert exact.output_bytes(1 << 20, 32, False) == 8 * (1 << 20) * 66
+    assert exact.output_bytes(1 << 20, 32, True) == 8 * (1 << 20) * (66 + 1024)
+
+
+def test_no_cpu_fallback_without_gpu():
+    from conftest import has_gpu
+    _, s = em.solver('ref_hybrid2')
+    if has_gpu():
+        s.run()
+        return
+    with pytest.raises(_abi.LhviError):
+        s.run()
+    model = em.build('ref_hybrid2')
+    em.set_indices(model)
+    with pytest.raises(_abi.LhviError):
+        exact.convert_to_bn(model['factors'], model['Vd'], model['Vc'])
+
+
+def test_host_code_without_continuous_or_discrete_variables():
+    """Nc = 0: a configuration is its table sum; Nd = 0: one configuration, the plain Gaussian integral"""
+    rng = np.random.RandomState(5)
+    Vd = [RV(Domain(tuple(range(d)))) for d in (2, 3)]
+    tabs = [F(nb=(Vd[0],), log_potential_fun=LogTable(rng.randn(2))), F(nb=(Vd[1], Vd[0]), log_potential_fun=LogTable(rng.randn(3, 2)))]
+    s = exact.ExactHybridGaussian(factors=tabs, Vd=Vd, Vc=[])
+    for cfg in range(6):
+        i, j = np.unravel_index(cfg, (2, 3))
+        lp, mu, var, cov = exact.config_host(s.model, cfg, cov=True)
+        assert abs(lp - (tabs[0].log_potential_fun((i,)) + tabs[1].log_potential_fun((j, i)))) <= 1e-15
+        assert mu.shape == var.shape == (0,) and cov.shape == (0, 0)
+    x = RV(Domain((-10, 10), continuous=True))
+    g1 = exact.ExactHybridGaussian(factors=[F(nb=(x,), log_potential_fun=LogQuadratic(-np.ones((1, 1)), np.array([3.]), 0.5))],
+                                   Vd=[], Vc=[x])
+    lp, mu, var, _ = exact.config_host(g1.model, 0)
+    # J = 2, b = 3: mu = 1.5, var = 0.5, log integral = 1/2 log(2 pi / 2) + b^2 / (2 J) + c
+    assert abs(mu[0] - 1.5) <= 1e-15 and abs(var[0] - 0.5) <= 1e-15
+    assert abs(lp - (0.5 * np.log(np.pi) + 2.25 + 0.5)) <= 1e-14
