@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 15  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 16  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -38,7 +38,8 @@ extern "C" {
                               * 12: lhvi_vi_map_bfgs;
                               * 13: lhvi_pbp_f2v selects the kernel families it launches with LHVI_PBP_F2V_* (replacing five bits that skipped kernels);
                               * 14: lhvi_mws_t, lhvi_mws_init / lhvi_mws_flips, lhvi_lbfgsb_host, lhvi_wall_clock_khz;
-                              * 15: lhvi_exact_t, lhvi_exact_*, LHVI_E_NOT_PD */
+                              * 15: lhvi_exact_t, lhvi_exact_*, LHVI_E_NOT_PD;
+                              * 16: lhvi_gibbs_t, lhvi_gibbs_* */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -47,7 +48,7 @@ extern "C" {
 #define LHVI_E_LAUNCH (-2)     /* hipLaunch failed; see lhvi_last_hip_error() */
 #define LHVI_E_UNSUPPORTED (-3)/* e.g. arity > LHVI_MAX_ARITY, n not supported */
 #define LHVI_E_NODEVICE (-4)   /* no HIP device visible */
-#define LHVI_E_NOT_PD (-5)     /* exact baseline: a precision matrix is not positive definite */
+#define LHVI_E_NOT_PD (-5)     /* exact baseline, block Gibbs: a precision matrix is not positive definite */
 
 /* potential kinds (pot_kind[]); parameter layouts are documented in csrc/potential.hpp */
 #define LHVI_POT_GENERIC 0
@@ -698,6 +699,59 @@ int lhvi_exact_map_polish(int32_t Nc, int64_t M, const double* mix, int32_t S, d
 /* one configuration on the HOST through the device's code (csrc/exact.hpp); every pointer of m and every output is host
  * memory; mean, var, cov may be NULL.  LHVI_E_NOT_PD when J is not positive definite. */
 int lhvi_exact_config_host(const lhvi_exact_t* m, int64_t cfg, double* logp, double* mean, double* var, double* cov);
+
+/* ---- Block Gibbs sampling in a hybrid Gaussian MRF (gibbs/hybrid_gaussian_mrf.py::block_gibbs_sample, gibbs/disc_mrf.py;
+ * csrc/gibbs.hip, csrc/gibbs.hpp) -------------------------------------------------------------------------------------------
+ * Many independent chains.  One outer iteration: x_c | x_d from the Cholesky factor of J(x_d) (x_c = L^-T (L^-1 b + z)), the
+ * reduced log table of every strictly hybrid factor at x_c, then disc_block_its sweeps of single-site Gibbs over x_d.
+ * ex: the flat model of the exact baseline; ex.M and ex.dstride are not read (a chain is not a configuration index).
+ * A "hybrid" factor is a quadratic descriptor with nd > 0; hybrid factor h is quadratic descriptor hyb_quad[h] and its reduced
+ * table occupies [hyb_off[h], hyb_off[h + 1]) of the chain's table row, in C order of its discrete scope.
+ * The draw of counter (chain, iteration, index, tag) comes from Philox4x32-10 keyed by seed. */
+typedef struct lhvi_gibbs {
+    lhvi_exact_t ex;
+    const int32_t* dstate_off;  /* [Nd + 1] prefix sums of ex.dstates (rows of the state counts) */
+    const int32_t* vt_ptr;      /* [Nd + 1] into vt_fac */
+    const int32_t* vt_fac;      /* table descriptors with variable n in scope, in factor order */
+    const int32_t* vh_ptr;      /* [Nd + 1] into vh_fac */
+    const int32_t* vh_fac;      /* hybrid factors (h) with variable n in scope, in factor order */
+    int32_t n_hyb;
+    const int32_t* hyb_quad;    /* [n_hyb] */
+    const int32_t* hyb_off;     /* [n_hyb + 1] */
+    int32_t table_doubles;      /* hyb_off[n_hyb] */
+    int32_t max_states;         /* max ex.dstates (1 when Nd = 0) */
+    double* table_scratch;      /* NULL: the reduced tables live in LDS.  Otherwise one row of table_doubles per chain, for the
+                                 * number of chains rounded up to a multiple of 64 */
+    int32_t disc_block_its;
+    int32_t num_burnin;         /* iterations [num_burnin, num_burnin + num_samples) are kept */
+    int32_t num_samples;        /* rows of a chain in the sample arrays */
+    uint64_t seed;
+} lhvi_gibbs_t;
+
+/* LDS of one workgroup of lhvi_gibbs_run (one wavefront, 64 / lanes chains).  table_doubles: the doubles a chain keeps in LDS
+ * for the discrete block = max_states + (the reduced tables when they live in LDS: lhvi_gibbs_t.table_doubles, else 0).
+ * 0 for an invalid `lanes`. */
+size_t lhvi_gibbs_lds_bytes(int32_t Nc, int32_t Nd, int32_t table_doubles, int32_t lanes);
+/* the initial state x_d [chains][Nd] (int32): variable n of chain c = floor(u dstates[n]) with u the uniform of counter
+ * (c, n, 0, init tag) */
+int lhvi_gibbs_init(const lhvi_gibbs_t* m, int64_t chains, int32_t* x_d, void* stream);
+/* iterations [it_begin, it_end) of every chain.  x_d [chains][Nd]: in / out, so a run is any number of calls.  lanes: lanes
+ * per chain, a power of two <= 64; a chain's samples depend neither on it, nor on `chains`, nor on the split into calls.
+ * z [iters][chains][Nc], u [iters][chains][disc_block_its][Nd]: injected draws (rows by absolute iteration), or NULL for the
+ * Philox stream.  Outputs, each NULL or: disc [chains][num_samples][Nd] (int32), cont [chains][num_samples][Nc], and the
+ * accumulators over the kept iterations, which the caller zeroes before the first call: counts [chains][sum dstates] (int32),
+ * sum1 [chains][Nc] = sum x_c, sum2 [chains][Nc (Nc + 1) / 2] = sum x_c x_c^T, lower triangle by rows.
+ * bad [1]: the caller sets it to UINT64_MAX; a chain whose J is not positive definite lowers it to (chain << 32 | iteration)
+ * (atomic min), keeps its x_d of that moment and stores nothing more.
+ * LHVI_E_UNSUPPORTED: Nc > LHVI_EXACT_MAX_NC or more than 64 KiB of LDS. */
+int lhvi_gibbs_run(const lhvi_gibbs_t* m, int64_t chains, int32_t it_begin, int32_t it_end, int32_t lanes, int32_t* x_d,
+                   const double* z, const double* u, int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2,
+                   uint64_t* bad, void* stream);
+/* one chain on the HOST through the device's code (csrc/gibbs.hpp) with injected draws z [iters][Nc], u [iters][its][Nd];
+ * every pointer of m and every argument is host memory, the outputs are this chain's rows and may be NULL.  m->table_scratch
+ * is ignored.  LHVI_E_NOT_PD when a J is not positive definite (x_d then holds the state). */
+int lhvi_gibbs_chain_host(const lhvi_gibbs_t* m, int32_t it_begin, int32_t it_end, int32_t* x_d, const double* z, const double* u,
+                          int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

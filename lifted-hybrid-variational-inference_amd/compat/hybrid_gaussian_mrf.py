@@ -1,4 +1,5 @@
 """Drop-in alias of the reference module of the same name (gibbs/hybrid_gaussian_mrf.py): re-exports the
-enumeration half from lhvi.exact.  Block Gibbs sampling is not part of this package."""
+enumeration half from lhvi.exact and the block Gibbs sampler from lhvi.gibbs."""
 from lhvi.exact import (convert_to_bn, get_crv_marg, get_drv_marg, get_drv_marg_map,  # noqa: F401
                         get_rv_marg_map_from_bn_params)
+from lhvi.gibbs import HybridGaussianSampler, block_gibbs_sample  # noqa: F401

@@ -36,22 +36,20 @@ LHVI_HD int64_t local_cfg(const int32_t* p, int nd, const int32_t* dig) {
     return l;
 }
 
-// One configuration.  Outputs (each may be null): logp = log p~(x_d), mean [Nc], var [Nc] = diag(J^-1), cov [Nc][Nc] = J^-1.
-// Returns 1 when J is not positive definite (a pivot <= 0 or NaN), the same value in every lane.
+// The three steps of a configuration that the block Gibbs sampler (csrc/gibbs.hpp) enters with the discrete digits already in
+// the workspace.  config() below calls them in this order; their floating-point operations are config()'s own.
+//
+// assemble: the joint quadratic A (mat, all of it), b and the constant c of the discrete state `dig`: every factor in factor
+// order, a lane adds the rows it owns (utils.get_joint_quadratic_params)
 template <class Ctx>
-LHVI_HD int config(const lhvi_exact_t& m, int64_t cfg, double* W, const Ctx& ctx, double* logp, double* mean, double* var,
-                   double* cov) {
-    const int Nc = m.Nc, Nd = m.Nd, ld = ld_of(Nc);
-    double *mat = W, *b = W + Nc * ld, *y = b + Nc, *mu = y + Nc, *ldiag = mu + Nc, *dinv = ldiag + Nc;
-    int32_t* dig = reinterpret_cast<int32_t*>(dinv + Nc);
-    for (int d = ctx.lane; d < Nd; d += ctx.lanes) dig[d] = (int32_t)((cfg / m.dstride[d]) % m.dstates[d]);
+LHVI_HD void assemble(const lhvi_exact_t& m, const int32_t* dig, double* mat, double* b, const Ctx& ctx, double& c) {
+    const int Nc = m.Nc, ld = ld_of(Nc);
     for (int r = ctx.lane; r < Nc; r += ctx.lanes) {
         for (int j = 0; j < Nc; ++j) mat[r * ld + j] = 0.0;
         b[r] = 0.0;
     }
     ctx.sync();
-    // the joint quadratic: every factor in factor order, a lane adds the rows it owns (utils.get_joint_quadratic_params)
-    double c = 0.0;
+    c = 0.0;
     for (int f = 0; f < m.n_quad; ++f) {
         const int32_t* rec = m.quad_desc + m.quad_ptr[f];
         const int nd = rec[0], nc = rec[1];
@@ -65,20 +63,36 @@ LHVI_HD int config(const lhvi_exact_t& m, int64_t cfg, double* W, const Ctx& ctx
                 }
         c += P[nc * nc + nc];
     }
+}
+
+// the log tables' sum at `dig`, in factor order
+LHVI_HD double table_sum(const lhvi_exact_t& m, const int32_t* dig) {
     double ts = 0.0;
     for (int f = 0; f < m.n_tab; ++f) {
         const int32_t* rec = m.tab_desc + m.tab_ptr[f];
         ts += m.tab_par[rec[1] + local_cfg(rec + 2, rec[0], dig)];
     }
-    ctx.sync();
-    // J = -(A + A^T), lower triangle in place (= -2A for the symmetric A every potential class produces); the upper triangle
-    // is read here for the last time
+    return ts;
+}
+
+// form_J: J = -(A + A^T), lower triangle in place (= -2A for the symmetric A every potential class produces); the upper
+// triangle is read here for the last time.  The caller syncs before (assemble's rows are complete) and this syncs after.
+template <class Ctx>
+LHVI_HD void form_J(int Nc, double* mat, const Ctx& ctx) {
+    const int ld = ld_of(Nc);
     for (int r = ctx.lane; r < Nc; r += ctx.lanes)
         for (int j = 0; j <= r; ++j) mat[r * ld + j] = -(mat[r * ld + j] + mat[j * ld + r]);
     ctx.sync();
-    // Cholesky, left-looking, one column per step: a lane forms its row's entry and (redundantly, same bits) the pivot
+}
+
+// cholesky: left-looking, one column per step: a lane forms its row's entry and (redundantly, same bits) the pivot.  L below
+// the diagonal of mat, its diagonal in ldiag, the reciprocal in dinv.  Returns 1 on a pivot <= 0 or NaN (taken as 1), the same
+// value in every lane.
+template <class Ctx>
+LHVI_HD int cholesky(int Nc, double* mat, double* ldiag, double* dinv, const Ctx& ctx, double& logdet) {
+    const int ld = ld_of(Nc);
     int bad = 0;
-    double logdet = 0.0;
+    logdet = 0.0;
     for (int j = 0; j < Nc; ++j) {
         double d = mat[j * ld + j];
         for (int k = 0; k < j; ++k) d -= mat[j * ld + k] * mat[j * ld + k];
@@ -95,6 +109,24 @@ LHVI_HD int config(const lhvi_exact_t& m, int64_t cfg, double* W, const Ctx& ctx
         }
         ctx.sync();
     }
+    return bad;
+}
+
+// One configuration.  Outputs (each may be null): logp = log p~(x_d), mean [Nc], var [Nc] = diag(J^-1), cov [Nc][Nc] = J^-1.
+// Returns 1 when J is not positive definite (a pivot <= 0 or NaN), the same value in every lane.
+template <class Ctx>
+LHVI_HD int config(const lhvi_exact_t& m, int64_t cfg, double* W, const Ctx& ctx, double* logp, double* mean, double* var,
+                   double* cov) {
+    const int Nc = m.Nc, Nd = m.Nd, ld = ld_of(Nc);
+    double *mat = W, *b = W + Nc * ld, *y = b + Nc, *mu = y + Nc, *ldiag = mu + Nc, *dinv = ldiag + Nc;
+    int32_t* dig = reinterpret_cast<int32_t*>(dinv + Nc);
+    for (int d = ctx.lane; d < Nd; d += ctx.lanes) dig[d] = (int32_t)((cfg / m.dstride[d]) % m.dstates[d]);
+    double c, logdet;
+    assemble(m, dig, mat, b, ctx, c);
+    const double ts = table_sum(m, dig);
+    ctx.sync();
+    form_J(Nc, mat, ctx);
+    const int bad = cholesky(Nc, mat, ldiag, dinv, ctx, logdet);
     // X = L^-1, column q by the lane that owns row q, stored transposed above the diagonal: mat[q][i] = X[i][q], i > q
     for (int q = ctx.lane; q < Nc; q += ctx.lanes)
         for (int i = q + 1; i < Nc; ++i) {

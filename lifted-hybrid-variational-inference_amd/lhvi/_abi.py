@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 15            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 16            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -125,6 +125,13 @@ class ExactStruct(C.Structure):
     _fields_ = [('Nd', C.c_int32), ('Nc', C.c_int32), ('M', C.c_int64), ('dstates', C.c_void_p), ('dstride', C.c_void_p),
                 ('n_quad', C.c_int32), ('quad_ptr', C.c_void_p), ('quad_desc', C.c_void_p), ('quad_par', C.c_void_p),
                 ('n_tab', C.c_int32), ('tab_ptr', C.c_void_p), ('tab_desc', C.c_void_p), ('tab_par', C.c_void_p)]
+
+
+class GibbsStruct(C.Structure):
+    _fields_ = [('ex', ExactStruct), ('dstate_off', C.c_void_p), ('vt_ptr', C.c_void_p), ('vt_fac', C.c_void_p),
+                ('vh_ptr', C.c_void_p), ('vh_fac', C.c_void_p), ('n_hyb', C.c_int32), ('hyb_quad', C.c_void_p),
+                ('hyb_off', C.c_void_p), ('table_doubles', C.c_int32), ('max_states', C.c_int32), ('table_scratch', C.c_void_p),
+                ('disc_block_its', C.c_int32), ('num_burnin', C.c_int32), ('num_samples', C.c_int32), ('seed', C.c_uint64)]
 
 
 E_NOT_PD = -5               # LHVI_E_NOT_PD
@@ -207,6 +214,10 @@ SIGNATURES = {
     'lhvi_exact_mixture': (C.c_int, [_i32, _i64, _vp, _i32, _vp, _vp, _vp]),
     'lhvi_exact_map_polish': (C.c_int, [_i32, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _i32, _vp, _vp]),
     'lhvi_exact_config_host': (C.c_int, [C.POINTER(ExactStruct), _i64, _vp, _vp, _vp, _vp]),
+    'lhvi_gibbs_lds_bytes': (_sz, [_i32, _i32, _i32, _i32]),
+    'lhvi_gibbs_init': (C.c_int, [C.POINTER(GibbsStruct), _i64, _vp, _vp]),
+    'lhvi_gibbs_run': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gibbs_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

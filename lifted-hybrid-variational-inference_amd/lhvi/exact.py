@@ -38,8 +38,12 @@ class ExactModel:
     def __init__(self, dstates, Nc):
         self.Nd, self.Nc = len(dstates), int(Nc)
         self.dstates = np.asarray(dstates, dtype=np.int32).reshape(-1)
-        self.M = int(np.prod(self.dstates, dtype=object)) if self.Nd else 1
-        self.dstride = np.array([int(np.prod(self.dstates[i + 1:], dtype=object)) for i in range(self.Nd)], dtype=np.int64)
+        M = int(np.prod(self.dstates, dtype=object)) if self.Nd else 1
+        if M < 2 ** 63:
+            self.M = M
+            self.dstride = np.array([int(np.prod(self.dstates[i + 1:], dtype=object)) for i in range(self.Nd)], dtype=np.int64)
+        else:       # too many configurations to number: only the sampler (lhvi/gibbs.py), which reads neither field, takes it
+            self.M, self.dstride = 0, np.zeros(self.Nd, dtype=np.int64)
         self.n_quad = self.n_tab = 0
 
     def struct(self, ptr_of, keep=None):
@@ -271,6 +275,8 @@ class _DeviceRun:
 
     def __init__(self, model, keep_cov, lanes=None, chunk=CHUNK):
         torch = _abi.require_gpu()
+        if model.M == 0:
+            raise ValueError('the %d discrete variables have more joint states than can be enumerated' % model.Nd)
         if model.Nc > MAX_NC:
             raise ValueError('Nc = %d continuous variables exceed LHVI_EXACT_MAX_NC = %d' % (model.Nc, MAX_NC))
         need = output_bytes(model.M, model.Nc, keep_cov)

@@ -1,0 +1,430 @@
+"""Block Gibbs sampling in a hybrid Gaussian MRF (API of ``gibbs/hybrid_gaussian_mrf.py``, the sampling half, and of
+``gibbs/disc_mrf.py``) as many independent chains on the device (``csrc/gibbs.hip``).
+
+``block_gibbs_sample``, ``HybridGaussianSampler`` and ``gibbs_sample`` keep the reference's names, argument order and return
+shapes, with one more keyword ``chains``; ``GibbsHybridGaussian`` is the solver-shaped form (evidence, automatic conversion of
+potentials, marginals with standard errors over chains, R-hat).  The model is the flat model of the exact baseline
+(``exact.flatten_factors``) plus the variable-to-factor lists of the discrete sweep (``GibbsModel``).  There is no CPU path:
+without a GPU the calls raise ``LhviError`` (``chain_host`` runs one chain with injected draws through the device's code for
+the tests).
+
+Deliberate differences (docs/kernels_gibbs.md): x_c is drawn as ``mu + L^-T z`` from the Cholesky factor of J instead of
+``np.random.multivariate_normal`` (SVD of the covariance); the random numbers are a counter-based Philox stream instead of
+``drand48`` / NumPy's generator; ``HybridGaussianSampler.map`` of a discrete variable works.
+"""
+from __future__ import annotations
+
+import ctypes as C
+import os
+import types
+
+import numpy as np
+
+from . import _abi
+from .exact import MAX_NC, ExactHybridGaussian, ExactModel, _Factor, flatten_factors
+from .potentials import LogTable
+
+LDS_LIMIT = 64 * 1024
+ITS_PER_LAUNCH = 256            # outer iterations of one launch
+
+
+# ---- host: flat model -> sampler model ----------------------------------------------------------------------------------------------
+class GibbsModel:
+    """the lists of ``lhvi_gibbs_t`` (include/lhvi.h) beyond its ``lhvi_exact_t``, in host arrays, derived from the descriptors
+    of an ``ExactModel``"""
+
+    FIELDS = ('dstate_off', 'vt_ptr', 'vt_fac', 'vh_ptr', 'vh_fac', 'hyb_quad', 'hyb_off')
+
+    def __init__(self, ex):
+        self.ex = ex
+        Nd = ex.Nd
+        vt, vh = [[] for _ in range(Nd)], [[] for _ in range(Nd)]
+        hyb_quad, hyb_off = [], [0]
+        for f in range(ex.n_quad):              # a LogHybridQuadratic without a discrete axis counts as continuous (:186-190)
+            rec = ex.quad_desc[ex.quad_ptr[f]:ex.quad_ptr[f + 1]]
+            nd = int(rec[0])
+            if nd == 0:
+                continue
+            scope = [int(v) for v in rec[3:3 + 2 * nd:2]]
+            for v in scope:
+                vh[v].append(len(hyb_quad))
+            hyb_quad.append(f)
+            hyb_off.append(hyb_off[-1] + int(np.prod(ex.dstates[scope], dtype=np.int64)))
+        for f in range(ex.n_tab):
+            rec = ex.tab_desc[ex.tab_ptr[f]:ex.tab_ptr[f + 1]]
+            for v in rec[2:2 + 2 * int(rec[0]):2]:
+                vt[int(v)].append(f)
+        if hyb_off[-1] >= 2 ** 31:
+            raise ValueError('the reduced tables of the hybrid factors exceed 32-bit offsets')
+        i32 = lambda a: np.asarray(a, dtype=np.int32).reshape(-1)                       # noqa: E731
+        self.dstate_off = i32(np.concatenate([[0], np.cumsum(ex.dstates)]))
+        self.vt_ptr = i32(np.concatenate([[0], np.cumsum([len(l) for l in vt])]))
+        self.vt_fac = i32([f for l in vt for f in l])
+        self.vh_ptr = i32(np.concatenate([[0], np.cumsum([len(l) for l in vh])]))
+        self.vh_fac = i32([h for l in vh for h in l])
+        self.hyb_quad, self.hyb_off = i32(hyb_quad), i32(hyb_off)
+        self.n_hyb, self.table_doubles = len(hyb_quad), int(hyb_off[-1])
+        self.max_states = int(ex.dstates.max()) if Nd else 1
+        self.n_states = int(ex.dstates.sum())
+
+    def struct(self, ptr_of, disc_block_its, num_burnin, num_samples, seed, table_scratch=None):
+        s = _abi.GibbsStruct()
+        s.ex = self.ex.struct(ptr_of)
+        for name in self.FIELDS:
+            setattr(s, name, ptr_of(name))
+        s.n_hyb, s.table_doubles, s.max_states = self.n_hyb, self.table_doubles, self.max_states
+        s.table_scratch = table_scratch
+        s.disc_block_its, s.num_burnin, s.num_samples = int(disc_block_its), int(num_burnin), int(num_samples)
+        s.seed = int(seed) & (2 ** 64 - 1)
+        return s
+
+    def arrays(self):
+        out = {n: getattr(self.ex, n) for n in ExactModel.FIELDS}
+        out.update({n: getattr(self, n) for n in self.FIELDS})
+        return out
+
+
+def _block_its(Nd, disc_block_its):
+    """one sweep samples p(x_d | x_c) exactly when there is one discrete variable (:167-168)"""
+    if disc_block_its < 0:
+        raise ValueError('disc_block_its must not be negative')
+    return 1 if Nd == 1 else int(disc_block_its)
+
+
+def _not_pd_message(state):
+    return 'the precision matrix J = -2A is not positive definite at the discrete state %r' % (tuple(int(s) for s in state),)
+
+
+def chain_host(gm, x_d, z, u, disc_block_its, num_burnin, num_samples, it_begin=0, it_end=None):
+    """one chain on the CPU through the device's code (``lhvi_gibbs_chain_host``) with injected draws z [iters, Nc] and
+    u [iters, its, Nd].  Returns a namespace: disc [num_samples, Nd], cont [num_samples, Nc], counts, sum1, sum2, x_d."""
+    ex = gm.ex
+    Nd, Nc = ex.Nd, ex.Nc
+    its = _block_its(Nd, disc_block_its)
+    it_end = num_burnin + num_samples if it_end is None else it_end
+    z = np.ascontiguousarray(z, dtype=np.float64).reshape(len(z), Nc)
+    u = np.ascontiguousarray(u, dtype=np.float64).reshape(len(u), its, Nd)
+    if (Nc and z.shape[0] < it_end) or (Nd and its and u.shape[0] < it_end):
+        raise ValueError('fewer injected draws than iterations')
+    arrs = {n: np.ascontiguousarray(a) for n, a in gm.arrays().items()}
+    s = gm.struct(lambda n: C.c_void_p(arrs[n].ctypes.data if arrs[n].size else 0), its, num_burnin, num_samples, 0)
+    r = types.SimpleNamespace(
+        disc=np.zeros((num_samples, Nd), dtype=np.int32), cont=np.zeros((num_samples, Nc)),
+        counts=np.zeros(gm.n_states, dtype=np.int32), sum1=np.zeros(Nc), sum2=np.zeros(Nc * (Nc + 1) // 2),
+        x_d=np.array(x_d, dtype=np.int32).reshape(Nd))
+    if Nd and (r.x_d.min() < 0 or (r.x_d >= ex.dstates).any()):
+        raise ValueError('x_d holds a state outside its variable\'s range')
+    p = lambda a: a.ctypes.data if a.size else None                                     # noqa: E731
+    rc = _abi.lib().lhvi_gibbs_chain_host(s, int(it_begin), int(it_end), p(r.x_d), p(z), p(u), p(r.disc), p(r.cont), p(r.counts),
+                                          p(r.sum1), p(r.sum2))
+    if rc == _abi.E_NOT_PD:
+        raise ValueError(_not_pd_message(r.x_d))
+    _abi.check(rc)
+    return r
+
+
+# ---- device ------------------------------------------------------------------------------------------------------------------
+def default_lanes(Nc):
+    """lanes per chain: the smallest power of two >= Nc / 2, at least 4 (docs/kernels_gibbs.md, "Lanes")"""
+    lanes = 4
+    while 2 * lanes < min(Nc, 64):
+        lanes *= 2
+    return lanes
+
+
+def output_bytes(gm, chains, num_samples, keep_samples):
+    """device bytes of the outputs of a run: the state, the accumulators (, the samples)"""
+    Nd, Nc = gm.ex.Nd, gm.ex.Nc
+    n = 4 * chains * (Nd + gm.n_states) + 8 * chains * (Nc + Nc * (Nc + 1) // 2)
+    return n + (chains * num_samples * (4 * Nd + 8 * Nc) if keep_samples else 0)
+
+
+class _Chains:
+    """`chains` chains on the device.  After ``run()``: x_d [chains, Nd], counts [chains, sum dstates], sum1 [chains, Nc],
+    sum2 [chains, Nc (Nc + 1) / 2] and, with keep_samples, disc [chains, num_samples, Nd] / cont [chains, num_samples, Nc]
+    as device tensors.  z / u: injected draws (host arrays [iters, chains, Nc] / [iters, chains, its, Nd]) for the tests;
+    tables: 'lds' / 'global' forces where the reduced tables live (default: LDS when the workspace fits)."""
+
+    def __init__(self, gm, chains, num_burnin, num_samples, disc_block_its, seed, keep_samples=False, lanes=None, init_x_d=None,
+                 z=None, u=None, tables=None):
+        ex = gm.ex
+        Nd, Nc = ex.Nd, ex.Nc
+        chains, num_burnin, num_samples = int(chains), int(num_burnin), int(num_samples)
+        if chains < 1 or num_burnin < 0 or num_samples < 0:
+            raise ValueError('chains >= 1, num_burnin >= 0 and num_samples >= 0 are required')
+        if Nc > MAX_NC:
+            raise ValueError('Nc = %d continuous variables exceed LHVI_EXACT_MAX_NC = %d' % (Nc, MAX_NC))
+        l = _abi.lib()
+        its = _block_its(Nd, disc_block_its)
+        lds_of = lambda lanes, in_lds: int(l.lhvi_gibbs_lds_bytes(                      # noqa: E731
+            Nc, Nd, gm.max_states + (gm.table_doubles if in_lds else 0), lanes))
+        if lanes is None:
+            lanes = default_lanes(Nc)
+            while lanes < 64 and lds_of(lanes, tables == 'lds') > LDS_LIMIT:
+                lanes *= 2
+        lanes = int(lanes)
+        if lanes < 1 or lanes > 64 or lanes & (lanes - 1):
+            raise ValueError('lanes must be a power of two up to 64')
+        in_lds = lds_of(lanes, True) <= LDS_LIMIT if tables is None else tables == 'lds'
+        if lds_of(lanes, in_lds) > LDS_LIMIT:
+            raise ValueError('a workgroup of %d chains needs %d bytes of LDS, more than %d' % (64 // lanes, lds_of(lanes, in_lds),
+                                                                                            LDS_LIMIT))
+        torch = _abi.require_gpu()
+        scratch_rows = 0 if in_lds else (chains + 63) // 64 * 64
+        need = output_bytes(gm, chains, num_samples, keep_samples) + 8 * scratch_rows * gm.table_doubles
+        free = int(torch.cuda.mem_get_info()[0])
+        if need > free:
+            raise MemoryError('%d chains of %d kept samples (Nd = %d, Nc = %d) need %d bytes of device memory, %d are free'
+                              % (chains, num_samples, Nd, Nc, need, free))
+        self.gm, self.chains, self.lanes, self.in_lds = gm, chains, lanes, in_lds
+        self.num_burnin, self.num_samples, self.its = num_burnin, num_samples, its
+        self.t = t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype)) for n, a in gm.arrays().items()})
+        dev = t['dstates'].device
+        self.scratch = None if in_lds else torch.empty(scratch_rows, max(gm.table_doubles, 1), dtype=torch.float64, device=dev)
+        self.s = gm.struct(lambda n: _abi.ptr(t[n]), its, num_burnin, num_samples, seed, _abi.ptr(self.scratch))
+        f64, i32 = torch.float64, torch.int32
+        self.x_d = torch.zeros(chains, Nd, dtype=i32, device=dev)
+        if init_x_d is not None:
+            init = np.asarray(init_x_d, dtype=np.int64)
+            init = np.broadcast_to(init.reshape(init.size // max(Nd, 1) if Nd else 1, Nd), (chains, Nd))
+            if Nd and (init.min() < 0 or (init >= ex.dstates[None, :]).any()):
+                raise ValueError('init_x_d holds a state outside its variable\'s range')
+            self.x_d = _abi.to_dev(np.ascontiguousarray(init, dtype=np.int32))
+        else:
+            _abi.check(l.lhvi_gibbs_init(self.s, chains, _abi.ptr(self.x_d) if Nd else None, _abi.stream_ptr()))
+        self.counts = torch.zeros(chains, gm.n_states, dtype=i32, device=dev)
+        self.sum1 = torch.zeros(chains, Nc, dtype=f64, device=dev)
+        self.sum2 = torch.zeros(chains, Nc * (Nc + 1) // 2, dtype=f64, device=dev)
+        self.disc = torch.zeros(chains, num_samples, Nd, dtype=i32, device=dev) if keep_samples else None
+        self.cont = torch.zeros(chains, num_samples, Nc, dtype=f64, device=dev) if keep_samples else None
+        iters = num_burnin + num_samples
+        self.z = self.u = None
+        if z is not None or u is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64).reshape(len(z), chains, Nc)
+            u = np.ascontiguousarray(u, dtype=np.float64).reshape(len(u), chains, its, Nd)
+            if (Nc and z.shape[0] < iters) or (Nd and its and u.shape[0] < iters):
+                raise ValueError('fewer injected draws than iterations')
+            self.z = _abi.to_dev(z) if z.size else None
+            self.u = _abi.to_dev(u) if u.size else None
+        self.bad = torch.full((1,), -1, dtype=torch.int64, device=dev)          # UINT64_MAX
+        self.done = 0
+
+    def advance(self, it_end):
+        """iterations [done, it_end) in one launch"""
+        p = lambda a: _abi.ptr(a) if a is not None and a.numel() else None              # noqa: E731
+        _abi.check(_abi.lib().lhvi_gibbs_run(self.s, self.chains, self.done, int(it_end), self.lanes, p(self.x_d), p(self.z),
+                                             p(self.u), p(self.disc), p(self.cont), p(self.counts), p(self.sum1), p(self.sum2),
+                                             _abi.ptr(self.bad), _abi.stream_ptr()))
+        self.done = int(it_end)
+
+    def run(self, its_per_launch=None):
+        step = ITS_PER_LAUNCH if its_per_launch is None else int(its_per_launch)
+        if step < 1:
+            raise ValueError('its_per_launch must be positive')
+        iters = self.num_burnin + self.num_samples
+        while self.done < iters:
+            self.advance(min(iters, self.done + step))
+        self.check()
+        return self
+
+    def check(self):
+        first = int(self.bad.item())
+        if first != -1:
+            chain = (first & (2 ** 64 - 1)) >> 32
+            raise ValueError(_not_pd_message(self.x_d[chain].cpu().numpy()) + ' (chain %d, iteration %d)'
+                             % (chain, first & 0xffffffff))
+
+
+def _seed(seed):
+    return int.from_bytes(os.urandom(8), 'little') if seed is None else int(seed)
+
+
+def _sample(gm, num_burnin, num_samples, init_x_d, disc_block_its, seed, chains, lanes=None):
+    """(disc [chains * num_samples, Nd] int64, cont [chains * num_samples, Nc], run): the kept samples, chain-major"""
+    run = _Chains(gm, chains, num_burnin, num_samples, disc_block_its, _seed(seed), keep_samples=True, lanes=lanes,
+                  init_x_d=init_x_d).run()
+    n = run.chains * run.num_samples
+    return run.disc.cpu().numpy().reshape(n, gm.ex.Nd).astype(np.int64), run.cont.cpu().numpy().reshape(n, gm.ex.Nc), run
+
+
+# ---- the reference's functions -----------------------------------------------------------------------------------------------
+def block_gibbs_sample(factors, Vd, Vc, num_burnin, num_samples, init_x_d=None, disc_block_its=100, seed=None, chains=1):
+    """``hybrid_gaussian_mrf.block_gibbs_sample`` (:145-265): (disc_samples [num_samples, Nd] int, cont_samples
+    [num_samples, Nc]).  Reads ``factor.log_potential_fun`` and ``factor.disc_nb_idx / cont_nb_idx`` like ``convert_to_bn``.
+    chains > 1: that many independent chains, their kept samples concatenated chain-major ([chains * num_samples, ...])."""
+    gm = GibbsModel(flatten_factors(factors, [rv.dstates for rv in Vd], len(Vc)))
+    disc, cont, _ = _sample(gm, num_burnin, num_samples, init_x_d, disc_block_its, seed, chains)
+    return disc, cont
+
+
+def get_disc_marg_table_from_samples(samples, dstates):
+    """``sampling_utils.get_disc_marg_table_from_samples``: the joint relative frequencies [v1..vN] of samples [S, N]"""
+    samples = np.asarray(samples)
+    counts = np.zeros(list(dstates), dtype=np.int64)
+    np.add.at(counts, tuple(samples[:, n] for n in range(samples.shape[1])), 1)
+    return counts / samples.shape[0]
+
+
+def fit_scalar_gm_from_samples(samples, K):
+    """``sampling_utils.fit_scalar_gm_from_samples``: (weights, means, variances) of a K-component mixture fitted by
+    scikit-learn"""
+    from sklearn import mixture
+    clf = mixture.GaussianMixture(n_components=K, covariance_type='diag')
+    clf.fit(np.asarray(samples, dtype=np.float64).reshape(-1, 1))
+    return clf.weights_, np.ravel(clf.means_), np.ravel(clf.covariances_)
+
+
+class HybridGaussianSampler:
+    """``hybrid_gaussian_mrf.HybridGaussianSampler`` (:268-302)"""
+
+    def __init__(self, factors, Vd, Vc, Vd_idx, Vc_idx):
+        self.factors, self.Vd, self.Vc, self.Vd_idx, self.Vc_idx = factors, Vd, Vc, Vd_idx, Vc_idx
+        self.dstates = [rv.dstates for rv in Vd]
+
+    def block_gibbs_sample(self, num_burnin, num_samples, init_x_d=None, disc_block_its=100, seed=None, chains=1):
+        self.disc_samples, self.cont_samples = block_gibbs_sample(self.factors, self.Vd, self.Vc, num_burnin, num_samples,
+                                                                  init_x_d, disc_block_its, seed, chains=chains)
+        self.sampled_disc_marginal_table = get_disc_marg_table_from_samples(self.disc_samples, self.dstates)
+
+    def map(self, rv, num_gm_components_for_crv=1):
+        """discrete: the argmax of the variable's sampled marginal (the reference's line :296 passes ``Vd_idx`` where an index
+        belongs and cannot run).  Continuous: the mode of a K-component mixture fitted to the samples; K = 1 is the sample
+        mean clipped to the domain."""
+        from .exact import get_drv_marg_map, get_rv_marg_map_from_bn_params
+        if rv in self.Vd_idx:
+            return get_drv_marg_map(self.sampled_disc_marginal_table, self.Vd_idx[rv])
+        x = self.cont_samples[:, self.Vc_idx[rv]]
+        if num_gm_components_for_crv == 1:
+            return float(min(max(x.mean(), rv.values[0]), rv.values[1]))
+        w, mu, var = fit_scalar_gm_from_samples(x, num_gm_components_for_crv)
+        return get_rv_marg_map_from_bn_params(w, mu[:, None], var[:, None, None], {}, {rv: 0}, rv)
+
+
+def gibbs_sample(lpot_tables, scopes, nbr_factor_ids, dstates, x, num_burnin, num_samples, seed=None, chains=1):
+    """``disc_mrf.gibbs_sample``: samples [num_samples, N] of a discrete MRF of log tables, one sweep per sample, from the
+    state x (which ends as the last state when chains = 1, like the reference's).  nbr_factor_ids is checked against the
+    scopes; the kernel adds a variable's tables in factor order."""
+    N = len(dstates)
+    for n in range(N):
+        if sorted(nbr_factor_ids[n]) != [j for j, sc in enumerate(scopes) if n in sc]:
+            raise ValueError('nbr_factor_ids[%d] does not list the factors whose scope holds variable %d' % (n, n))
+    factors = [_Factor('table %d' % j, LogTable(np.asarray(t, dtype=np.float64)), tuple(int(i) for i in sc), ())
+               for j, (t, sc) in enumerate(zip(lpot_tables, scopes))]
+    gm = GibbsModel(flatten_factors(factors, list(dstates), 0))
+    disc, _, run = _sample(gm, num_burnin, num_samples, np.asarray(x), 1, seed, chains)
+    if chains == 1 and isinstance(x, np.ndarray):
+        x[:] = run.x_d[0].cpu().numpy()
+    return disc
+
+
+# ---- the solver-shaped class ---------------------------------------------------------------------------------------------------
+class GibbsHybridGaussian:
+    """Sampled marginals of a hybrid Gaussian MRF from many independent block Gibbs chains.  ``GibbsHybridGaussian(g)`` or
+    ``GibbsHybridGaussian(factors=, Vd=, Vc=)``; variables with ``rv.value`` set are evidence, potentials are converted as in
+    ``ExactHybridGaussian``.  After ``run()``: ``disc_marginals()``, ``moments()``, ``rhat()``, ``map`` / ``map_all`` /
+    ``belief``, and with ``keep_samples`` ``disc_samples`` [chains, num_samples, Nd] / ``cont_samples``."""
+
+    def __init__(self, g=None, factors=None, Vd=None, Vc=None):
+        if g is None and (factors is None or Vd is None or Vc is None):
+            raise ValueError('GibbsHybridGaussian needs a graph, or factors=, Vd= and Vc=')
+        ex = ExactHybridGaussian(g=g, factors=factors, Vd=Vd, Vc=Vc)           # the flattening, evidence included
+        self.rvs, self.Vd, self.Vc, self.Vd_idx, self.Vc_idx = ex.rvs, ex.Vd, ex.Vc, ex.Vd_idx, ex.Vc_idx
+        self.dstates, self.factors = ex.dstates, ex.factors
+        self.model = GibbsModel(ex.model)
+        self._run = None
+
+    def run(self, chains=1024, num_burnin=100, num_samples=100, disc_block_its=100, seed=0, keep_samples=False, lanes=None,
+            its_per_launch=None, init_x_d=None):
+        if num_samples < 1:
+            raise ValueError('num_samples must be positive')
+        self._run = r = _Chains(self.model, chains, num_burnin, num_samples, disc_block_its, _seed(seed), keep_samples, lanes,
+                                init_x_d=init_x_d).run(its_per_launch)
+        self.chains, self.num_samples = r.chains, r.num_samples
+        self.counts = r.counts.cpu().numpy()
+        self.sum1, self.sum2 = r.sum1.cpu().numpy(), r.sum2.cpu().numpy()
+        self.disc_samples = r.disc.cpu().numpy() if keep_samples else None
+        self.cont_samples = r.cont.cpu().numpy() if keep_samples else None
+        return self
+
+    def _need_run(self):
+        if self._run is None:
+            raise RuntimeError('call run() first')
+        return self._run
+
+    def _stderr(self, per_chain):
+        if self.chains < 2:
+            return np.full(per_chain.shape[1:], np.nan)
+        return per_chain.std(axis=0, ddof=1) / np.sqrt(self.chains)
+
+    def disc_marginals(self):
+        """per discrete variable (marginal [states], standard error [states]): the grand mean of the chains' relative
+        frequencies and the standard error of that mean over chains"""
+        self._need_run()
+        freq = self.counts / float(self.num_samples)
+        mean, se = freq.mean(axis=0), self._stderr(freq)
+        off = self.model.dstate_off
+        return [(mean[off[i]:off[i + 1]], se[off[i]:off[i + 1]]) for i in range(len(self.Vd))]
+
+    def moments(self):
+        """namespace: mean [Nc] = E[x_c], second [Nc, Nc] = E[x_c x_c^T], cov = second - mean mean^T, and the standard errors
+        over chains mean_se, second_se"""
+        self._need_run()
+        Nc = len(self.Vc)
+        i, j = np.tril_indices(Nc)
+        m1, m2 = self.sum1 / float(self.num_samples), self.sum2 / float(self.num_samples)
+
+        def full(v):
+            out = np.zeros((Nc, Nc))
+            out[i, j] = out[j, i] = v
+            return out
+        mean, second = m1.mean(axis=0), full(m2.mean(axis=0))
+        return types.SimpleNamespace(mean=mean, second=second, cov=second - np.outer(mean, mean), mean_se=self._stderr(m1),
+                                     second_se=full(self._stderr(m2)))
+
+    def rhat(self):
+        """Gelman-Rubin potential scale reduction from the per-chain accumulators: namespace disc (list of [states] arrays, one
+        per discrete variable: the state's indicator), cont [Nc], max (NaN entries, a state no chain left or entered, skipped)"""
+        self._need_run()
+        S, Nc = float(self.num_samples), len(self.Vc)
+        if self.chains < 2 or S < 2:
+            raise ValueError('rhat needs at least two chains and two kept samples')
+
+        def psr(means, within):
+            W = within.mean(axis=0)
+            B_over_n = means.var(axis=0, ddof=1)
+            with np.errstate(divide='ignore', invalid='ignore'):
+                return np.sqrt(((S - 1) / S * W + B_over_n) / W)
+        p = self.counts / S
+        rd = psr(p, p * (1 - p) * S / (S - 1))
+        diag = np.arange(Nc) * (np.arange(Nc) + 1) // 2 + np.arange(Nc)
+        m1 = self.sum1 / S
+        rc = psr(m1, (self.sum2[:, diag] / S - m1 * m1) * S / (S - 1))
+        off = self.model.dstate_off
+        both = np.concatenate([rd, rc])
+        return types.SimpleNamespace(disc=[rd[off[i]:off[i + 1]] for i in range(len(self.Vd))], cont=rc,
+                                     max=float(np.nanmax(both)) if both.size and not np.isnan(both).all() else float('nan'))
+
+    def map(self, rv):
+        """observed: its value; discrete: the state of largest sampled marginal; continuous: the sample mean clipped to the
+        domain (the one-component fit of ``HybridGaussianSampler.map``)"""
+        if rv.value is not None:
+            return rv.value
+        self._need_run()
+        if rv in self.Vd_idx:
+            return rv.domain.values[int(np.argmax(self.disc_marginals()[self.Vd_idx[rv]][0]))]
+        mean = float(self.moments().mean[self.Vc_idx[rv]])
+        return float(min(max(mean, rv.domain.values[0]), rv.domain.values[1]))
+
+    def map_all(self):
+        """``map`` of every variable of ``self.rvs`` as an array"""
+        return np.array([float(self.map(rv)) for rv in self.rvs])
+
+    def belief(self, x, rv):
+        """sampled marginal probability of the state x of a discrete variable"""
+        if rv.value is not None:
+            return 1 if x == rv.value else 0
+        self._need_run()
+        if rv not in self.Vd_idx:
+            raise NotImplementedError('belief is the sampled marginal of a discrete variable; see moments() for x_c')
+        vals = list(rv.domain.values)
+        return float(self.disc_marginals()[self.Vd_idx[rv]][0][vals.index(x)]) if x in vals else 0.0
