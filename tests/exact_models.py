@@ -119,8 +119,123 @@ def rand_model(ns, Nd, Nc, seed):
     return _pack(Vd + Vc, factors)
 
 
+# ---- shape models: explicit states, Nc and scopes (the CPU / GPU tests of the shapes the fixtures lack) ---------------------------
+CDOM = (-10, 10)
+SHAPES = ('wide_states', 'deep_scope', 'nc1', 'nc7', 'nc33', 'nc63', 'nc64')
+# name: (seed, dstates, Nc, hybrid scopes (discrete, continuous), table scopes, quadratic scopes or 'dense', tables sharing the
+# log potential of an earlier table {later: earlier})
+SHAPE_SPECS = {
+    # d > lanes at 4 and 8 lanes: a unary table on every variable, one 9 x 5 table, one hybrid factor on the 9-state variable
+    'wide_states': (101, (9, 5, 2), 3, [((0,), (1,))], [(0,), (1,), (2,), (0, 1)], [(0,), (1,), (2,), (0, 1), (1, 2)], {}),
+    # three strides in scope order (2, 0, 1) with three continuous arguments (12 local states), a table of arity 3 over
+    # (3, 1, 0), variable 1 in the middle of a second hybrid scope, tables 2 and 3 sharing one log potential
+    'deep_scope': (102, (2, 3, 2, 2), 4, [((2, 0, 1), (3, 0, 2)), ((3, 1, 0), (1,))], [(3, 1, 0), (1,), (0, 2), (3, 2)],
+                   [(0,), (1,), (2,), (3,), (0, 1), (3, 2)], {3: 2}),
+    'nc1': (103, (2,), 1, [((0,), (0,))], [(0,)], 'dense', {}),
+    'nc7': (104, (3, 2), 7, [((0,), (6, 2)), ((1,), (3, 0))], [(1, 0)], 'dense', {}),
+    'nc33': (105, (2, 3), 33, [((0,), (32, 5)), ((1,), (16, 31))], [(1, 0)], 'dense', {}),
+    'nc63': (106, (2,), 63, [((0,), (62, 7))], [(0,)], 'dense', {}),
+    'nc64': (107, (2, 3), 64, [((0,), (63, 11)), ((1,), (32, 0))], [(1, 0)], 'dense', {}),
+    # the reduced table of one hybrid factor is 625 doubles a chain: more than a workgroup of 16 chains holds in LDS
+    'scratch_tables': (108, (5, 5, 5, 5), 2, [((3, 0, 2, 1), (1, 0)), ((1,), (0,))], [(0, 2), (3,)], [(0,), (1,), (0, 1)], {}),
+}
+
+
+def shape_model(ns, seed, dstates, Nc, hybrids, tables, quads, share=None, cdom=CDOM):
+    """seeded generator with a stream of its own (never rand_model's): discrete variable i has dstates[i] states; factors in
+    the order quadratics, hybrids, tables, every scope as given (positions in Vd / Vc, any order).  quads = 'dense': one
+    quadratic over all of Vc, -1/2 (B B^T + I) with B ~ N(0, 1 / Nc) (big_model of the GPU tests); else a list of scopes:
+    arity 1 gives A = -(0.5 + U), arity 2 gives -(w / 2)(a x - y)^2.  A hybrid block is -1/2 m m^T with m ~ 0.5 N(0, 1), so
+    every J is the base plus positive semi-definite terms.  share {j: i}: table j takes the log potential object of table i."""
+    rng = np.random.RandomState(seed)
+    Vd = [ns.RV(domain=ns.Domain(values=tuple(range(d)), continuous=False)) for d in dstates]
+    Vc = [ns.RV(domain=ns.Domain(values=tuple(cdom), continuous=True)) for _ in range(Nc)]
+    factors = []
+    if quads == 'dense':
+        B = rng.randn(Nc, Nc) / np.sqrt(Nc)
+        factors.append(ns.F(nb=tuple(Vc), log_potential_fun=ns.LogQuadratic(A=-0.5 * (B @ B.T + np.eye(Nc)), b=rng.randn(Nc), c=0.)))
+    else:
+        for sc in quads:
+            if len(sc) == 1:
+                lp = ns.LogQuadratic(A=-(0.5 + rng.rand(1, 1)), b=rng.randn(1), c=0.)
+            else:
+                w, a = rng.uniform(0.2, 1.0), rng.randn()
+                lp = ns.LogQuadratic(A=-(w / 2) * np.array([[a * a, -a], [-a, 1.]]), b=np.zeros(2), c=0.)
+            factors.append(ns.F(nb=tuple(Vc[i] for i in sc), log_potential_fun=lp))
+    for ds, cs in hybrids:
+        dims, nc = [dstates[i] for i in ds], len(cs)
+        A = np.empty(dims + [nc, nc])
+        for idx in np.ndindex(*dims):
+            m = 0.5 * rng.randn(nc, 1)
+            A[idx] = -0.5 * m @ m.T
+        lp = ns.LogHybridQuadratic(A=A, b=rng.randn(*(dims + [nc])), c=0.5 * rng.randn(*dims))
+        factors.append(ns.F(nb=tuple([Vd[i] for i in ds] + [Vc[i] for i in cs]), log_potential_fun=lp))
+    made = []
+    for j, sc in enumerate(tables):
+        lp = made[share[j]] if share and j in share else ns.LogTable(rng.randn(*[dstates[i] for i in sc]))
+        made.append(lp)
+        factors.append(ns.F(nb=tuple(Vd[i] for i in sc), log_potential_fun=lp))
+    return _pack(Vd + Vc, factors)
+
+
+def reduction_model(ns, dstates, seed=109, span=66., cdom=CDOM):
+    """Nc = 1, for the reductions and the mixtures at large M: a unary table on every discrete variable, its entries spread over
+    span / Nd (log p~ then spans about `span` over the configurations, centred on 0), and a hybrid factor (variable, x) on
+    every variable that moves J within [1, 1.25] and the mean by a few tenths"""
+    rng = np.random.RandomState(seed)
+    n = len(dstates)
+    Vd = [ns.RV(domain=ns.Domain(values=tuple(range(d)), continuous=False)) for d in dstates]
+    x = ns.RV(domain=ns.Domain(values=tuple(cdom), continuous=True))
+    factors = [ns.F(nb=(x,), log_potential_fun=ns.LogQuadratic(A=-0.5 * np.ones((1, 1)), b=rng.randn(1), c=0.))]
+    for rv, d in zip(Vd, dstates):
+        lp = ns.LogHybridQuadratic(A=-0.5 * (0.25 / n) * rng.rand(d, 1, 1), b=0.3 * rng.randn(d, 1), c=0.1 * rng.randn(d))
+        factors.append(ns.F(nb=(rv, x), log_potential_fun=lp))
+    for rv, d in zip(Vd, dstates):
+        t = rng.rand(d)
+        t = ((t - t.min()) / (t.max() - t.min()) - 0.5) * (span / n)
+        factors.append(ns.F(nb=(rv,), log_potential_fun=ns.LogTable(t)))
+    return _pack(Vd + [x], factors)
+
+
+def numpy_config(factors, dstates, Nc, config):
+    """convert_to_bn's loop body (:30-65) restated on this package's classes: (log p~, mu, Sig)"""
+    from lhvi.potentials import LogQuadratic, LogTable
+    A, b, c, t = np.zeros((Nc, Nc)), np.zeros(Nc), 0.0, 0.0
+    for f in factors:
+        lp = f.log_potential_fun
+        xd = tuple(config[i] for i in f.disc_nb_idx)
+        if isinstance(lp, LogTable):
+            t += lp(xd)
+            continue
+        A_, b_, c_ = (lp.A, lp.b, lp.c) if isinstance(lp, LogQuadratic) else lp.get_quadratic_params_given_x_d(xd)
+        sc = f.cont_nb_idx
+        for i in range(len(sc)):
+            for j in range(len(sc)):
+                A[sc[i], sc[j]] += A_[i, j]
+            b[sc[i]] += b_[i]
+        c += c_
+    Sig = np.linalg.inv(-2. * A)
+    mu = Sig @ b
+    return t + (Nc / 2 * np.log(2 * np.pi) + 0.5 * np.linalg.slogdet(Sig)[1] + 0.5 * mu @ b + c), mu, Sig
+
+
+def enumerate_numpy(model):
+    """numpy_config over every configuration of a model with its indices set: (logp [M], mu [M, Nc], Sig [M, Nc, Nc],
+    largest cond(J))"""
+    dstates, Nc = [rv.dstates for rv in model['Vd']], len(model['Vc'])
+    M = int(np.prod(dstates))
+    logp, mu, sig, cond = np.zeros(M), np.zeros((M, Nc)), np.zeros((M, Nc, Nc)), 0.0
+    for cfg in range(M):
+        logp[cfg], mu[cfg], sig[cfg] = numpy_config(model['factors'], dstates, Nc, np.unravel_index(cfg, dstates))
+        cond = max(cond, np.linalg.cond(sig[cfg]))
+    return logp, mu, sig, cond
+
+
 def build(name, ns=None, **kw):
     ns = ns or local_ns()
+    if name in SHAPE_SPECS:
+        seed, dstates, Nc, hybrids, tables, quads, share = SHAPE_SPECS[name]
+        return shape_model(ns, seed, list(dstates), Nc, hybrids, tables, quads, share, **kw)
     if name == 'ref_hybrid2':
         return ref_hybrid2(ns)
     if name == 'ref_mln0':

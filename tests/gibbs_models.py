@@ -6,7 +6,10 @@ LogHybridQuadratic.get_table_params_given_x_c, and the sweep of disc_mrf.gibbs_s
 disc_mrf_sampler.pyx (softmax as exp(v - (m + log(sum))), the first state with u <= cumulative sum).  It asserts that every
 injected uniform is at least MARGIN away from every cumulative probability it is compared with, so that a difference in the
 last bits of a probability cannot change a state; DRAW_SEED was checked on the CPU to satisfy that for every chain of every
-model."""
+model.
+
+``philox_normals`` / ``philox_uniforms`` / ``philox_init`` restate the device generator from the counter layout written down in
+docs/kernels_gibbs.md ("Random numbers"), independently of csrc/gibbs.hpp."""
 import numpy as np
 
 import exact_models as em
@@ -14,7 +17,8 @@ from lhvi import exact, gibbs
 from lhvi.graph import F, RV, Domain
 from lhvi.potentials import LogHybridQuadratic, LogQuadratic, LogTable
 
-DET_MODELS = ('ref_hybrid2', 'rand_3_2', 'rand_8_8', 'pure_disc', 'no_disc')
+DET_MODELS = ('ref_hybrid2', 'rand_3_2', 'rand_8_8', 'pure_disc', 'no_disc',
+              'wide_states', 'deep_scope', 'nc1', 'nc7', 'nc33', 'nc64')    # exact_models.SHAPE_SPECS: shapes the fixtures lack
 CHAINS, ITERS, ITS, BURNIN = 8, 6, 3, 2
 MARGIN = 1e-9
 DRAW_SEED = 2026
@@ -56,6 +60,10 @@ def build(name):
     """model dict with disc_nb_idx / cont_nb_idx set, plus dstates and the GibbsModel"""
     model = {'pure_disc': pure_disc, 'no_disc': no_disc, 'not_pd': not_pd}[name]() if name in ('pure_disc', 'no_disc', 'not_pd') \
         else em.build(name)
+    return finish(model)
+
+
+def finish(model):
     em.set_indices(model)
     model['dstates'] = [rv.dstates for rv in model['Vd']]
     model['gm'] = gibbs.GibbsModel(exact.flatten_factors(model['factors'], model['dstates'], len(model['Vc'])))
@@ -72,12 +80,8 @@ def draws(model, chains=CHAINS, iters=ITERS, its=ITS, seed=DRAW_SEED):
     return x0, rng.randn(iters, chains, Nc), rng.rand(iters, chains, its, Nd)
 
 
-def restate(model, x_d, z, u, num_burnin=0, margin=MARGIN):
-    """one chain: x_d [Nd], z [iters, Nc], u [iters, its, Nd] -> (disc [iters - num_burnin, Nd], cont [.., Nc], smallest
-    distance of a uniform from a cumulative probability)"""
-    factors, dstates, Nc = model['factors'], model['dstates'], len(model['Vc'])
-    Nd = len(dstates)
-    iters, its = u.shape[0], u.shape[1]
+def split_factors(factors):
+    """(continuous, discrete, strictly hybrid) factors, each in factor order"""
     cont_f, disc_f, hyb_f = [], [], []
     for f in factors:
         lp = f.log_potential_fun
@@ -87,6 +91,21 @@ def restate(model, x_d, z, u, num_burnin=0, margin=MARGIN):
             hyb_f.append(f)
         else:
             disc_f.append(f)
+    return cont_f, disc_f, hyb_f
+
+
+def reduced_tables(hyb_f, x_c):
+    """the log table of every strictly hybrid factor at x_c, shaped by the factor's own discrete scope"""
+    return [np.asarray(f.log_potential_fun.get_table_params_given_x_c(x_c[list(f.cont_nb_idx)])) for f in hyb_f]
+
+
+def restate(model, x_d, z, u, num_burnin=0, margin=MARGIN):
+    """one chain: x_d [Nd], z [iters, Nc], u [iters, its, Nd] -> (disc [iters - num_burnin, Nd], cont [.., Nc], smallest
+    distance of a uniform from a cumulative probability)"""
+    factors, dstates, Nc = model['factors'], model['dstates'], len(model['Vc'])
+    Nd = len(dstates)
+    iters, its = u.shape[0], u.shape[1]
+    cont_f, disc_f, hyb_f = split_factors(factors)
     tables = [np.asarray(f.log_potential_fun.table) for f in disc_f]
     scopes = [f.disc_nb_idx for f in disc_f] + [f.disc_nb_idx for f in hyb_f]
     nbrs = [[j for j, sc in enumerate(scopes) if n in sc] for n in range(Nd)]
@@ -111,7 +130,7 @@ def restate(model, x_d, z, u, num_burnin=0, margin=MARGIN):
             assert np.linalg.cond(J) <= 500
             L = np.linalg.cholesky(J)
             x_c = np.linalg.solve(J, b) + np.linalg.solve(L.T, z[it])
-        cond = tables + [np.asarray(f.log_potential_fun.get_table_params_given_x_c(x_c[list(f.cont_nb_idx)])) for f in hyb_f]
+        cond = tables + reduced_tables(hyb_f, x_c)
         for s in range(its):
             for n in range(Nd):
                 lprobs = np.zeros(dstates[n])
@@ -128,3 +147,51 @@ def restate(model, x_d, z, u, num_burnin=0, margin=MARGIN):
             cont.append(x_c.copy())
     assert closest >= margin, 'an injected uniform is %.3g from a cumulative probability' % closest
     return np.array(disc).reshape(len(disc), Nd), np.array(cont).reshape(len(cont), Nc), closest
+
+
+# ---- the device generator, restated from docs/kernels_gibbs.md ---------------------------------------------------------------------
+TAG_NORMAL, TAG_UNIFORM, TAG_INIT = (int.from_bytes(t, 'big') for t in (b'GBNZ', b'GBUF', b'GBXI'))
+
+
+def philox4(c0, c1, c2, c3, seed):
+    """Philox4x32-10 on uint64 arrays holding 32-bit counter words; key = (low, high) word of the seed"""
+    m32 = np.uint64(0xffffffff)
+    c = [np.asarray(a, dtype=np.uint64) & m32 for a in np.broadcast_arrays(c0, c1, c2, c3)]
+    k0, k1 = int(seed) & 0xffffffff, (int(seed) >> 32) & 0xffffffff
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c[0], np.uint64(0xCD9E8D57) * c[2]
+        c = [(p1 >> np.uint64(32)) ^ c[1] ^ np.uint64(k0), p1 & m32, (p0 >> np.uint64(32)) ^ c[3] ^ np.uint64(k1), p0 & m32]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xffffffff, (k1 + 0xBB67AE85) & 0xffffffff
+    return c
+
+
+def uniform2(a, b, draw, tag, seed):
+    """the two 53-bit uniforms in [0, 1) of counter (a, b, draw, tag): words (0, 1) and (2, 3), high word first"""
+    c = philox4(a, b, draw, tag, seed)
+    r0, r1 = (c[0] << np.uint64(32)) | c[1], (c[2] << np.uint64(32)) | c[3]
+    return (r0 >> np.uint64(11)).astype(np.float64) * 2.0 ** -53, (r1 >> np.uint64(11)).astype(np.float64) * 2.0 ** -53
+
+
+def philox_normals(seed, chains, iters, Nc):
+    """z [iters, chains, Nc]: counter (chain, iteration, r // 2, GBNZ); Box-Muller radius sqrt(-2 log(1 - u0)), angle 2 pi u1,
+    cosine for even r, sine for odd r"""
+    it, ch, r = np.meshgrid(np.arange(iters), np.arange(chains), np.arange(Nc), indexing='ij')
+    u0, u1 = uniform2(ch, it, r // 2, TAG_NORMAL, seed)
+    rad, ang = np.sqrt(-2.0 * np.log(1.0 - u0)), 6.283185307179586 * u1
+    return np.where(r % 2 == 1, rad * np.sin(ang), rad * np.cos(ang))
+
+
+def philox_uniforms(seed, chains, iters, its, Nd):
+    """u [iters, chains, its, Nd]: draw index (sweep * Nd + variable) // 2 with GBUF, the first uniform for an even index"""
+    it, ch, sw, n = np.meshgrid(np.arange(iters), np.arange(chains), np.arange(its), np.arange(Nd), indexing='ij')
+    idx = sw * Nd + n
+    u0, u1 = uniform2(ch, it, idx // 2, TAG_UNIFORM, seed)
+    return np.where(idx % 2 == 1, u1, u0)
+
+
+def philox_init(seed, chains, dstates):
+    """x_d [chains, Nd] of gibbs_init_kernel: counter (chain, variable, 0, GBXI), state floor(u0 d) capped at d - 1"""
+    ch, n = np.meshgrid(np.arange(chains), np.arange(len(dstates)), indexing='ij')
+    u0, _ = uniform2(ch, n, 0, TAG_INIT, seed)
+    d = np.asarray(dstates)[None, :]
+    return np.minimum((u0 * d).astype(np.int64), d - 1).astype(np.int32)

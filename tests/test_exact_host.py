@@ -3,7 +3,13 @@ per-configuration code run on the host (lhvi_exact_config_host) against the reco
 precision matrix that is not positive definite, the compat alias, and the failure without a GPU.
 
 Tolerances (docs/kernels_exact.md): log table, logZ, means, variances, covariances rtol 1e-10 against the reference (both
-sides are backward-stable solves of the same matrix: c n cond(J) u with n <= 32, cond <= 500 asserted at capture)."""
+sides are backward-stable solves of the same matrix: c n cond(J) u with n <= 64, cond <= 500 asserted at capture and by the
+twins of the shape models below: 64 * 500 * 1.1e-16 = 4e-12).
+
+The shape models (exact_models.SHAPE_SPECS, reduction_model) reach what the fixtures' models do not: more states than lanes,
+scopes of three arguments in any order, Nc = 1, odd Nc, Nc = 33 / 63 / 64.  Each is proven here first -- cond(J) <= 500 and the
+host code equal to the NumPy restatement on every configuration (M <= 4096) -- so that a failure on the device is a kernel
+finding."""
 import os
 import subprocess
 import sys
@@ -21,25 +27,7 @@ PKG = os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd')
 RTOL = 1e-10
 
 
-def numpy_config(factors, dstates, Nc, config):
-    """convert_to_bn's loop body (:30-65) restated on this package's classes: (log p~, mu, Sig)"""
-    A, b, c, t = np.zeros((Nc, Nc)), np.zeros(Nc), 0.0, 0.0
-    for f in factors:
-        lp = f.log_potential_fun
-        xd = tuple(config[i] for i in f.disc_nb_idx)
-        if isinstance(lp, LogTable):
-            t += lp(xd)
-            continue
-        A_, b_, c_ = (lp.A, lp.b, lp.c) if isinstance(lp, LogQuadratic) else lp.get_quadratic_params_given_x_d(xd)
-        sc = f.cont_nb_idx
-        for i in range(len(sc)):
-            for j in range(len(sc)):
-                A[sc[i], sc[j]] += A_[i, j]
-            b[sc[i]] += b_[i]
-        c += c_
-    Sig = np.linalg.inv(-2. * A)
-    mu = Sig @ b
-    return t + (Nc / 2 * np.log(2 * np.pi) + 0.5 * np.linalg.slogdet(Sig)[1] + 0.5 * mu @ b + c), mu, Sig
+numpy_config = em.numpy_config         # shared with the GPU suite
 
 
 def test_flatten_ref_hybrid2_descriptors():
@@ -252,3 +240,72 @@ def test_host_code_without_continuous_or_discrete_variables():
     # J = 2, b = 3: mu = 1.5, var = 0.5, log integral = 1/2 log(2 pi / 2) + b^2 / (2 J) + c
     assert abs(mu[0] - 1.5) <= 1e-15 and abs(var[0] - 0.5) <= 1e-15
     assert abs(lp - (0.5 * np.log(np.pi) + 2.25 + 0.5)) <= 1e-14
+
+
+# ---- the shape models: CPU twins of the GPU comparisons -------------------------------------------------------------------------------
+REDUCTION_DSTATES = {243: (3,) * 5, 256: (2,) * 8, 288: (2,) * 5 + (3,) * 2, 177147: (3,) * 11, 262144: (2,) * 18,
+                     531441: (3,) * 12, 131072: (2,) * 17}
+
+
+def assert_host_equals_numpy(model, m, cfgs):
+    """config_host against numpy_config at the module's tolerances; returns the largest cond(J) met"""
+    dstates, Nc = [rv.dstates for rv in model['Vd']], len(model['Vc'])
+    worst = 0.0
+    for cfg in cfgs:
+        want_lp, want_mu, want_sig = numpy_config(model['factors'], dstates, Nc, np.unravel_index(int(cfg), dstates))
+        worst = max(worst, np.linalg.cond(want_sig))
+        lp, mu, var, cov = exact.config_host(m, int(cfg), cov=True)
+        em.assert_log_close(lp, want_lp, RTOL, 'log p~ of configuration %d' % cfg)
+        np.testing.assert_allclose(mu, want_mu, rtol=RTOL, atol=1e-12)
+        np.testing.assert_allclose(cov, want_sig, rtol=RTOL, atol=1e-12)
+        np.testing.assert_array_equal(var, np.diagonal(cov))
+        np.testing.assert_array_equal(cov, cov.T)
+    assert worst <= 500, 'cond(J) = %.3g' % worst
+    return worst
+
+
+@pytest.mark.parametrize('name', em.SHAPES + ('scratch_tables',))
+def test_shape_model_host_equals_numpy_on_every_configuration(name):
+    model = em.build(name)
+    em.set_indices(model)
+    dstates = [rv.dstates for rv in model['Vd']]
+    assert tuple(dstates) == em.SHAPE_SPECS[name][1] and len(model['Vc']) == em.SHAPE_SPECS[name][2]
+    m = exact.flatten_factors(model['factors'], dstates, len(model['Vc']))
+    assert m.M <= 4096
+    worst = assert_host_equals_numpy(model, m, range(m.M))
+    print('%s: M = %d, max cond(J) = %.4g' % (name, m.M, worst))
+
+
+def test_deep_scope_descriptors_keep_the_scope_order():
+    """the strides of a descriptor follow the factor's own argument order, not the variables': scope (2, 0, 1) of dimensions
+    (2, 2, 3) has local strides (6, 3, 1); the shared table is stored once"""
+    model = em.build('deep_scope')
+    em.set_indices(model)
+    m = exact.flatten_factors(model['factors'], [2, 3, 2, 2], 4)
+    hyb = [f for f in range(m.n_quad) if m.quad_desc[m.quad_ptr[f]] == 3]
+    rec = m.quad_desc[m.quad_ptr[hyb[0]]:m.quad_ptr[hyb[0] + 1]]
+    assert list(rec[:2]) == [3, 3] and list(rec[3:9]) == [2, 6, 0, 3, 1, 1] and list(rec[9:]) == [3, 0, 2]
+    rec = m.quad_desc[m.quad_ptr[hyb[1]]:m.quad_ptr[hyb[1] + 1]]
+    assert list(rec[:2]) == [3, 1] and list(rec[3:9]) == [3, 6, 1, 2, 0, 1] and list(rec[9:]) == [1]
+    rec = m.tab_desc[m.tab_ptr[0]:m.tab_ptr[1]]
+    assert list(rec) == [3, 0, 3, 6, 1, 2, 0, 1]
+    assert m.n_tab == 4 and m.tab_par.size == 12 + 3 + 4
+    assert m.tab_desc[m.tab_ptr[2] + 1] == m.tab_desc[m.tab_ptr[3] + 1] == 15
+
+
+@pytest.mark.parametrize('M', sorted(REDUCTION_DSTATES))
+def test_reduction_model_host_equals_numpy(M):
+    """the Nc = 1 models of the reduction and mixture tests: every configuration up to M = 4096, else the two ends and 32
+    seeded ones"""
+    dstates = list(REDUCTION_DSTATES[M])
+    model = em.reduction_model(em.local_ns(), dstates)
+    em.set_indices(model)
+    m = exact.flatten_factors(model['factors'], dstates, 1)
+    assert m.M == M
+    cfgs = range(M) if M <= 4096 else sorted(set([0, M - 1] + list(np.random.RandomState(M % 1000).randint(M, size=32))))
+    assert_host_equals_numpy(model, m, cfgs)
+    # log p~ spans at least 60: every table at its largest against every table at its smallest entry
+    tabs = [f.log_potential_fun.table for f in model['factors'] if isinstance(f.log_potential_fun, LogTable)]
+    hi = int(np.ravel_multi_index([int(np.argmax(t)) for t in tabs], dstates))
+    lo = int(np.ravel_multi_index([int(np.argmin(t)) for t in tabs], dstates))
+    assert exact.config_host(m, hi)[0] - exact.config_host(m, lo)[0] >= 60

@@ -20,7 +20,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd')
 
 
-@pytest.fixture(scope='module', params=gmod.DET_MODELS)
+@pytest.fixture(scope='module', params=gmod.DET_MODELS + ('scratch_tables',))
 def case(request):
     model = gmod.build(request.param)
     x0, z, u = gmod.draws(model)
@@ -67,6 +67,7 @@ def test_host_chain_equals_numpy_restatement(case):
         np.testing.assert_allclose(r.cont, cont, rtol=1e-9, atol=1e-12)
         if Nd:
             np.testing.assert_array_equal(r.x_d, disc[-1])
+    print('smallest distance of a uniform from a cumulative probability: %.3g' % min(w[2] for w in want))
 
 
 def test_host_split_run_and_accumulators(case):
@@ -175,3 +176,42 @@ def test_sampled_table_and_map_of_the_sampler_class():
     np.testing.assert_array_equal(s.sampled_disc_marginal_table, want)
     assert s.map(model['Vd'][0]) == 2 and s.map(model['Vd'][1]) == 1
     assert s.map(model['Vc'][0]) == 2.5 and s.map(model['Vc'][1]) == 5.0
+
+
+def test_restated_conditional_tables_equal_the_formula_written_out():
+    """the yardstick's reduced tables at arity 3, independently of the potentials' helper: x^T A_k x + b_k . x + c_k for every
+    local state k of both hybrid factors of deep_scope, indexed in the factor's own argument order"""
+    model = gmod.build('deep_scope')
+    _, _, hyb_f = gmod.split_factors(model['factors'])
+    assert [f.disc_nb_idx for f in hyb_f] == [(2, 0, 1), (3, 1, 0)] and [f.cont_nb_idx for f in hyb_f] == [(3, 0, 2), (1,)]
+    x_c = np.array([0.7, -1.3, 2.1, -0.4])
+    got = gmod.reduced_tables(hyb_f, x_c)
+    for f, t in zip(hyb_f, got):
+        lp = f.log_potential_fun
+        dims = tuple(model['dstates'][i] for i in f.disc_nb_idx)
+        assert t.shape == dims
+        x = np.array([x_c[i] for i in f.cont_nb_idx])
+        for k in np.ndindex(*dims):
+            want = sum(lp.A[k][a, b] * x[a] * x[b] for a in range(len(x)) for b in range(len(x)))
+            want += sum(lp.b[k][a] * x[a] for a in range(len(x))) + lp.c[k]
+            assert abs(t[k] - want) <= 1e-13 * max(1.0, abs(want))
+
+
+def test_philox_restatement_is_a_generator():
+    """the NumPy restatement of the device generator (gibbs_models.philox_*), before the GPU suite compares the kernel with it:
+    the Philox4x32-10 known-answer vectors of Random123 (kat_vectors: zero and all-ones counter and key), uniforms in [0, 1),
+    normals and initial states with the moments of their distributions"""
+    m = 0xffffffff
+    assert [int(w) for w in gmod.philox4(0, 0, 0, 0, 0)] == [0x6627e8d5, 0xe169c58d, 0xbc57ac4c, 0x9b00dbd8]
+    assert [int(w) for w in gmod.philox4(m, m, m, m, (m << 32) | m)] == [0x408f276d, 0x41c83b0e, 0xa20bc7c6, 0x6d5451fd]
+    z = gmod.philox_normals(7, 64, 20, 5)
+    u = gmod.philox_uniforms(7, 64, 20, 3, 5)
+    assert z.shape == (20, 64, 5) and u.shape == (20, 64, 3, 5) and u.min() >= 0 and u.max() < 1
+    n = z.size
+    assert abs(z.mean()) <= 4.5 / np.sqrt(n) and abs(z.var() - 1) <= 4.5 * np.sqrt(2. / n)
+    assert abs(u.mean() - 0.5) <= 4.5 / np.sqrt(12. * u.size)
+    assert len(np.unique(z)) == z.size and len(np.unique(u)) == u.size
+    x = gmod.philox_init(7, 4096, [9, 5, 2])
+    for k, d in enumerate((9, 5, 2)):
+        freq = np.bincount(x[:, k], minlength=d) / 4096.
+        assert np.abs(freq - 1. / d).max() <= 4.5 * np.sqrt((1. / d) * (1 - 1. / d) / 4096)

@@ -21,23 +21,90 @@ SEED = 20261017
 
 
 # ---- injected draws ----------------------------------------------------------------------------------------------------------------
+def allowed_lanes(gm):
+    """every power-of-two lane count at which a workgroup's chains, reduced tables included, fit 64 KiB of LDS"""
+    from lhvi import _abi
+    Nc, Nd, disc = gm.ex.Nc, gm.ex.Nd, gm.max_states + gm.table_doubles
+    return [l for l in (1, 2, 4, 8, 16, 32, 64) if _abi.lib().lhvi_gibbs_lds_bytes(Nc, Nd, disc, l) <= gibbs.LDS_LIMIT]
+
+
+def injected_run(gm, lanes, x0, z, u):
+    r = gibbs._Chains(gm, gmod.CHAINS, gmod.BURNIN, gmod.ITERS - gmod.BURNIN, gmod.ITS, 0, keep_samples=True, lanes=lanes,
+                      init_x_d=x0, z=z, u=u).run()
+    return r.disc.cpu().numpy(), r.cont.cpu().numpy()
+
+
 @pytest.mark.parametrize('name', gmod.DET_MODELS)
 def test_kernel_equals_numpy_restatement(name):
+    """every allowed lane count: fewer lanes than states (wide_states has 9 states, deep_scope 12 local states of a hybrid
+    factor), idle lanes, lanes that do not divide Nc, the one lane count left at Nc = 64"""
     model = gmod.build(name)
     x0, z, u = gmod.draws(model)
-    kept = gmod.ITERS - gmod.BURNIN
-    got = {}
-    for lanes in (4, 64):
-        r = gibbs._Chains(model['gm'], gmod.CHAINS, gmod.BURNIN, kept, gmod.ITS, 0, keep_samples=True, lanes=lanes, init_x_d=x0,
-                          z=z, u=u).run()
-        got[lanes] = (r.disc.cpu().numpy(), r.cont.cpu().numpy())
-    np.testing.assert_array_equal(got[4][0], got[64][0])
-    np.testing.assert_array_equal(got[4][1], got[64][1])
+    lanes = allowed_lanes(model['gm'])
+    assert 64 in lanes and (name not in ('wide_states', 'deep_scope', 'nc1') or lanes == [1, 2, 4, 8, 16, 32, 64])
+    assert name != 'nc64' or lanes == [64]
+    got = {l: injected_run(model['gm'], l, x0, z, u) for l in lanes}
+    for l in lanes[1:]:
+        np.testing.assert_array_equal(got[lanes[0]][0], got[l][0], err_msg='lanes %d' % l)
+        np.testing.assert_array_equal(got[lanes[0]][1], got[l][1], err_msg='lanes %d' % l)
     for c in range(gmod.CHAINS):
         disc, cont, closest = gmod.restate(model, x0[c], z[:, c], u[:, c], gmod.BURNIN)
         assert closest >= gmod.MARGIN
-        np.testing.assert_array_equal(got[4][0][c], disc)
-        np.testing.assert_allclose(got[4][1][c], cont, rtol=1e-9, atol=1e-12)
+        np.testing.assert_array_equal(got[lanes[0]][0][c], disc)
+        np.testing.assert_allclose(got[lanes[0]][1][c], cont, rtol=1e-9, atol=1e-12)
+
+
+def test_reduced_tables_too_large_for_lds_go_to_global_scratch():
+    """scratch_tables: 625 + 5 doubles of reduced tables a chain.  At the default 4 lanes a workgroup holds 16 chains and the
+    tables do not fit: the default choice puts them in global scratch.  At 8 lanes they fit; the forced-LDS run there gives the
+    same samples and accumulators bit for bit, and both equal the restatement"""
+    model = gmod.build('scratch_tables')
+    gm = model['gm']
+    assert gm.table_doubles == 630 and gibbs.default_lanes(2) == 4
+    x0, z, u = gmod.draws(model)
+    kept = gmod.ITERS - gmod.BURNIN
+    a = gibbs._Chains(gm, gmod.CHAINS, gmod.BURNIN, kept, gmod.ITS, 0, keep_samples=True, init_x_d=x0, z=z, u=u)
+    assert a.lanes == 4 and not a.in_lds and a.scratch is not None and a.scratch.shape == (64, 630)
+    b = gibbs._Chains(gm, gmod.CHAINS, gmod.BURNIN, kept, gmod.ITS, 0, keep_samples=True, lanes=8, tables='lds', init_x_d=x0, z=z, u=u)
+    assert b.in_lds and b.scratch is None
+    with pytest.raises(ValueError, match='bytes of LDS'):
+        gibbs._Chains(gm, gmod.CHAINS, gmod.BURNIN, kept, gmod.ITS, 0, lanes=4, tables='lds')
+    a.run(), b.run()
+    for k in ('disc', 'cont', 'counts', 'sum1', 'sum2', 'x_d'):
+        np.testing.assert_array_equal(getattr(a, k).cpu().numpy(), getattr(b, k).cpu().numpy(), err_msg=k)
+    got_d, got_c = a.disc.cpu().numpy(), a.cont.cpu().numpy()
+    for c in range(gmod.CHAINS):
+        disc, cont, closest = gmod.restate(model, x0[c], z[:, c], u[:, c], gmod.BURNIN)
+        np.testing.assert_array_equal(got_d[c], disc)
+        np.testing.assert_allclose(got_c[c], cont, rtol=1e-9, atol=1e-12)
+    assert_same(chains_of(gm, lanes=None), chains_of(gm, lanes=8, tables='lds'))       # and with the device generator
+
+
+# ---- the device generator against its written specification -----------------------------------------------------------------------
+@pytest.mark.parametrize('name', ['rand_8_8', 'wide_states'])
+def test_device_generator_equals_its_specification(name):
+    """z, u and the initial state restated in NumPy from the counters of docs/kernels_gibbs.md (gibbs_models.philox_*), injected
+    into the kernel, against the kernel drawing for itself on the same seed: discrete samples equal, continuous within rtol 1e-9
+    (libm and the device's log / sin / cos differ by ulps; the restatement's margin check holds for the injected side, so an ulp
+    cannot move a state).  An off-by-one in a draw index, a swapped sine and cosine or a swapped pair of uniforms gives other
+    samples altogether."""
+    model = gmod.build(name)
+    gm, Nd, Nc = model['gm'], len(model['Vd']), len(model['Vc'])
+    chains, iters, its = 8, 6, 3                        # 3 sweeps of an odd Nd (wide_states): draw indices of both parities
+    z = gmod.philox_normals(SEED, chains, iters, Nc)
+    u = gmod.philox_uniforms(SEED, chains, iters, its, Nd)
+    x0 = gmod.philox_init(SEED, chains, model['dstates'])
+    dev = gibbs._Chains(gm, chains, 0, iters, its, SEED, keep_samples=True)
+    np.testing.assert_array_equal(dev.x_d.cpu().numpy(), x0)                     # gibbs_init_kernel, before any iteration
+    dev.run()
+    inj = gibbs._Chains(gm, chains, 0, iters, its, SEED + 1, keep_samples=True, init_x_d=x0, z=z, u=u).run()
+    np.testing.assert_array_equal(dev.disc.cpu().numpy(), inj.disc.cpu().numpy())
+    np.testing.assert_allclose(dev.cont.cpu().numpy(), inj.cont.cpu().numpy(), rtol=1e-9, atol=0)
+    for c in range(chains):
+        disc, cont, closest = gmod.restate(model, x0[c], z[:, c], u[:, c])
+        assert closest >= gmod.MARGIN
+        np.testing.assert_array_equal(inj.disc.cpu().numpy()[c], disc)
+        np.testing.assert_allclose(inj.cont.cpu().numpy()[c], cont, rtol=1e-9, atol=1e-12)
 
 
 # ---- bit equality, device generator ----------------------------------------------------------------------------------------------
@@ -176,6 +243,28 @@ def test_sampled_moments_match_the_reference_exact_results(name):
     for p, v in model['evidence'].items():          # an observed variable's map is its value
         assert s.map(model['rvs'][p]) == v
     assert s.map_all().shape == (len(model['rvs']),)
+
+
+def test_sampled_moments_of_wide_states_match_the_host_enumeration():
+    """a 9-state and a 5-state variable, which the recorded models lack: marginals, E[x_i] and E[x_i x_j] enumerated on the host
+    with numpy_config (M = 90), not with the device's exact solver; the settings and the bound of the test above
+    (docs/kernels_gibbs.md records what the host code gave on three seeds)"""
+    model = em.build('wide_states')
+    em.set_indices(model)
+    logp, mu, sig, _ = em.enumerate_numpy(model)
+    t = np.exp(logp - logp.max())
+    t /= t.sum()
+    joint = t.reshape(9, 5, 2)
+    marg = np.concatenate([joint.sum(axis=(1, 2)), joint.sum(axis=(0, 2)), joint.sum(axis=(0, 1))])
+    i, j = np.tril_indices(3)
+    want = np.concatenate([marg, t @ mu, t @ (sig[:, i, j] + mu[:, i] * mu[:, j])])
+    s = gibbs.GibbsHybridGaussian(factors=model['factors'], Vd=model['Vd'], Vc=model['Vc'])
+    s.run(chains=4096, num_burnin=50, num_samples=50, disc_block_its=10, seed=SEED)
+    got = np.concatenate([s.counts, s.sum1, s.sum2], axis=1) / 50.
+    assert got.shape == (4096, want.size) and want.size == 16 + 3 + 6
+    z = np.abs(got.mean(axis=0) - want) / (got.std(axis=0, ddof=1) / np.sqrt(4096))
+    print('wide_states: %d quantities, max z = %.2f' % (want.size, z.max()))
+    assert z.max() <= 4.5
 
 
 def test_forty_discrete_variables_mix_and_agree_between_seeds():
