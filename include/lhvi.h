@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 16  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 17  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -39,7 +39,8 @@ extern "C" {
                               * 13: lhvi_pbp_f2v selects the kernel families it launches with LHVI_PBP_F2V_* (replacing five bits that skipped kernels);
                               * 14: lhvi_mws_t, lhvi_mws_init / lhvi_mws_flips, lhvi_lbfgsb_host, lhvi_wall_clock_khz;
                               * 15: lhvi_exact_t, lhvi_exact_*, LHVI_E_NOT_PD;
-                              * 16: lhvi_gibbs_t, lhvi_gibbs_* */
+                              * 16: lhvi_gibbs_t, lhvi_gibbs_*;
+                              * 17: lhvi_gauss_exact_*, LHVI_GAUSS_EXACT_NB */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -752,6 +753,43 @@ int lhvi_gibbs_run(const lhvi_gibbs_t* m, int64_t chains, int32_t it_begin, int3
  * is ignored.  LHVI_E_NOT_PD when a J is not positive definite (x_d then holds the state). */
 int lhvi_gibbs_chain_host(const lhvi_gibbs_t* m, int32_t it_begin, int32_t it_end, int32_t* x_d, const double* z, const double* u,
                           int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2);
+
+/* ---- Exact Gaussian-MRF marginals: dense blocked fp64 Cholesky (osi/utils.py get_gaussian_mean_params_from_quadratic_params;
+ * csrc/gauss_exact.hip, csrc/gauss_exact.hpp) ----------------------------------------------------------------------------------
+ * p(x) ~ exp(x'Ax + b'x + c) over N hidden variables, J = -(A + A^T) = L L^T, X = L^-1, Sig = X^T X, mu = X^T (X b),
+ * var_j = sum_i X_ij^2, log det J = 2 sum log L_ii.  A matrix on the device is a "packed triangle": padded to T = ceil(N / NB)
+ * tiles a side (identity on the padding), lower block triangle only, tile (i, j) at (i (i + 1) / 2 + j) NB^2 doubles,
+ * column-major inside a tile.  All indices are 64-bit.  N = 0: every call returns LHVI_OK without a launch.
+ * LHVI_E_UNSUPPORTED: more than 46340 tiles a side. */
+#define LHVI_GAUSS_EXACT_NB 64
+/* doubles of one packed triangle / of the workspace of lhvi_gauss_exact_moments */
+size_t lhvi_gauss_exact_tri_doubles(int64_t N);
+size_t lhvi_gauss_exact_ws_doubles(int64_t N);
+/* J and b from the contributions of the conditioned factors, sorted by the host: entry e is J[ent_row[e]][ent_col[e]], row >=
+ * col, each pair once; vals[ent_ptr[e] .. ent_mid[e]) are the terms of A[row][col] and vals[ent_mid[e] .. ent_ptr[e + 1]) those
+ * of A[col][row], each in the reference's (factor, i, j) order (a diagonal entry has the first range only); b_vals[b_ptr[r] ..
+ * b_ptr[r + 1]) the terms of b[r].  One thread sums one entry in that order: the same input gives the same bits.
+ * Jt (a packed triangle) and b [T NB] must be zero on entry. */
+int lhvi_gauss_exact_assemble(int64_t N, int64_t n_ent, const int32_t* ent_row, const int32_t* ent_col, const int64_t* ent_ptr,
+                              const int64_t* ent_mid, const double* vals, const int64_t* b_ptr, const double* b_vals, double* Jt,
+                              double* b, void* stream);
+/* Jt = -(A + A^T) from a dense row-major A [N][N] */
+int lhvi_gauss_exact_pack(int64_t N, const double* A, double* Jt, void* stream);
+/* J -> L in place (Lt), blocked right-looking: per step a diagonal-tile kernel, a panel solve, a trailing update.  Xt: a second
+ * packed triangle, zero on entry; its diagonal tiles receive L_kk^-1.  tlog [T]: scratch; logdet [1] = log det J.
+ * bad [1]: the caller sets it to INT32_MAX; a pivot <= 0 or NaN lowers it to its column (atomic min on the integer) and is
+ * taken as 1, so every kernel of the run ends normally and the outputs are meaningless (the caller raises, LHVI_E_NOT_PD). */
+int lhvi_gauss_exact_factor(int64_t N, double* Lt, double* Xt, double* tlog, int32_t* bad, double* logdet, void* stream);
+/* X = L^-1 by blocked forward substitution, after lhvi_gauss_exact_factor on the same two triangles */
+int lhvi_gauss_exact_inverse(int64_t N, const double* Lt, double* Xt, void* stream);
+/* mu, var [T NB] (entries >= N: padding) from X and b [T NB]; sums in a fixed order.  ws: lhvi_gauss_exact_ws_doubles(N) */
+int lhvi_gauss_exact_moments(int64_t N, const double* Xt, const double* b, double* ws, double* mu, double* var, void* stream);
+/* out [S][S] = Sig[cols[a]][cols[b]] from the columns of X; S <= 65535; a column outside [0, N) gives zeros */
+int lhvi_gauss_exact_cov(int64_t N, const double* Xt, int32_t S, const int32_t* cols, double* out, void* stream);
+/* the whole computation on the HOST through the same tile routines in the same order (csrc/gauss_exact.hpp): J [N][N] dense
+ * row-major (its lower triangle is read), b, mu, var [N], logdet [1]; bad_col (may be NULL): the first column with a pivot <= 0
+ * or NaN, else -1.  LHVI_E_NOT_PD when there is one. */
+int lhvi_gauss_exact_host(int64_t N, const double* J, const double* b, double* mu, double* var, double* logdet, int64_t* bad_col);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 16            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 17            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -136,6 +136,7 @@ class GibbsStruct(C.Structure):
 
 E_NOT_PD = -5               # LHVI_E_NOT_PD
 EXACT_MAX_NC = 64           # LHVI_EXACT_MAX_NC
+GAUSS_EXACT_NB = 64         # LHVI_GAUSS_EXACT_NB
 
 # the objective of lhvi_lbfgsb_host: double fun(const double* x, void* ctx)
 LBFGSB_FUN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_void_p)
@@ -217,6 +218,15 @@ SIGNATURES = {
     'lhvi_gibbs_lds_bytes': (_sz, [_i32, _i32, _i32, _i32]),
     'lhvi_gibbs_init': (C.c_int, [C.POINTER(GibbsStruct), _i64, _vp, _vp]),
     'lhvi_gibbs_run': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gauss_exact_tri_doubles': (_sz, [_i64]),
+    'lhvi_gauss_exact_ws_doubles': (_sz, [_i64]),
+    'lhvi_gauss_exact_assemble': (C.c_int, [_i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gauss_exact_pack': (C.c_int, [_i64, _vp, _vp, _vp]),
+    'lhvi_gauss_exact_factor': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gauss_exact_inverse': (C.c_int, [_i64, _vp, _vp, _vp]),
+    'lhvi_gauss_exact_moments': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gauss_exact_cov': (C.c_int, [_i64, _vp, _i32, _vp, _vp, _vp]),
+    'lhvi_gauss_exact_host': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gibbs_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

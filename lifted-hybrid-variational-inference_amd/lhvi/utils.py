@@ -138,3 +138,126 @@ def get_conditional_quadratic(A, b, c, obs_args_vals):
     b_cond = A[np.ix_(xi, yi)] @ y + A[np.ix_(yi, xi)].T @ y + b[xi]
     c_cond = np.dot(y, A[np.ix_(yi, yi)] @ y) + np.dot(b[yi], y) + c
     return A[np.ix_(xi, xi)], b_cond, c_cond
+
+
+def get_conditional_gaussian(mu, Sig, obs_args_vals):
+    """``osi/utils.py:279-303``: mean and covariance of p(x_a | x_b) from the joint (mu, Sig) with x_b = ``obs_args_vals``
+    {index: value} (PRML 2.81, 2.82)"""
+    mu, Sig = np.asarray(mu, dtype=np.float64), np.asarray(Sig, dtype=np.float64)
+    bi = np.array(list(obs_args_vals.keys()), dtype=int)
+    bv = np.array([obs_args_vals[i] for i in bi], dtype=np.float64)
+    ai = np.setdiff1d(np.arange(len(mu)), bi)
+    Sbb_inv = np.linalg.inv(Sig[np.ix_(bi, bi)])
+    Sab = Sig[np.ix_(ai, bi)]
+    return mu[ai] + Sab @ (Sbb_inv @ (bv - mu[bi])), Sig[np.ix_(ai, ai)] - Sab @ Sbb_inv @ Sab.T
+
+
+def _quadratic_family():
+    from .potentials import GaussianPotential, LinearGaussianPotential, QuadraticPotential, X2Potential, XYPotential
+    return (QuadraticPotential, GaussianPotential, LinearGaussianPotential, X2Potential, XYPotential)
+
+
+def condition_factors_on_evidence(factors, evidence):
+    """``osi/utils.py:306-361`` for the quadratic family: a new list of factors reduced to the context of ``evidence`` {rv: value}
+    (the given factors are not modified).  A partly observed factor becomes a ``QuadraticPotential`` over its remaining
+    arguments (``get_conditional_quadratic``), a fully observed one a constant ``log_potential_fun`` with ``potential`` None.
+    An MLN or generic potential that the evidence touches raises ``NotImplementedError``."""
+    from copy import copy
+    from .potentials import QuadraticPotential
+    out = []
+    for factor in factors:
+        if not any(rv in evidence for rv in factor.nb):
+            out.append(factor)
+            continue
+        partial = {i: evidence[rv] for i, rv in enumerate(factor.nb) if rv in evidence}
+        f = copy(factor)
+        f.uncond_factor = factor
+        f.nb = [rv for rv in factor.nb if rv not in evidence]
+        potential = factor.potential
+        if not f.nb:
+            f.potential = None
+            f.log_potential_fun = (lambda fac: lambda x: fac.log_potential_fun([evidence[rv] for rv in fac.nb]))(factor)
+        elif isinstance(potential, _quadratic_family()):
+            pot = QuadraticPotential(*get_conditional_quadratic(*potential.get_quadratic_params(), partial))
+            if hasattr(potential, 'symmetric'):
+                pot.symmetric = potential.symmetric
+            f.potential = pot
+            f.log_potential_fun = pot.to_log_potential()
+        else:
+            raise NotImplementedError('%s: conditioning a %s on evidence is not supported (quadratic family only)'
+                                      % (factor, type(potential).__name__))
+        out.append(f)
+    return out
+
+
+def get_conditional_mrf(factors, rvs, evidence, update_rv_nbs=False):
+    """``osi/utils.py:432-455``: a ``Graph`` of the unobserved rvs and the conditioned, non-empty factors.  The rv objects are
+    shared with the caller's graph; ``update_rv_nbs`` runs ``init_nb`` on the result (which rewrites their ``nb``)."""
+    from .graph import Graph
+    cond = [f for f in condition_factors_on_evidence(factors, evidence) if len(f.nb) > 0]
+    g = Graph()
+    g.rvs = [rv for rv in rvs if rv not in evidence]
+    g.factors = cond
+    if update_rv_nbs:
+        g.init_nb()
+    return g
+
+
+def get_joint_quadratic_params(factor_params, factor_scopes, N=None):
+    """``osi/utils.py:458-488``: (A, b, c) of x'Ax + b'x + c from quadratic factors [(A1, b1, c1), ...] over the index tuples
+    ``factor_scopes``, summed in the reference's factor, i, j order"""
+    flat = np.array([i for scope in factor_scopes for i in scope], dtype=int)
+    assert np.all(flat >= 0)
+    if N is None:
+        N = int(flat.max()) + 1
+    A, b, c = np.zeros([N, N], dtype='float'), np.zeros(N, dtype='float'), 0
+    for (A_, b_, c_), scope in zip(factor_params, factor_scopes):
+        n = len(scope)
+        for i in range(n):
+            for j in range(n):
+                A[scope[i], scope[j]] += A_[i, j]
+            b[scope[i]] += b_[i]
+        c += c_
+    return A, b, c
+
+
+def get_quadratic_params_from_factor_graph(factors, rvs_list):
+    """``osi/utils.py:491-522``: ((A, b, c), rvs_idx) of the joint quadratic of exp-quadratic factors; a factor's
+    ``log_potential_fun`` (a ``LogQuadratic``) is read when set, else its potential's ``get_quadratic_params``"""
+    from .potentials import LogQuadratic
+    rvs_idx = {rv: i for i, rv in enumerate(rvs_list)}
+    params, scopes = [], []
+    for factor in factors:
+        lp = getattr(factor, 'log_potential_fun', None)
+        if lp is not None:
+            assert isinstance(lp, LogQuadratic)
+            params.append((np.asarray(lp.A), np.asarray(lp.b), lp.c))
+        else:
+            assert isinstance(factor.potential, _quadratic_family())
+            params.append(factor.potential.get_quadratic_params())
+        scopes.append(tuple(rvs_idx[rv] for rv in factor.nb))
+    return get_joint_quadratic_params(params, scopes, len(rvs_list)), rvs_idx
+
+
+def get_prec_mat_from_gaussian_mrf(factors, rvs_list):
+    """``osi/utils.py:544-564``: (precision matrix, rvs_idx) of a Gaussian MRF of ``GaussianPotential`` factors"""
+    from .potentials import GaussianPotential
+    rvs_idx = {rv: i for i, rv in enumerate(rvs_list)}
+    prec = np.zeros([len(rvs_list), len(rvs_list)], dtype='float')
+    for factor in factors:
+        assert isinstance(factor.potential, GaussianPotential)
+        J = np.linalg.inv(factor.potential.sig)
+        pos = [rvs_idx[rv] for rv in factor.nb]
+        for i in range(len(pos)):
+            for j in range(len(pos)):
+                prec[pos[i], pos[j]] += J[i, j]
+    return prec, rvs_idx
+
+
+def get_gaussian_mean_params_from_quadratic_params(A, b, mu_only=True):
+    """``osi/utils.py:525-541`` on the device: mu (and Sig unless ``mu_only``) with -1/2 (x - mu)' Sig^-1 (x - mu) = x'Ax + b'x +
+    const.  ``A``, ``b``: arrays or device tensors (the results are of the same kind).  A blocked fp64 Cholesky of
+    J = -(A + A^T) (csrc/gauss_exact.hip) instead of ``np.linalg.solve`` / ``inv``; a J that is not positive definite raises
+    ``ValueError``; without a GPU the call raises ``LhviError``."""
+    from . import gauss_exact
+    return gauss_exact.mean_params_from_quadratic(A, b, mu_only)
