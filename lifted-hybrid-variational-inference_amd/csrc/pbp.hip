@@ -864,42 +864,50 @@ __global__ void __launch_bounds__(BLOCK) pbp_f2v_fast_kernel(lhvi_graph_t g, lhv
 // (a tail zone of one-entry claims lost: 0.875 -> 0.948 ms per heavy launch, profiles/r05_experiments.md item 1)
 template <int WORK_CHUNK, int WAVES_PER_BLOCK = BLOCK / WAVE>
 struct WorkCursor {
-    uint32_t* ticket;       // nullptr: static striding
-    int item, limit, left, stride, pending, lo;
-    __device__ __forceinline__ int claim(int lane) const {
+    // `ticket()` names the counters (nullptr: static striding).  It is called where a chunk is claimed, once per WORK_CHUNK
+    // entries, so a kernel short of scalar registers can hand in a reload of its argument instead of keeping the pointer
+    int item, limit, left, pending;
+    int part;               // the counter of this workgroup's range; -1: static striding
+    int step;               // with a ticket: where this workgroup's range starts; without: the stride
+    template <typename Ticket>
+    __device__ __forceinline__ int claim(int lane, Ticket&& ticket) const {
         int v = 0;
-        if (lane == 0) v = lo + (int)atomicAdd(ticket, (uint32_t)WORK_CHUNK);
+        // (the comparison is formed where it is used: hoisted, its mask would sit in two scalar registers for the whole kernel)
+        // (and so is the counter's offset: kept as a 64-bit byte offset it would take two more)
+        int which = part;
+        asm volatile("" : "+v"(lane), "+s"(which));
+        if (lane == 0) v = step + (int)atomicAdd(ticket() + which, (uint32_t)WORK_CHUNK);
         return v;                                           // valid in lane 0
     }
     // with tickets the list is cut into one contiguous range per XCD (workgroup i runs on XCD i mod 8, and each XCD has
     // its own L2: its waves then walk one region of the descriptors, particles and messages), each with its own counter
-    __device__ __forceinline__ bool start(uint32_t* base, int nitems, int lane) {
-        stride = gridDim.x * WAVES_PER_BLOCK;
-        left = 0; pending = 0; lo = 0; limit = nitems;
-        ticket = base;
-        if (ticket) {
+    template <typename Ticket>
+    __device__ __forceinline__ bool start(Ticket&& ticket, int nitems, int lane) {
+        left = 0; pending = 0; limit = nitems; part = -1;
+        if (ticket()) {
             const int parts = min((int)gridDim.x, LHVI_PBP_TICKET_COUNTERS);
-            const int part = blockIdx.x % parts;
+            part = blockIdx.x % parts;
             const int per = ((nitems + parts - 1) / parts + WORK_CHUNK - 1) / WORK_CHUNK * WORK_CHUNK;
-            lo = min(part * per, nitems);
-            limit = min(lo + per, nitems);
-            ticket = base + part;
-            item = __builtin_amdgcn_readfirstlane(claim(lane));
-            pending = claim(lane);
+            step = min(part * per, nitems);
+            limit = min(step + per, nitems);
+            item = __builtin_amdgcn_readfirstlane(claim(lane, ticket));
+            pending = claim(lane, ticket);
             left = WORK_CHUNK - 1;
         } else {
+            step = gridDim.x * WAVES_PER_BLOCK;
             item = blockIdx.x * WAVES_PER_BLOCK + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
         }
         return item < limit;
     }
     __device__ __forceinline__ int next() const {           // the entry after `item` (>= limit: none)
-        if (!ticket) return item + stride;
+        if (part < 0) return item + step;
         return left > 0 ? item + 1 : __builtin_amdgcn_readfirstlane(pending);
     }
-    __device__ __forceinline__ void advance(int nxt, int lane) {     // move to `nxt` = next()
-        if (ticket) {
+    template <typename Ticket>
+    __device__ __forceinline__ void advance(int nxt, int lane, Ticket&& ticket) {     // move to `nxt` = next()
+        if (part >= 0) {
             if (left > 0) --left;
-            else { left = WORK_CHUNK - 1; pending = claim(lane); }
+            else { left = WORK_CHUNK - 1; pending = claim(lane, ticket); }
         }
         item = nxt;
     }
@@ -1081,27 +1089,85 @@ __device__ __forceinline__ int round_log2_width(int rem) {      // 64 lanes for 
     return lw;
 }
 
-__device__ __forceinline__ HeavyData heavy_fetch(const FastDesc& d, const lhvi_graph_t& g, const lhvi_pbp_t& s,
-                                                 const double* __restrict__ v2f, int lane) {
+// What the heavy kernel reads of lhvi_graph_t / lhvi_pbp_t: the dispatcher fills this block, the two structs stay on the host
+// (passed by value they cost a 920-byte kernarg and the scalar registers of whatever the compiler chose to keep of them).
+struct HeavyArgs {
+    int32_t n, T;
+    uint32_t flags;
+    const double* particles;
+    const double* old_particles;
+    const double* dom_val;
+    uint32_t* f2v_ticket;       // the work counters (nullptr: static striding)
+    uint32_t* stats;            // two counters of grid / fallback edges, or nullptr
+};
+// The two pointers above are needed once per chunk of eight edges and once per wave.  The kernel reads them from the
+// argument block where it needs them instead of holding four scalar registers for them through the edge loop (the asm keeps
+// the compiler from hoisting the load back to the top).  HeavyArgs is the kernel's FIRST argument: its offset is 0.
+template <typename T>
+__device__ __forceinline__ T heavy_arg_reload(size_t offset) {
+    auto p = (const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *(const __attribute__((address_space(4))) T*)(p + offset);
+}
+// A descriptor in the two halves the kernel consumes at different times (same 128 bytes as FastDesc): the head says what
+// to fetch and is read one edge ahead, the coefficients are read when the edge's arithmetic starts.
+struct HeavyHead {
+    int32_t e, tv, pv, pce, cls, pos, kind, nj, np, T, gb, par_off;
+    double pval;
+    int32_t type, grid;
+};
+struct HeavyCoef { double ay, by, c, axy, bx, kx, gx0, gh; };
+struct HeavyDesc { HeavyHead h; HeavyCoef k; };
+static_assert(sizeof(HeavyDesc) == sizeof(FastDesc) && offsetof(HeavyDesc, k) == offsetof(FastDesc, ay) &&
+              offsetof(HeavyHead, pval) == offsetof(FastDesc, pval) && offsetof(HeavyHead, grid) == offsetof(FastDesc, pad) + 4 &&
+              offsetof(HeavyCoef, gx0) + offsetof(HeavyDesc, k) == offsetof(FastDesc, pad2), "HeavyDesc is FastDesc in two halves");
+
+// A wave-uniform row pointer pinned to scalar registers: the compiler then keeps the row base on the scalar side and a
+// load or store through it with an unsigned 32-bit lane index takes the saddr + voffset form (left alone it folds the
+// lane into a 64-bit per-lane base, kept across the edge loop, and adds the row offset with vector instructions)
+// (the result is typed as a global-memory pointer: through the asm the compiler can no longer infer the address space, and
+// a generic pointer would be accessed with flat instructions)
+template <typename T> using global_ptr = __attribute__((address_space(1))) T*;
+template <typename T>
+__device__ __forceinline__ global_ptr<T> scalar_row(T* p) { global_ptr<T> q = (global_ptr<T>)p; asm("" : "+s"(q)); return q; }
+
+// (the byte offset in 32 bits: a row is far shorter than 4 GiB)
+template <typename T>
+__device__ __forceinline__ T row_load(global_ptr<T> row, uint32_t i) { return *(global_ptr<T>)((global_ptr<const char>)row + i * (uint32_t)sizeof(T)); }
+template <typename T>
+__device__ __forceinline__ void row_store(global_ptr<T> row, uint32_t i, T v) { *(global_ptr<T>)((global_ptr<char>)row + i * (uint32_t)sizeof(T)) = v; }
+
+__device__ __forceinline__ HeavyData heavy_fetch(const HeavyHead& d, const HeavyArgs& s, const double* __restrict__ v2f, int lane) {
     HeavyData h;
     // edges whose integral points go through the grid recurrence (or its fallback) fetch their particles only
-    const int n = s.n, np = d.np, npts = grid_eligible(d.pad[1], d.nj, d.T) ? d.np : d.np + d.T;
+    const int n = s.n, np = d.np, npts = grid_eligible(d.grid, d.nj, d.T) ? d.np : d.np + d.T;
+    // row bases on the scalar side, the lane as an unsigned 32-bit offset: the loads take the saddr + voffset form
+    const uint32_t ul = (uint32_t)lane;
+    const auto prow = scalar_row(s.particles + (int64_t)d.tv * n);
+    // (the grid row is read by the edges off the recurrence only: its base comes from the argument block when one is met)
+    const auto grid_row = [&] { return scalar_row(heavy_arg_reload<const double*>(offsetof(HeavyArgs, dom_val)) + d.gb); };
     h.y = d.pval; h.m = 0.0; h.x0 = 0.0; h.x1 = 0.0;
-    if (is_hidden(d.pval) && lane < d.nj) { h.y = s.old_particles[(int64_t)d.pv * n + lane]; h.m = v2f[(int64_t)d.pce * n + lane]; }
-    {
+    if (is_hidden(d.pval) && lane < d.nj) {
+        h.y = row_load(scalar_row(s.old_particles + (int64_t)d.pv * n), ul);
+        h.m = row_load(scalar_row(v2f + (int64_t)d.pce * n), ul);
+    }
+    if (np == 64 && npts == 64) {
+        // the dominant shape (64 target particles, grid points by the recurrence): one full round, lane = particle
+        h.x0 = row_load(prow, ul);
+    } else {
         const int pl = lane & ((1 << round_log2_width(npts)) - 1);
-        if (pl < npts) h.x0 = pl < np ? s.particles[(int64_t)d.tv * n + pl] : g.dom_val[d.gb + pl - np];
+        if (pl < npts) h.x0 = pl < np ? row_load(prow, (uint32_t)pl) : row_load(grid_row(), (uint32_t)(pl - np));
     }
     if (npts > 64) {
         const int rem = npts - 64, pl = lane & ((1 << round_log2_width(rem)) - 1), pp = 64 + pl;
-        if (pl < rem) h.x1 = pp < np ? s.particles[(int64_t)d.tv * n + pp] : g.dom_val[d.gb + pp - np];
+        if (pl < rem) h.x1 = pp < np ? row_load(prow, (uint32_t)pp) : row_load(grid_row(), (uint32_t)(pp - np));
     }
     return h;
 }
 
-__global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_eu(LHVI_HEAVY_WAVES, LHVI_HEAVY_WAVES))) pbp_f2v_heavy_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ v2f,
-                                                             double* __restrict__ f2v, const FastDesc* __restrict__ descs,
-                                                             int nitems, uint32_t* __restrict__ stats) {
+__global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_eu(LHVI_HEAVY_WAVES, LHVI_HEAVY_WAVES))) pbp_f2v_heavy_kernel(HeavyArgs s, const double* __restrict__ v2f,
+                                                             double* __restrict__ f2v, const HeavyDesc* __restrict__ descs,
+                                                             int nitems) {
     __shared__ AB sh_all[HEAVY_BLOCK / WAVE][WAVE];
     __shared__ double sh_tab[EXP_TAB_N];
     __shared__ LogRec sh_log[LOG_TAB_N];
@@ -1112,25 +1178,29 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
     AB* sh = sh_all[wid];
     // (descs is a kernel argument of its own so that its restrict qualifier holds and the descriptors come through the
     // scalar cache: s_load does not take part in vmcnt, which the prefetched vector loads rely on)
-    const int last = nitems - 1;
     const int n = s.n, S = s.n + s.T;
     WorkCursor<8, HEAVY_BLOCK / WAVE> cur;
-    if (!cur.start(s.f2v_ticket, nitems, lane)) return;
+    const auto ticket = [] { return heavy_arg_reload<uint32_t*>(offsetof(HeavyArgs, f2v_ticket)); };
+    if (!cur.start(ticket, nitems, lane)) return;
     int n_grid = 0, n_direct = 0;          // edges of this wave whose integral points went through the recurrence / fell back
     // pipeline: the loads of edge k+1 are issued as soon as edge k has been staged into LDS (its registers are free
-    // then, so nothing has to be rotated) and stay in flight through the term loops of edge k; `dn` is the full
-    // descriptor of edge k+1, fetched one edge ahead, `d` the seven words the arithmetic of edge k needs
+    // then, so nothing has to be rotated) and stay in flight through the term loops of edge k; `hn` is the head of the
+    // descriptor of edge k+1, fetched one edge ahead; of edge k the six words of its head that the arithmetic needs stay,
+    // and its coefficients are loaded here (one descriptor's worth of scalar registers, not one and a half)
     struct { int32_t e, nj, np, T, gb, grid; double ay, by, c, axy, bx, kx, gx0, gh; } d;
-    FastDesc dn = descs[cur.item];
-    HeavyData h = heavy_fetch(dn, g, s, v2f, lane);
+    HeavyHead hn = descs[cur.item].h;
+    HeavyData h = heavy_fetch(hn, s, v2f, lane);
     for (;;) {
-        d.e = dn.e; d.nj = dn.nj; d.np = dn.np; d.T = dn.T; d.gb = dn.gb; d.grid = dn.pad[1];
-        d.ay = dn.ay; d.by = dn.by; d.c = dn.c; d.axy = dn.axy; d.bx = dn.bx; d.kx = dn.kx; d.gx0 = dn.pad2[0]; d.gh = dn.pad2[1];
+        d.e = hn.e; d.nj = hn.nj; d.np = hn.np; d.T = hn.T; d.gb = hn.gb; d.grid = hn.grid;
+        {
+            const HeavyCoef k = descs[cur.item].k;
+            d.ay = k.ay; d.by = k.by; d.c = k.c; d.axy = k.axy; d.bx = k.bx; d.kx = k.kx; d.gx0 = k.gx0; d.gh = k.gh;
+        }
         const int nxt = cur.next();
         const bool more = nxt < cur.limit;
-        dn = descs[__builtin_amdgcn_readfirstlane(min(nxt, last))];
+        hn = descs[__builtin_amdgcn_readfirstlane(min(nxt, cur.limit - 1))].h;     // (no next entry: any descriptor of the list, unused)
         const int np = d.np, nj = d.nj;
-        double* out = f2v + (int64_t)d.e * S;
+        const auto out = scalar_row(f2v + (int64_t)d.e * S);
         const double kconst = d.kx;
         // integral points by recurrence along the uniform grid (below) when every exponent a_j + b_j x + kx x^2 stays far
         // inside the double range over the whole grid (then neither form under- or overflows and they agree to rounding)
@@ -1158,7 +1228,7 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
         }
         const int npts = eligible ? np : np + d.T;          // eligible: the integral points are handled after the particle rounds
         const double x0 = h.x0, x1 = h.x1;
-        if (more) h = heavy_fetch(dn, g, s, v2f, lane);
+        if (more) h = heavy_fetch(hn, s, v2f, lane);
         if (grid_path) {
             double gv = exp_core(fma(mine.b, d.gx0, mine.a), sh_tab);
             const double q = exp_core(mine.b * d.gh, sh_tab);
@@ -1168,7 +1238,7 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
                 const int t = t0 + grid_owned_point(lane);
                 if (t < d.T && !(lane & 1)) {
                     const double xt = fma((double)t, d.gh, d.gx0);
-                    out[n + t] = sum > 0.0 ? fma(kconst * xt, xt, log_table(sum, sh_log)) : -700.0;
+                    row_store(out, (uint32_t)(n + t), sum > 0.0 ? fma(kconst * xt, xt, log_table(sum, sh_log)) : -700.0);
                 }
             }
         } else if (eligible) {
@@ -1179,11 +1249,11 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
                 const int lw = round_log2_width(rem);
                 const int width = 1 << lw, split = 64 >> lw, sub = lane >> lw, pl = lane & (width - 1);
                 const bool valid = pl < rem;
-                const double X1 = valid ? g.dom_val[d.gb + t0 + pl] : 0.0, C = kconst * X1 * X1;
+                const double X1 = valid ? heavy_arg_reload<const double*>(offsetof(HeavyArgs, dom_val))[d.gb + t0 + pl] : 0.0, C = kconst * X1 * X1;
                 const int chunk = (s.flags & LHVI_PBP_SKIP_TERMS) ? 0 : (nj + split - 1) >> (6 - lw);
                 double acc = fast_accumulate_floor<LHVI_HEAVY_UNROLL>(sh + sub * chunk, sh_tab, chunk, X1, C);
                 for (int off = width; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
-                if (valid && sub == 0) out[n + t0 + pl] = acc > 0.0 ? log_table(acc, sh_log) : -700.0;
+                if (valid && sub == 0) row_store(out, (uint32_t)(n + t0 + pl), acc > 0.0 ? log_table(acc, sh_log) : -700.0);
             }
         }
 #pragma nounroll
@@ -1199,11 +1269,12 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
             const int chunk = (s.flags & LHVI_PBP_SKIP_TERMS) ? 0 : (nj + split - 1) >> (6 - lw);   // flag 16: tuning aid, skips the term loop
             double acc = fast_accumulate_floor<LHVI_HEAVY_UNROLL>(sh + sub * chunk, sh_tab, chunk, X1, C);
             for (int off = width; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
-            if (valid && sub == 0) out[p < np ? p : n + (p - np)] = acc > 0.0 ? log_table(acc, sh_log) : -700.0;
+            if (valid && sub == 0) row_store(out, (uint32_t)(p < np ? p : n + (p - np)), acc > 0.0 ? log_table(acc, sh_log) : -700.0);
         }
         if (!more) break;
-        cur.advance(nxt, lane);
+        cur.advance(nxt, lane, ticket);
     }
+    uint32_t* stats = heavy_arg_reload<uint32_t*>(offsetof(HeavyArgs, stats));
     if (stats && lane == 0) { atomicAdd(stats, (uint32_t)n_grid); atomicAdd(stats + 1, (uint32_t)n_direct); }
 }
 
@@ -1468,7 +1539,8 @@ __global__ void __launch_bounds__(BLOCK) pbp_f2v_light_kernel(lhvi_graph_t g, lh
     // (static striding: this kernel's entries are short, a late workgroup owes little, and neighbouring waves on neighbouring
     // entries measured 15 % faster than chunks of 64 through the ticket)
     WorkCursor<64> work;
-    if (!work.start(nullptr, nitems, lane)) return;
+    const auto no_ticket = [] { return (uint32_t*)nullptr; };
+    if (!work.start(no_ticket, nitems, lane)) return;
     struct { int32_t e, type, nj, np, T, pce; double pval, A0, b0, c0, A1, b1, c1; } d;
     FastDesc dn = descs[work.item];
     LightData h = light_fetch(dn, g, s, v2f, lane);
@@ -1504,7 +1576,7 @@ __global__ void __launch_bounds__(BLOCK) pbp_f2v_light_kernel(lhvi_graph_t g, lh
             if (lane < d.np) out[lane] = res > 0.0 ? log_table(res, sh_log) : -700.0;
         }
         if (!more) break;
-        work.advance(nxt, lane);
+        work.advance(nxt, lane, no_ticket);
     }
 }
 
@@ -3200,13 +3272,16 @@ int lhvi_pbp_f2v(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_
         // several of them; a short list (a small graph, the interior part of a shard) keeps one entry per wave and strides
         constexpr int HWPB = HEAVY_BLOCK / WAVE;
         const int heavy_grid = min((s->n_heavy + HWPB - 1) / HWPB, max(cus * max(heavy_per_cu - share, 1) - spare * (BLOCK / WAVE) / HWPB, 1));
-        lhvi_pbp_t sh = *s;
-        if (sh.f2v_ticket && (int64_t)s->n_heavy < (int64_t)heavy_grid * HWPB * 8 * 4) sh.f2v_ticket = nullptr;
+        HeavyArgs ha;
+        ha.n = s->n; ha.T = s->T; ha.flags = s->flags;
+        ha.particles = s->particles; ha.old_particles = s->old_particles; ha.dom_val = g->dom_val;
+        ha.f2v_ticket = s->f2v_ticket;
+        ha.stats = s->f2v_ticket ? s->f2v_ticket + LHVI_PBP_TICKET_COUNTERS : nullptr;
+        if (ha.f2v_ticket && (int64_t)s->n_heavy < (int64_t)heavy_grid * HWPB * 8 * 4) ha.f2v_ticket = nullptr;
         if (s->f2v_ticket && hipMemsetAsync(s->f2v_ticket, 0, LHVI_PBP_TICKET_WORDS * sizeof(uint32_t), as_stream(stream)) != hipSuccess)
             return LHVI_E_LAUNCH;
         hipLaunchKernelGGL(pbp_f2v_heavy_kernel, dim3(heavy_grid), dim3(HEAVY_BLOCK), 0, as_stream(stream),
-                           *g, sh, v2f, f2v, reinterpret_cast<const FastDesc*>(s->heavy_desc), s->n_heavy,
-                           s->f2v_ticket ? s->f2v_ticket + LHVI_PBP_TICKET_COUNTERS : (uint32_t*)nullptr);
+                           ha, v2f, f2v, reinterpret_cast<const HeavyDesc*>(s->heavy_desc), s->n_heavy);
     }
     if (want(LHVI_PBP_F2V_SMALL)) {
         // lane groups as narrow as the particle count allows: 10 / 12 lanes, or 8 with two particles per lane, for the small16 list;
