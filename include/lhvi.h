@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 17  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 18  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -40,7 +40,8 @@ extern "C" {
                               * 14: lhvi_mws_t, lhvi_mws_init / lhvi_mws_flips, lhvi_lbfgsb_host, lhvi_wall_clock_khz;
                               * 15: lhvi_exact_t, lhvi_exact_*, LHVI_E_NOT_PD;
                               * 16: lhvi_gibbs_t, lhvi_gibbs_*;
-                              * 17: lhvi_gauss_exact_*, LHVI_GAUSS_EXACT_NB */
+                              * 17: lhvi_gauss_exact_*, LHVI_GAUSS_EXACT_NB;
+                              * 18: lhvi_mix_t, lhvi_mix_*, LHVI_MIX_* */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -790,6 +791,81 @@ int lhvi_gauss_exact_cov(int64_t N, const double* Xt, int32_t S, const int32_t* 
  * row-major (its lower triangle is read), b, mu, var [N], logdet [1]; bad_col (may be NULL): the first column with a pivot <= 0
  * or NaN, else -1.  LHVI_E_NOT_PD when there is one. */
 int lhvi_gauss_exact_host(int64_t N, const double* J, const double* b, double* mu, double* var, double* logdet, int64_t* bad_col);
+
+/* ---- Conditional queries on a fitted mixture belief (osi/mixture_beliefs.py:505-746, osi/utils.py:21-98; csrc/mixture.hip,
+ * csrc/mixture.hpp) ---------------------------------------------------------------------------------------------------------
+ * q(x) = sum_k w_k prod_v q_vk(x_v) over V "rows" (ground variables or lifted clusters); q_vk is N(mu_vk, var_vk) or a
+ * categorical pi_vk.  Conditioning on observed rows re-weights the components: w' = softmax(log w + sum_o log q_ok(x_o)).
+ * Variables enter every call as int32 row indices, repeats allowed.  Evidence is X [M][n_obs] doubles: a value (continuous
+ * row) or a state index (discrete row), NaN = not observed in that evidence row. */
+#define LHVI_MIX_MAX_K 128      /* the limit of lhvi_vi_map_bfgs; beyond it every call returns LHVI_E_UNSUPPORTED */
+#define LHVI_MIX_TILE 64        /* observed variables of one stage-1 partial sum of lhvi_mix_condition */
+#define LHVI_MIX_ROWS 4         /* evidence rows that share one pass over the records */
+#define LHVI_MIX_GAUSSIAN 0     /* normaliser: c = -1/2 log 2 pi + 1/2 log(1 / var) (osi/mixture_beliefs.py:538) */
+#define LHVI_MIX_VI 1           /* normaliser: c = -log(2.506628274631 var), the density of VarInference.norm_pdf */
+typedef struct lhvi_mix {
+    int32_t V, K, Dmax;
+    const int32_t* nstates;     /* [V] 0: continuous row, > 0: discrete row of that many states, < 0: row without parameters */
+    const double* logw;         /* [K] log w */
+    const double* rec;          /* [V][K][3] (c, mu, 1 / var), c by the normaliser; the layout of lhvi_exact_mix_prepare */
+    const double* lpi;          /* [V][K][Dmax] log pi (-inf beyond the row's states), or NULL without discrete rows */
+    const double* pi;           /* [V][K][Dmax] pi, the caller's eta_d itself, or NULL without discrete rows */
+} lhvi_mix_t;
+/* logw, rec and lpi (may be NULL when no row is discrete) from w [K], eta_c [V][K][2] (mean, variance; may be NULL when no
+ * row is continuous), eta_d [V][K][Dmax] and nstates [V]: the arrays of lhvi_vi_t, read in place */
+int lhvi_mix_prepare(int32_t V, int32_t K, int32_t Dmax, int32_t normaliser, const double* w, const double* eta_c,
+                     const double* eta_d, const int32_t* nstates, double* logw, double* rec, double* lpi, void* stream);
+/* doubles of the workspace of lhvi_mix_condition: M * tiles * K, tiles = ceil(n_obs / LHVI_MIX_TILE) */
+size_t lhvi_mix_condition_ws_doubles(int64_t M, int32_t n_obs, int32_t K);
+/* comp [M][K] = sum_o log q_ok(X[m][o]), logp [M] = logsumexp_k(log w + comp), condw [M][K] = exp(log w + comp - logp); each
+ * output may be NULL.  Two stages, no atomics: a thread sums one tile of observed variables in index order for one component
+ * and LHVI_MIX_ROWS evidence rows, then a thread per evidence row adds the tiles in index order.  The launch geometry depends on
+ * (n_obs, K) only: a row's bits depend neither on M, nor on its position, nor on the run.  n_obs = 0: comp = 0, condw = w.
+ * A discrete observation that is no state of its row gives NaN (the caller validates). */
+int lhvi_mix_condition(const lhvi_mix_t* b, int64_t M, int32_t n_obs, const int32_t* obs_rows, const double* X, double* ws,
+                       double* comp, double* logp, double* condw, void* stream);
+/* marginal MAP of every (evidence row m, query q) under the weights condw [M][K] (marginal_map :723-746): xout / fout [M][n_q].
+ * Discrete row: the index of the first state of largest sum_k condw[m][k] pi[q][k][s] (drv_belief_map :693-708) and that
+ * probability.  Continuous row: the mode of sum_k condw[m][k] N(x; mu_qk, var_qk) inside [lo[q], hi[q]] and its log density
+ * (get_scalar_gm_mode, osi/utils.py:66-98): a safeguarded Newton iteration (at most max_iter steps) from every component mean
+ * clipped to the bounds, the best start kept, ties to the lowest component.  lanes: lanes per item, a power of two <= 64; the
+ * answer does not depend on it.  qobs_ptr [n_q + 1] / qobs_idx (or NULL / NULL, then X is not read): the positions of query q
+ * in the observed list of X [M][n_obs]; a query that row m observes there returns that value (fout NaN).  A row without
+ * parameters returns NaN. */
+int lhvi_mix_marginal_map(const lhvi_mix_t* b, int64_t M, const double* condw, int32_t n_q, const int32_t* query_rows,
+                          const double* lo, const double* hi, int32_t n_obs, const double* X, const int32_t* qobs_ptr,
+                          const int32_t* qobs_idx, int32_t lanes, int32_t max_iter, double* xout, double* fout, void* stream);
+/* out [M][n_q][P] = log sum_k condw[m][k] q_qk(x[q][p]), x [n_q][P]: values (continuous row) or state indices (discrete) */
+int lhvi_mix_log_belief(const lhvi_mix_t* b, int64_t M, const double* condw, int32_t n_q, const int32_t* query_rows, int32_t P,
+                        const double* x, double* out, void* stream);
+/* joint MAP of Nd discrete rows (drows) and Nc continuous rows (crows, bounds lo / hi [Nc]) under the log weights logw [K]:
+ * joint_map_from_belief_params (:771-867) with get_multivar_gm_mode(init_xs=[xc]) (osi/utils.py:101-161), S starts, one workgroup
+ * each.  Start s: x0 [S][Nc] (joint_map: column k of Mu, NOT clipped) and xd0 [S][Nd] (joint_map: argmax_s pi[n][k][s]).  Per
+ * coordinate iteration (at most coord_its): projected gradient ascent with Polyak averaging on the continuous block (gamma = 0.05,
+ * grad_lr = 0.01, at most grad_its = 500 steps, tol = 1e-7 in the reference), then one sweep over the discrete rows, each set to
+ * the first state of largest joint density.  Outputs per start: xc [S][Nc] of the best coordinate iteration, xd [S][Nd] of the
+ * LAST sweep (the reference's best_xd aliases xd, :848), best_obj [S]; the caller takes the first start of largest best_obj.
+ * A start stops early when a whole coordinate iteration changed neither xd nor a bit of xc (the rest would repeat it).
+ * ws: lhvi_mix_joint_map_ws_doubles() doubles.  Rows and xd0 must be valid (the caller checks). */
+size_t lhvi_mix_joint_map_ws_doubles(int32_t K, int32_t Nc, int32_t Nd, int32_t Dmax, int32_t S);
+int lhvi_mix_joint_map(const lhvi_mix_t* b, const double* logw, int32_t Nc, const int32_t* crows, const double* lo, const double* hi,
+                       int32_t Nd, const int32_t* drows, int32_t S, const double* x0, const int32_t* xd0, int32_t coord_its,
+                       double gamma, double grad_lr, int32_t grad_its, double tol, double* ws, double* xc, int32_t* xd,
+                       double* best_obj, void* stream);
+/* the same entry points on the HOST through the device's code (csrc/mixture.hpp) with one "lane"; every pointer is host memory */
+int lhvi_mix_prepare_host(int32_t V, int32_t K, int32_t Dmax, int32_t normaliser, const double* w, const double* eta_c,
+                          const double* eta_d, const int32_t* nstates, double* logw, double* rec, double* lpi);
+int lhvi_mix_condition_host(const lhvi_mix_t* b, int64_t M, int32_t n_obs, const int32_t* obs_rows, const double* X, double* ws,
+                            double* comp, double* logp, double* condw);
+int lhvi_mix_marginal_map_host(const lhvi_mix_t* b, int64_t M, const double* condw, int32_t n_q, const int32_t* query_rows,
+                               const double* lo, const double* hi, int32_t n_obs, const double* X, const int32_t* qobs_ptr,
+                               const int32_t* qobs_idx, int32_t max_iter, double* xout, double* fout);
+int lhvi_mix_log_belief_host(const lhvi_mix_t* b, int64_t M, const double* condw, int32_t n_q, const int32_t* query_rows,
+                             int32_t P, const double* x, double* out);
+int lhvi_mix_joint_map_host(const lhvi_mix_t* b, const double* logw, int32_t Nc, const int32_t* crows, const double* lo,
+                            const double* hi, int32_t Nd, const int32_t* drows, int32_t S, const double* x0, const int32_t* xd0,
+                            int32_t coord_its, double gamma, double grad_lr, int32_t grad_its, double tol, double* ws, double* xc,
+                            int32_t* xd, double* best_obj);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 17            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 18            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -138,11 +138,21 @@ E_NOT_PD = -5               # LHVI_E_NOT_PD
 EXACT_MAX_NC = 64           # LHVI_EXACT_MAX_NC
 GAUSS_EXACT_NB = 64         # LHVI_GAUSS_EXACT_NB
 
+MIX_MAX_K, MIX_TILE, MIX_ROWS = 128, 64, 4     # LHVI_MIX_MAX_K / LHVI_MIX_TILE / LHVI_MIX_ROWS
+MIX_GAUSSIAN, MIX_VI = 0, 1                     # normaliser of lhvi_mix_prepare
+
+
+class MixStruct(C.Structure):
+    _fields_ = [('V', C.c_int32), ('K', C.c_int32), ('Dmax', C.c_int32), ('nstates', C.c_void_p), ('logw', C.c_void_p),
+                ('rec', C.c_void_p), ('lpi', C.c_void_p), ('pi', C.c_void_p)]
+
+
 # the objective of lhvi_lbfgsb_host: double fun(const double* x, void* ctx)
 LBFGSB_FUN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_void_p)
 
 _G, _P, _S, _VI = C.POINTER(GraphStruct), C.POINTER(PotsStruct), C.POINTER(PbpStruct), C.POINTER(ViStruct)
 _GP = C.POINTER(GabpPlanStruct)
+_MX = C.POINTER(MixStruct)
 _vp, _i32, _i64, _u32, _u64, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); must list every symbol include/lhvi.h declares (tests/test_abi.py checks)
@@ -227,6 +237,18 @@ SIGNATURES = {
     'lhvi_gauss_exact_moments': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gauss_exact_cov': (C.c_int, [_i64, _vp, _i32, _vp, _vp, _vp]),
     'lhvi_gauss_exact_host': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_mix_prepare': (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_mix_condition_ws_doubles': (_sz, [_i64, _i32, _i32]),
+    'lhvi_mix_condition': (C.c_int, [_MX, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_mix_marginal_map': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp]),
+    'lhvi_mix_log_belief': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
+    'lhvi_mix_joint_map_ws_doubles': (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    'lhvi_mix_joint_map': (C.c_int, [_MX, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f64, _f64, _i32, _f64, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_mix_joint_map_host': (C.c_int, [_MX, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _i32, _vp, _vp, _i32, _f64, _f64, _i32, _f64, _vp, _vp, _vp, _vp]),
+    'lhvi_mix_prepare_host': (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_mix_condition_host': (C.c_int, [_MX, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_mix_marginal_map_host': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    'lhvi_mix_log_belief_host': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'lhvi_gibbs_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 

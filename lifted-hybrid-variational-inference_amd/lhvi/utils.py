@@ -31,6 +31,42 @@ def KL(q, p, domain):
     return total
 
 
+def softmax(a, axis=None):
+    """``osi/utils.py:21-34``: exp(a) / sum exp(a) along ``axis`` through scipy's logsumexp"""
+    from scipy.special import logsumexp
+    lse = logsumexp(a, axis=axis)
+    if axis is not None:
+        lse = np.expand_dims(lse, axis)
+    return np.exp(a - lse)
+
+
+def get_scalar_gm_mode(w, mu, var, bds, best_log_pdf=False, host=False):
+    """``osi/utils.py:66-98`` on the device: the mode of the scalar Gaussian mixture (w, mu, var) inside ``bds`` = (lb, ub), and
+    its log density with ``best_log_pdf``.  A safeguarded Newton iteration from every component mean instead of one bounded
+    ``scipy.optimize.minimize`` per mean (``lhvi_mix_marginal_map``, docs/kernels_mixture.md): a deviation in method, not in
+    result.  ``lhvi.mixture.MixtureBelief.marginal_map_all`` is the batched form."""
+    from .mixture import MixtureBelief
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    belief = MixtureBelief(w, np.asarray(mu, dtype=np.float64).reshape(1, -1), np.asarray(var, dtype=np.float64).reshape(1, -1),
+                           bds=np.asarray(bds, dtype=np.float64).reshape(2, 1))
+    x, f = belief.map_weights(w, [0], host=host)
+    return (float(x[0]), float(f[0])) if best_log_pdf else float(x[0])
+
+
+def get_multivar_gm_mode(log_w, Mu, Var, bds, init_xs=None, diagonal_cov=True, best_log_pdf=False, grad_lr=0.01, grad_its=500,
+                         tol=1e-7, host=False):
+    """``osi/utils.py:101-161`` on the device: the approximate mode of a Gaussian mixture with diagonal covariances (``Mu``, ``Var``
+    [N, K], log weights ``log_w``, ``bds`` [2, N]) by projected gradient ascent with Polyak averaging from each of ``init_xs``
+    [M, N] (default: the K component means), the best one kept, with its log density under ``best_log_pdf``
+    (``lhvi_mix_joint_map`` without discrete rows and one coordinate iteration, docs/kernels_mixture.md)."""
+    from .mixture import MixtureBelief
+    assert diagonal_cov, 'Currently assume diagonal covariance matrices!!!'
+    log_w = np.asarray(log_w, dtype=np.float64).reshape(-1)
+    belief = MixtureBelief(np.full(log_w.size, 1.0 / log_w.size), Mu, Var, bds=bds)
+    r = belief.joint_map(log_w=log_w, init_xs=init_xs, coord_its=1, grad_lr=grad_lr, grad_its=grad_its, tol=tol, host=host)
+    return (r['xc'], float(np.max(r['objs']))) if best_log_pdf else r['xc']
+
+
 def kl_discrete(p, q):
     """KL(p || q) of two probability tables of the same shape (utils.py:34-44)"""
     return np.sum(p * (np.log(p) - np.log(q)))

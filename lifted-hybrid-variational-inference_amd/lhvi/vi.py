@@ -480,6 +480,12 @@ class _Variational:
         x, f, it, st = self._cache[key]
         return (x, (f, it, st)) if info else x
 
+    def mixture_belief(self, normaliser='vi'):
+        """the fitted mixture as a ``lhvi.mixture.MixtureBelief``: conditional weights, marginal MAP and log beliefs for many
+        evidence rows at once, on the device, reading this solver's parameters in place"""
+        from .mixture import MixtureBelief
+        return MixtureBelief.from_solver(self, normaliser=normaliser)
+
     def rvs_map(self, rvs):
         """VI:378-456: coordinate ascent on the joint mixture belief"""
         from scipy.optimize import minimize
