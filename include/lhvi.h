@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 18  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 19  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -41,7 +41,8 @@ extern "C" {
                               * 15: lhvi_exact_t, lhvi_exact_*, LHVI_E_NOT_PD;
                               * 16: lhvi_gibbs_t, lhvi_gibbs_*;
                               * 17: lhvi_gauss_exact_*, LHVI_GAUSS_EXACT_NB;
-                              * 18: lhvi_mix_t, lhvi_mix_*, LHVI_MIX_* */
+                              * 18: lhvi_mix_t, lhvi_mix_*, LHVI_MIX_*;
+                              * 19: lhvi_gm_fit, lhvi_gm_fit_host, LHVI_GMFIT_MAX_K */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -866,6 +867,28 @@ int lhvi_mix_joint_map_host(const lhvi_mix_t* b, const double* logw, int32_t Nc,
                             const double* hi, int32_t Nd, const int32_t* drows, int32_t S, const double* x0, const int32_t* xd0,
                             int32_t coord_its, double gamma, double grad_lr, int32_t grad_its, double tol, double* ws, double* xc,
                             int32_t* xd, double* best_obj);
+
+/* ---- Scalar Gaussian mixtures fitted to samples by EM (sampling_utils.fit_scalar_gm_from_samples: scikit-learn's
+ * GaussianMixture(n_components=K, covariance_type='diag') on one column; csrc/gmfit.hip, csrc/gmfit.hpp,
+ * docs/kernels_gmfit.md) ----------------------------------------------------------------------------------------------------
+ * Every row of x [R][n] is fitted on its own, one workgroup per row, the whole fit in one launch.  Per row: y = x - mean(x);
+ * the start is init [R][3][K] = (w0, mu0, var0) or, with init NULL, deterministic: centres sd * Phi^-1((k + 1/2) / K), kmeans_its
+ * Lloyd iterations (an empty cluster keeps its centre), one M-step from the hard assignments.  Then at most max_iter EM
+ * iterations with scikit-learn's formulas (nk = sum r_k + 10 DBL_EPSILON, mu = sum r_k y / nk, var = sum r_k y^2 / nk - mu^2 +
+ * reg_covar, w = nk / n renormalised), stopped when |lower bound - previous| < tol (the first previous is -inf).  Outputs are
+ * the parameters after the M-step of the last iteration (mu with the mean added back), the last lower bound (the mean over
+ * the samples of logsumexp_k), the iterations done and flags: bit 0 converged, bit 1 the row holds a non-finite sample (its
+ * other outputs are then NaN / 0).  Sums are formed in a fixed order without atomics: a row's bits depend neither on R, nor on
+ * its position, nor on the run.  LHVI_E_ARG: R < 1, n < K, K < 1 or K > LHVI_GMFIT_MAX_K, max_iter < 1, kmeans_its < 0,
+ * reg_covar < 0 or NaN, a NULL array. */
+#define LHVI_GMFIT_MAX_K 16
+int lhvi_gm_fit(int32_t R, int64_t n, int32_t K, const double* x, const double* init, double reg_covar, double tol,
+                int32_t max_iter, int32_t kmeans_its, double* w, double* mu, double* var, double* lower_bound, int32_t* n_iter,
+                int32_t* flags, void* stream);
+/* the same on the HOST through the device's code (csrc/gmfit.hpp) with one "lane": every sum runs in index order */
+int lhvi_gm_fit_host(int32_t R, int64_t n, int32_t K, const double* x, const double* init, double reg_covar, double tol,
+                     int32_t max_iter, int32_t kmeans_its, double* w, double* mu, double* var, double* lower_bound,
+                     int32_t* n_iter, int32_t* flags);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 18            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 19            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -140,6 +140,7 @@ GAUSS_EXACT_NB = 64         # LHVI_GAUSS_EXACT_NB
 
 MIX_MAX_K, MIX_TILE, MIX_ROWS = 128, 64, 4     # LHVI_MIX_MAX_K / LHVI_MIX_TILE / LHVI_MIX_ROWS
 MIX_GAUSSIAN, MIX_VI = 0, 1                     # normaliser of lhvi_mix_prepare
+GMFIT_MAX_K = 16            # LHVI_GMFIT_MAX_K
 
 
 class MixStruct(C.Structure):
@@ -250,6 +251,8 @@ SIGNATURES = {
     'lhvi_mix_marginal_map_host': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     'lhvi_mix_log_belief_host': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'lhvi_gibbs_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gm_fit': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gm_fit_host': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

@@ -10,7 +10,9 @@ the tests).
 
 Deliberate differences (docs/kernels_gibbs.md): x_c is drawn as ``mu + L^-T z`` from the Cholesky factor of J instead of
 ``np.random.multivariate_normal`` (SVD of the covariance); the random numbers are a counter-based Philox stream instead of
-``drand48`` / NumPy's generator; ``HybridGaussianSampler.map`` of a discrete variable works.
+``drand48`` / NumPy's generator; ``HybridGaussianSampler.map`` of a discrete variable works.  ``GibbsHybridGaussian`` fits the
+mixtures of all continuous variables to the kept samples on the device (``fit_marginals``, ``lhvi/gmfit.py``);
+``fit_scalar_gm_from_samples`` and ``HybridGaussianSampler.map`` keep calling scikit-learn like the reference.
 """
 from __future__ import annotations
 
@@ -274,6 +276,21 @@ def fit_scalar_gm_from_samples(samples, K):
     return clf.weights_, np.ravel(clf.means_), np.ravel(clf.covariances_)
 
 
+def fit_scalar_gms_from_samples(samples, K, **fit_args):
+    """the batched sibling of ``fit_scalar_gm_from_samples``: a K-component mixture fitted to every column of ``samples``
+    [S, N] (an array or a device tensor, laid out like the reference's ``cont_samples``) in one launch.  Returns the
+    ``gmfit.ScalarMixtures`` of the N columns; ``fit_args``: the keywords of ``gmfit.fit_scalar_gms``."""
+    from .gmfit import fit_scalar_gms
+    if isinstance(samples, np.ndarray) or not hasattr(samples, 'data_ptr'):
+        samples = np.asarray(samples, dtype=np.float64)
+        if samples.ndim != 2:
+            raise ValueError('samples must be [S, N]')
+        return fit_scalar_gms(np.ascontiguousarray(samples.T), K, **fit_args)
+    if samples.dim() != 2:
+        raise ValueError('samples must be [S, N]')
+    return fit_scalar_gms(samples.t().contiguous(), K, **fit_args)
+
+
 class HybridGaussianSampler:
     """``hybrid_gaussian_mrf.HybridGaussianSampler`` (:268-302)"""
 
@@ -322,7 +339,8 @@ class GibbsHybridGaussian:
     """Sampled marginals of a hybrid Gaussian MRF from many independent block Gibbs chains.  ``GibbsHybridGaussian(g)`` or
     ``GibbsHybridGaussian(factors=, Vd=, Vc=)``; variables with ``rv.value`` set are evidence, potentials are converted as in
     ``ExactHybridGaussian``.  After ``run()``: ``disc_marginals()``, ``moments()``, ``rhat()``, ``map`` / ``map_all`` /
-    ``belief``, and with ``keep_samples`` ``disc_samples`` [chains, num_samples, Nd] / ``cont_samples``."""
+    ``belief``, and with ``keep_samples`` ``disc_samples`` [chains, num_samples, Nd] / ``cont_samples`` and
+    ``fit_marginals(K)``: the mixtures of the continuous variables fitted to the kept samples on the device."""
 
     def __init__(self, g=None, factors=None, Vd=None, Vc=None):
         if g is None and (factors is None or Vd is None or Vc is None):
@@ -332,6 +350,7 @@ class GibbsHybridGaussian:
         self.dstates, self.factors = ex.dstates, ex.factors
         self.model = GibbsModel(ex.model)
         self._run = None
+        self.marginals, self._fits = None, {}
 
     def run(self, chains=1024, num_burnin=100, num_samples=100, disc_block_its=100, seed=0, keep_samples=False, lanes=None,
             its_per_launch=None, init_x_d=None):
@@ -340,6 +359,7 @@ class GibbsHybridGaussian:
         self._run = r = _Chains(self.model, chains, num_burnin, num_samples, disc_block_its, _seed(seed), keep_samples, lanes,
                                 init_x_d=init_x_d).run(its_per_launch)
         self.chains, self.num_samples = r.chains, r.num_samples
+        self.marginals, self._fits = None, {}           # fits of an earlier run's samples
         self.counts = r.counts.cpu().numpy()
         self.sum1, self.sum2 = r.sum1.cpu().numpy(), r.sum2.cpu().numpy()
         self.disc_samples = r.disc.cpu().numpy() if keep_samples else None
@@ -404,27 +424,61 @@ class GibbsHybridGaussian:
         return types.SimpleNamespace(disc=[rd[off[i]:off[i + 1]] for i in range(len(self.Vd))], cont=rc,
                                      max=float(np.nanmax(both)) if both.size and not np.isnan(both).all() else float('nan'))
 
-    def map(self, rv):
+    def fit_marginals(self, K, **fit_args):
+        """Fit a K-component Gaussian mixture to the kept samples of every continuous variable in one launch
+        (``gmfit.fit_scalar_gms`` on the device tensor of the samples, transposed to [Nc, chains * num_samples]: they do not
+        visit the host).  Returns the ``gmfit.ScalarMixtures`` in ``Vc`` order and keeps it as ``self.marginals``, which
+        ``belief`` of a continuous variable reads.  Needs ``run(keep_samples=True)``."""
+        from .gmfit import fit_scalar_gms
+        r = self._need_run()
+        if r.cont is None:
+            raise RuntimeError('fit_marginals needs the kept samples: call run(keep_samples=True)')
+        Nc = len(self.Vc)
+        if Nc == 0:
+            raise ValueError('the model has no continuous variable')
+        x = r.cont.reshape(r.chains * r.num_samples, Nc).t().contiguous()
+        self.marginals = fit_scalar_gms(x, K, **fit_args)
+        if not fit_args:
+            self._fits[int(K)] = self.marginals
+        return self.marginals
+
+    def _bds(self):
+        return np.array([[rv.domain.values[0] for rv in self.Vc], [rv.domain.values[1] for rv in self.Vc]], dtype=np.float64)
+
+    def map(self, rv, num_gm_components_for_crv=1):
         """observed: its value; discrete: the state of largest sampled marginal; continuous: the sample mean clipped to the
-        domain (the one-component fit of ``HybridGaussianSampler.map``)"""
+        domain (the one-component fit of ``HybridGaussianSampler.map``) or, with ``num_gm_components_for_crv`` = K > 1, the
+        mode inside the domain of the K-component mixture fitted to the kept samples on the device (``fit_marginals(K)``
+        with its defaults, fitted once for all variables)"""
         if rv.value is not None:
             return rv.value
         self._need_run()
         if rv in self.Vd_idx:
             return rv.domain.values[int(np.argmax(self.disc_marginals()[self.Vd_idx[rv]][0]))]
+        K = int(num_gm_components_for_crv)
+        if K > 1:
+            fit = self._fits[K] if K in self._fits else self.fit_marginals(K)
+            return float(fit.modes(self._bds())[0][self.Vc_idx[rv]])
         mean = float(self.moments().mean[self.Vc_idx[rv]])
         return float(min(max(mean, rv.domain.values[0]), rv.domain.values[1]))
 
-    def map_all(self):
+    def map_all(self, num_gm_components_for_crv=1):
         """``map`` of every variable of ``self.rvs`` as an array"""
-        return np.array([float(self.map(rv)) for rv in self.rvs])
+        return np.array([float(self.map(rv, num_gm_components_for_crv)) for rv in self.rvs])
 
     def belief(self, x, rv):
-        """sampled marginal probability of the state x of a discrete variable"""
+        """sampled marginal probability of the state x of a discrete variable; for a continuous variable the density at x
+        (a number or an array) of its mixture of the last ``fit_marginals`` call"""
         if rv.value is not None:
             return 1 if x == rv.value else 0
         self._need_run()
         if rv not in self.Vd_idx:
-            raise NotImplementedError('belief is the sampled marginal of a discrete variable; see moments() for x_c')
+            if self.marginals is None:
+                raise NotImplementedError('belief of a continuous variable is the density of its fitted mixture: call '
+                                          'fit_marginals(K) first (or see moments())')
+            xs = np.asarray(x, dtype=np.float64)
+            out = self.marginals.pdf(xs.reshape(1, -1), rows=[self.Vc_idx[rv]])
+            out = (out if isinstance(out, np.ndarray) else out.cpu().numpy()).reshape(xs.shape)
+            return float(out) if xs.ndim == 0 else out
         vals = list(rv.domain.values)
         return float(self.disc_marginals()[self.Vd_idx[rv]][0][vals.index(x)]) if x in vals else 0.0
