@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 19  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 20  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -42,7 +42,8 @@ extern "C" {
                               * 16: lhvi_gibbs_t, lhvi_gibbs_*;
                               * 17: lhvi_gauss_exact_*, LHVI_GAUSS_EXACT_NB;
                               * 18: lhvi_mix_t, lhvi_mix_*, LHVI_MIX_*;
-                              * 19: lhvi_gm_fit, lhvi_gm_fit_host, LHVI_GMFIT_MAX_K */
+                              * 19: lhvi_gm_fit, lhvi_gm_fit_host, LHVI_GMFIT_MAX_K;
+                              * 20: lhvi_npvi_opt_t, lhvi_npvi_*, LHVI_NPVI_MAX_K, LHVI_NPVI_MAX_SLOTS, LHVI_VI_GAUSSIAN_PDF */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -512,7 +513,9 @@ typedef struct lhvi_vi {
     int32_t K;                  /* mixture components */
     int32_t T;                  /* Gauss-Hermite points */
     int32_t Dmax;               /* max #states of a discrete variable (row stride of eta_d) */
-    int32_t quirks;             /* 1 = reproduce VarInference.py:147-150 */
+    int32_t quirks;             /* 1 = reproduce VarInference.py:147-150; (ABI 20) | LHVI_VI_GAUSSIAN_PDF: lhvi_vi_map_bfgs
+                                 * evaluates the components as normal densities exp(-u^2 / 2 var) / sqrt(2 pi var) (an NPVI fit) instead of
+                                 * VarInference.norm_pdf's exp(-u^2 / 2 var) / (2.5066 var) */
     const double* gh_x;         /* [T] hermgauss nodes */
     const double* gh_w;         /* [T] weights / sqrt(pi) */
     const double* w;            /* [K] softmax(w_tau) */
@@ -545,6 +548,7 @@ typedef struct lhvi_vi {
      * depends on the graph and the evidence pattern only; NULL: the group kernels derive it per (factor, k) */
     const int32_t* edge_axis;
 } lhvi_vi_t;
+#define LHVI_VI_GAUSSIAN_PDF 2
 #define LHVI_VI_GROUP_SLOTS 24
 #define LHVI_VI_GROUP_COMP 48
 #define LHVI_VI_TINY_NODES 32
@@ -889,6 +893,64 @@ int lhvi_gm_fit(int32_t R, int64_t n, int32_t K, const double* x, const double* 
 int lhvi_gm_fit_host(int32_t R, int64_t n, int32_t K, const double* x, const double* init, double reg_covar, double tol,
                      int32_t max_iter, int32_t kmeans_its, double* w, double* mu, double* var, double* lower_bound,
                      int32_t* n_iter, int32_t* flags);
+
+/* ---- Nonparametric variational inference (osi/NPVI.py: Gershman-style NPVI on a K-component product mixture; csrc/npvi.hip,
+ * csrc/npvi.hpp, docs/kernels_npvi.md) -----------------------------------------------------------------------------------------
+ * Parameters: tau [K] (w = softmax(tau)), theta_c [V][K][2] = (mu, log var) of the hidden continuous variables, rho [V][K][Dmax]
+ * (pi = softmax(rho) over a hidden discrete variable's own states).  The lhvi_vi_t passed alongside is the parameter VIEW the
+ * kernels and every query read: K, T, gh_x, gh_w, Dmax, edge_axis (required) and w, eta_c = (mu, var), eta_d = pi, which the update
+ * keeps in step with tau / theta_c / rho.  obs_var must be NULL; quirks (LHVI_VI_GAUSSIAN_PDF for the queries) and the factor lists
+ * are not read.
+ * Objective (NPVI.py:133-159): obj = sum_f c_f sum_k w_k E_{q_k}[-log phi_f] (Gauss-Hermite on the factor's grid,
+ * mixture_beliefs.py:160-256 / :293-340 with neg_lpot_only) + sum_k w_k logsumexp_j(L[k][j] + log w_j), L[k][j] = sum_v c_v l_v(k, j)
+ * (the Jensen bound on the mixture entropy, :903-942).  The gradient is that of the reference's auxiliary objective: the grid
+ * nodes and node weights are constants (tf.stop_gradient), the factor term is differentiated through log b alone; the entropy
+ * term is differentiated fully.  Sums are formed in a fixed order without atomics: a run's bits do not depend on the run.
+ * A factor's axis lengths (T per hidden continuous argument, #states per hidden discrete one, 1 per observed one) must sum to at
+ * most LHVI_NPVI_MAX_SLOTS; a longer factor makes obj NaN (the caller checks: max_slots). */
+#define LHVI_NPVI_MAX_K 16
+#define LHVI_NPVI_MAX_SLOTS 24
+typedef struct lhvi_npvi_opt {
+    double* tau;                /* [K] mixture logits */
+    double* theta_c;            /* [V][K][2] (mu, log var) */
+    double* rho;                /* [V][K][Dmax] category logits */
+    double *m_tau, *s_tau, *m_c, *s_c, *m_rho, *s_rho;   /* Adam moments, shaped like tau / theta_c / rho */
+    double *g_tau, *g_c, *g_rho;/* gradient scratch, same shapes */
+    double* obj;                /* [1] scratch for the objective when it is not logged */
+    double* w;                  /* [K]: the arrays the lhvi_vi_t passed alongside points to (the step writes what the view reads) */
+    double* eta_c;              /* [V][K][2] (mu, var = exp(log var)) */
+    double* eta_d;              /* [V][K][Dmax] softmax(rho) */
+    const double* mu_lo;        /* [V] the variable's domain: mu is clipped to [mu_lo, mu_hi] after every step (NPVI.py:123) */
+    const double* mu_hi;        /* [V] */
+    double lvar_lo, lvar_hi;    /* log of Var_bds (NPVI.py:107,124) */
+    const double* var_count;    /* [V] sharing_count of the variables (cluster sizes), NULL = ones */
+    const double* fac_count;    /* [F] sharing_count of the factors, NULL = ones */
+    double lr, b1, b2, eps;     /* tf.train.AdamOptimizer: lr, 0.9, 0.999, 1e-8 */
+    int32_t t;                  /* updates done before this call (the step size uses t + i + 1) */
+    /* hints, 0 = unknown: the largest sum of axis lengths of a factor and the largest arity.  With max_arity <= 3 and no interpreted
+     * formula (lhvi_pots_t.interpreted == 0) the factor kernel's lean builds run (max_slots <= 8: the one with the smaller LDS
+     * tables).  A factor beyond a hint makes obj NaN. */
+    int32_t max_slots;
+    int32_t max_arity;
+} lhvi_npvi_opt_t;
+size_t lhvi_npvi_workspace_bytes(const lhvi_graph_t* g, const lhvi_vi_t* p);
+/* obj [1] and the gradient of the auxiliary objective at the view's parameters: g_tau [K] (through the softmax), g_c [V][K][2]
+ * (d/d mu, d/d log var; zero rows for other variables), g_rho [V][K][Dmax] (through the softmax; zero beyond a variable's states
+ * and for other variables).  LHVI_E_ARG: K < 1, K > LHVI_NPVI_MAX_K, T < 1, a NULL array (edge_axis included). */
+int lhvi_npvi_grad(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* var_count,
+                   const double* fac_count, int32_t max_slots, int32_t max_arity, double* obj, double* g_tau, double* g_c,
+                   double* g_rho, void* ws, size_t ws_bytes, void* stream);
+/* `iterations` updates (NPVI.run, NPVI.py:230-263) enqueued back to back, no host work in between: per update one gradient pass
+ * and ONE launch for TensorFlow's Adam on tau / rho / theta_c (lr_t = lr sqrt(1 - b2^t) / (1 - b1^t), theta -= lr_t m /
+ * (sqrt(v) + eps)), the clips of mu and log var, tau := 0 while the update's index < fix_mix_its (its moments keep running), both
+ * softmaxes and eta_c.  obj_log: device [iterations] or NULL -- obj_log[i] = the objective at the parameters before update i. */
+int lhvi_npvi_run(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const lhvi_npvi_opt_t* o, int32_t iterations,
+                  int32_t fix_mix_its, double* obj_log, void* ws, size_t ws_bytes, void* stream);
+/* the same on the HOST through the device's code (csrc/npvi.hpp) with one "lane": every pointer is host memory, sums run in index order */
+int lhvi_npvi_grad_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* var_count,
+                        const double* fac_count, double* obj, double* g_tau, double* g_c, double* g_rho);
+int lhvi_npvi_run_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const lhvi_npvi_opt_t* o,
+                       int32_t iterations, int32_t fix_mix_its, double* obj_log);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

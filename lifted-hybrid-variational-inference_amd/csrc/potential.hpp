@@ -19,6 +19,9 @@
 #pragma once
 #include "common.hpp"
 
+// the evaluators below also run on the host (the host twins of csrc/npvi.hpp call pot_eval_on with one "lane")
+#define LHVI_POT_HD __host__ __device__ __forceinline__
+
 namespace lhvi {
 
 constexpr int MLN_STACK = 12;
@@ -27,8 +30,8 @@ constexpr int MLN_STACK = 12;
 // waterfall) or a column of LDS (slot i of thread t at base[i * stride]: two instructions per access)
 struct MlnRegStack {
     double v[MLN_STACK];
-    __device__ __forceinline__ double get(int i) const { return v[i]; }
-    __device__ __forceinline__ void set(int i, double x) { v[i] = x; }
+    LHVI_POT_HD double get(int i) const { return v[i]; }
+    LHVI_POT_HD void set(int i, double x) { v[i] = x; }
 };
 template <int STRIDE>
 struct MlnLdsStack {
@@ -38,7 +41,7 @@ struct MlnLdsStack {
 };
 
 template <class Stack>
-__device__ __forceinline__ double mln_formula_on(const double* __restrict__ code, int ncode, const double* x, Stack& st) {
+LHVI_POT_HD double mln_formula_on(const double* __restrict__ code, int ncode, const double* x, Stack& st) {
     int sp = 0;
     for (int i = 0; i < ncode; ++i) {
         const int op = (int)code[2 * i];
@@ -74,7 +77,7 @@ __device__ __forceinline__ double mln_formula_on(const double* __restrict__ code
 // coef[ncfg][6]] (lhvi/expr.py::cq_block): cfg = mixed-radix index of the discrete arguments' states (first one most
 // significant), (u, v) = the continuous arguments in argument order, log phi = (a00 u + axy v + b0) u + (a11 v + b1) v + c.
 // Straight-line: no opcode fetch, no evaluation stack.  idx[a] = state index of a discrete argument.
-__device__ __forceinline__ double cq_log_phi(const double* __restrict__ b, const double* x, const int* idx) {
+LHVI_POT_HD double cq_log_phi(const double* __restrict__ b, const double* x, const int* idx) {
     const int arity = (int)b[1], Nd = (int)b[2];
     const double* __restrict__ role = b + 4;
     const double* __restrict__ dims = role + arity;
@@ -98,7 +101,7 @@ __device__ __forceinline__ double mln_formula(const double* __restrict__ code, i
     return mln_formula_on(code, ncode, x, st);
 }
 
-__device__ __forceinline__ double quad_form(const double* __restrict__ A, const double* __restrict__ b, double c,
+LHVI_POT_HD double quad_form(const double* __restrict__ A, const double* __restrict__ b, double c,
                                             int n, const double* x) {
     double res = 0.0;
     for (int i = 0; i < n; ++i) {
@@ -114,7 +117,7 @@ __device__ __forceinline__ double quad_form(const double* __restrict__ A, const 
 // INTERP = false: the build for graphs without an interpreted formula (every MLN row carries a conditional-quadratic block, no
 // hard formula: lhvi_pots_t.interpreted == 0) -- the bytecode loop and its evaluation stack are not compiled in.
 template <bool INTERP = true, class Stack>
-__device__ __forceinline__ double pot_eval_on(int kind, const double* __restrict__ par, const double* x, const int* idx,
+LHVI_POT_HD double pot_eval_on(int kind, const double* __restrict__ par, const double* x, const int* idx,
                                               bool& is_log, Stack& st) {
     is_log = true;
     switch (kind) {
@@ -182,8 +185,8 @@ __device__ __forceinline__ double pot_eval_on(int kind, const double* __restrict
 }
 
 struct MlnNoStack {        // the INTERP = false builds: nothing to hold
-    __device__ __forceinline__ double get(int) const { return 0.0; }
-    __device__ __forceinline__ void set(int, double) {}
+    LHVI_POT_HD double get(int) const { return 0.0; }
+    LHVI_POT_HD void set(int, double) {}
 };
 
 template <bool INTERP = true>

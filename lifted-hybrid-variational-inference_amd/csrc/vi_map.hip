@@ -26,13 +26,14 @@ struct Row {
     const double* w;
     const double* eta;
     int K;
+    bool gauss;     // lhvi_vi_t.quirks & LHVI_VI_GAUSSIAN_PDF: the components are normal densities (an NPVI fit)
 };
 
 // b[k] = w[k] * norm_pdf(x, eta[k]) (VarInference.py:26-30, 346-348): np.e ** (-u * u * 0.5 / var) / (2.506628274631 * var)
 VM_HD double term(const Row& r, int k, double x) {
     const double mu = r.eta[2 * k], var = r.eta[2 * k + 1];
     const double u = x - mu;
-    return r.w[k] * (pow_e_np(-u * u * 0.5 / var) / (2.506628274631 * var));
+    return r.w[k] * (pow_e_np(-u * u * 0.5 / var) / (2.506628274631 * (r.gauss ? sqrt(var) : var)));
 }
 
 // np.sum(b) (VarInference.py:353): sequential below 8 terms, else numpy's pairwise block -- eight running sums, combined as
@@ -335,7 +336,7 @@ __global__ void __launch_bounds__(BLOCK) vi_map_bfgs_kernel(lhvi_graph_t g, lhvi
     if (v >= 0 && v < g.V && is_hidden(g.var_value[v])) {
         const int d = g.var_dom[v];
         if (g.dom_cont[d]) {
-            const vimap::Row row{p.w, p.eta_c + (int64_t)v * p.K * 2, p.K};
+            const vimap::Row row{p.w, p.eta_c + (int64_t)v * p.K * 2, p.K, (p.quirks & LHVI_VI_GAUSSIAN_PDF) != 0};
             const vimap::Result r = vimap::map_continuous(row, gtol, maxiter);
             x = r.x; f = -r.fun; it = r.nit; st = r.status;
         } else {

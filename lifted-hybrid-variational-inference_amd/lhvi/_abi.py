@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 19            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 20            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -141,6 +141,15 @@ GAUSS_EXACT_NB = 64         # LHVI_GAUSS_EXACT_NB
 MIX_MAX_K, MIX_TILE, MIX_ROWS = 128, 64, 4     # LHVI_MIX_MAX_K / LHVI_MIX_TILE / LHVI_MIX_ROWS
 MIX_GAUSSIAN, MIX_VI = 0, 1                     # normaliser of lhvi_mix_prepare
 GMFIT_MAX_K = 16            # LHVI_GMFIT_MAX_K
+VI_GAUSSIAN_PDF = 2         # LHVI_VI_GAUSSIAN_PDF (lhvi_vi_t.quirks)
+NPVI_MAX_K, NPVI_MAX_SLOTS = 16, 24             # LHVI_NPVI_MAX_K / LHVI_NPVI_MAX_SLOTS
+
+
+class NpviOptStruct(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ('tau', 'theta_c', 'rho', 'm_tau', 's_tau', 'm_c', 's_c', 'm_rho', 's_rho', 'g_tau', 'g_c',
+                                          'g_rho', 'obj', 'w', 'eta_c', 'eta_d', 'mu_lo', 'mu_hi')] + \
+               [('lvar_lo', C.c_double), ('lvar_hi', C.c_double), ('var_count', C.c_void_p), ('fac_count', C.c_void_p)] + \
+               [(n, C.c_double) for n in ('lr', 'b1', 'b2', 'eps')] + [('t', C.c_int32), ('max_slots', C.c_int32), ('max_arity', C.c_int32)]
 
 
 class MixStruct(C.Structure):
@@ -154,6 +163,7 @@ LBFGSB_FUN = C.CFUNCTYPE(C.c_double, C.POINTER(C.c_double), C.c_void_p)
 _G, _P, _S, _VI = C.POINTER(GraphStruct), C.POINTER(PotsStruct), C.POINTER(PbpStruct), C.POINTER(ViStruct)
 _GP = C.POINTER(GabpPlanStruct)
 _MX = C.POINTER(MixStruct)
+_NO = C.POINTER(NpviOptStruct)
 _vp, _i32, _i64, _u32, _u64, _f64, _sz = C.c_void_p, C.c_int32, C.c_int64, C.c_uint32, C.c_uint64, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); must list every symbol include/lhvi.h declares (tests/test_abi.py checks)
@@ -253,6 +263,11 @@ SIGNATURES = {
     'lhvi_gibbs_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit_host': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_npvi_workspace_bytes': (_sz, [_G, _VI]),
+    'lhvi_npvi_grad': (C.c_int, [_G, _P, _VI, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    'lhvi_npvi_run': (C.c_int, [_G, _P, _VI, _NO, _i32, _i32, _vp, _vp, _sz, _vp]),
+    'lhvi_npvi_grad_host': (C.c_int, [_G, _P, _VI, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_npvi_run_host': (C.c_int, [_G, _P, _VI, _NO, _i32, _i32, _vp]),
 }
 
 _lib = None

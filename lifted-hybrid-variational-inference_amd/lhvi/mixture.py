@@ -134,12 +134,16 @@ class MixtureBelief:
         self._row_of = None
 
     @classmethod
-    def from_solver(cls, vi, normaliser='vi'):
+    def from_solver(cls, vi, normaliser=None):
         """The belief of a fitted ``VarInference`` / ``LiftedVarInference`` / ``C2FVarInference``: its device tensors are read in
         place (nothing is expanded: a lifted solver's rows are its clusters, and ``row(rv)`` goes through ``rv.cluster``).  Rows
         that were evidence when the solver ran have no parameters: naming one in ``obs`` raises ``ValueError``, as a query it
-        returns its value.  With ``normaliser='vi'`` and no evidence ``log_belief_all`` is ``log vi.belief(x, rv)``.  The
+        returns its value.  ``normaliser`` defaults to the solver's ``belief_normaliser`` ('vi'; 'gaussian' for ``NPVI``).  With ``normaliser='vi'`` and no evidence ``log_belief_all`` is ``log vi.belief(x, rv)``.  The
         records are prepared now: call again after further updates of the solver."""
+        if normaliser is None:                       # the density the solver fitted: VarInference's own, NPVI's normal one
+            normaliser = getattr(vi, 'belief_normaliser', 'vi')
+        if hasattr(vi, '_ensure_dev'):               # (a solver that keeps host copies: bring its device arrays up to date)
+            vi._ensure_dev()
         if vi._dev is None:
             raise RuntimeError('the solver has no parameters yet: call init_param() or run() first')
         cls._check_K(vi.K)
