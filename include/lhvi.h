@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 20  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 21  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -43,7 +43,8 @@ extern "C" {
                               * 17: lhvi_gauss_exact_*, LHVI_GAUSS_EXACT_NB;
                               * 18: lhvi_mix_t, lhvi_mix_*, LHVI_MIX_*;
                               * 19: lhvi_gm_fit, lhvi_gm_fit_host, LHVI_GMFIT_MAX_K;
-                              * 20: lhvi_npvi_opt_t, lhvi_npvi_*, LHVI_NPVI_MAX_K, LHVI_NPVI_MAX_SLOTS, LHVI_VI_GAUSSIAN_PDF */
+                              * 20: lhvi_npvi_opt_t, lhvi_npvi_*, LHVI_NPVI_MAX_K, LHVI_NPVI_MAX_SLOTS, LHVI_VI_GAUSSIAN_PDF;
+                              * 21: lhvi_oneshot_* */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -951,6 +952,30 @@ int lhvi_npvi_grad_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lh
                         const double* fac_count, double* obj, double* g_tau, double* g_c, double* g_rho);
 int lhvi_npvi_run_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const lhvi_npvi_opt_t* o,
                        int32_t iterations, int32_t fix_mix_its, double* obj_log);
+
+/* ---- OneShot (osi/OneShot.py: the same K-component product mixture fitted to the Bethe free energy; csrc/oneshot.hip,
+ * csrc/oneshot.hpp, docs/kernels_oneshot.md) ------------------------------------------------------------------------------------
+ * Parameters, parameter view, lhvi_npvi_opt_t, limits (LHVI_NPVI_MAX_K, LHVI_NPVI_MAX_SLOTS), hints and the update are NPVI's.
+ * Objective (OneShot.py:53-150): obj = sum_f c_f E_b[-log phi_f + log b_f] (the factor grid of NPVI with log b inside the expectant,
+ * mixture_beliefs.py:160-256 / :293-340 with neg_lpot_only=False) + sum_v var_coef[v] E_b[log b_v] (:441-502; Gauss-Hermite at the K * T
+ * nodes of a continuous variable, the states of a discrete one).  var_coef [V], required: c_v (1 - deg_v) for a hidden variable --
+ * c_v its sharing count, deg_v the number of ground factors a (member) variable touches -- and 0 for an observed one; rows with 0
+ * are not evaluated.  The gradient is that of the reference's auxiliary objective: nodes, node weights and the expectant are
+ * constants, both terms are differentiated through log b alone.  Fixed-order sums, no atomics.
+ * LHVI_E_ARG: as for lhvi_npvi_*, and a NULL var_coef. */
+size_t lhvi_oneshot_workspace_bytes(const lhvi_graph_t* g, const lhvi_vi_t* p);
+int lhvi_oneshot_grad(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* var_count,
+                      const double* fac_count, const double* var_coef, int32_t max_slots, int32_t max_arity, double* obj, double* g_tau,
+                      double* g_c, double* g_rho, void* ws, size_t ws_bytes, void* stream);
+/* `iterations` updates (OneShot.run, OneShot.py:221-254: the loop of NPVI.run) enqueued back to back; obj_log as in lhvi_npvi_run */
+int lhvi_oneshot_run(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const lhvi_npvi_opt_t* o,
+                     const double* var_coef, int32_t iterations, int32_t fix_mix_its, double* obj_log, void* ws, size_t ws_bytes,
+                     void* stream);
+/* the same on the HOST through the device's code (csrc/npvi.hpp, csrc/oneshot.hpp) with one "lane": host pointers, sums in index order */
+int lhvi_oneshot_grad_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* var_count,
+                           const double* fac_count, const double* var_coef, double* obj, double* g_tau, double* g_c, double* g_rho);
+int lhvi_oneshot_run_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const lhvi_npvi_opt_t* o,
+                          const double* var_coef, int32_t iterations, int32_t fix_mix_its, double* obj_log);
 
 /* ---- Colour refinement (CompressedGraphWithObs.py / CompressedGraphSorted.py) --------------------
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct

@@ -1,5 +1,6 @@
 // npvi.hip -- nonparametric variational inference (osi/NPVI.py) on gfx950; the arithmetic is csrc/npvi.hpp's, shared with the host
-// twins at the end of this file.  docs/kernels_npvi.md.
+// twins at the end of this file.  docs/kernels_npvi.md.  The factor and gather kernels, the block reduction and the argument checks
+// live in csrc/npvi_dev.hpp, which csrc/oneshot.hip shares; the other kernels are defined here.
 //   npvi_factor_kernel<KP, SL, MA, INTERP>
 //                               a group of KP lanes per factor, lane m = mixture component m (KP = K rounded up to 1, 2, 4, 16): every
 //                               lane walks the factor's K grids, the group adds the lanes' terms of the belief at each node with
@@ -15,84 +16,10 @@
 //   npvi_gather_kernel          a thread per (variable, k): its edges' partials in rv.nb order, the entropy gradient through
 //                               S + S^T, the softmax chain of a discrete row;  npvi_gather_hub_kernel: a wavefront per (hub, k)
 //   npvi_update_kernel          TensorFlow's Adam on tau / rho / (mu, log var), clips, fix_mix reset, softmaxes, eta_c
-#include "common.hpp"
-#include "npvi.hpp"
+#include "npvi_dev.hpp"
 
 namespace lhvi {
 namespace npvi {
-
-template <bool INTERP, int BLK> struct DevStack { using type = MlnLdsStack<BLK>; static constexpr int DOUBLES = MLN_STACK * BLK; };
-template <int BLK> struct DevStack<false, BLK> { using type = MlnNoStack; static constexpr int DOUBLES = 1; };
-constexpr int PT = MAXA + 1;        // doubles / ints per lane for the evaluation point (odd: neighbouring lanes on different banks)
-
-template <int KP, int SL, int BLK, bool INTERP>
-struct DevCtx {
-    static constexpr int NM = 1;
-    static constexpr int GROUPS = BLK / KP;
-    int gl, gn;
-    double* xt;     // [SL][GROUPS] + group
-    double* ct;
-    double* qt;     // [SL][BLK] + thread
-    double* zt;
-    double* px;     // [BLK][PT] + thread * PT
-    int* pi;
-    typename DevStack<INTERP, BLK>::type st;
-    __device__ __forceinline__ double* point() { return px; }
-    __device__ __forceinline__ int* point_idx() { return pi; }
-    __device__ __forceinline__ typename DevStack<INTERP, BLK>::type& stack() { return st; }
-    __device__ __forceinline__ int m(int) const { return gl; }
-    __device__ __forceinline__ double& x(int s) { return xt[s * GROUPS]; }
-    __device__ __forceinline__ double& c(int s) { return ct[s * GROUPS]; }
-    __device__ __forceinline__ double& q(int, int s) { return qt[s * BLK]; }
-    __device__ __forceinline__ double& z(int, int s) { return zt[s * BLK]; }
-    __device__ __forceinline__ double sum_m(double v) const {
-#pragma unroll
-        for (int d = 1; d < KP; d <<= 1) v += __shfl_xor(v, d, 64);
-        return v;
-    }
-    __device__ __forceinline__ void sync() const {
-        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-    }
-};
-
-template <int SL> struct FacBlock { static constexpr int value = SL <= 8 ? 128 : 64; };
-
-template <int KP, int SL, int MA, bool INTERP>
-__global__ void __launch_bounds__(FacBlock<SL>::value) npvi_factor_kernel(lhvi_graph_t g, lhvi_pots_t pots, lhvi_vi_t p,
-                                                                          const double* __restrict__ fac_count, double* __restrict__ pe_c,
-                                                                          double* __restrict__ pe_d, double* __restrict__ pf) {
-    constexpr int BLK = FacBlock<SL>::value;
-    using Ctx = DevCtx<KP, SL, BLK, INTERP>;
-    __shared__ double sh_x[SL * Ctx::GROUPS], sh_c[SL * Ctx::GROUPS], sh_q[SL * BLK], sh_z[SL * BLK], sh_px[PT * BLK];
-    __shared__ double sh_st[DevStack<INTERP, BLK>::DOUBLES];
-    __shared__ int sh_pi[PT * BLK];
-    const int grp = threadIdx.x / KP;
-    const int64_t f = (int64_t)blockIdx.x * Ctx::GROUPS + grp;
-    if (f >= g.F) return;                            // (whole groups leave together)
-    Ctx ctx{(int)threadIdx.x % KP, KP, sh_x + grp, sh_c + grp, sh_q + threadIdx.x, sh_z + threadIdx.x, sh_px + threadIdx.x * PT,
-            sh_pi + threadIdx.x * PT, {}};
-    if constexpr (INTERP) ctx.st.base = sh_st + threadIdx.x;
-    factor_item<MA, INTERP, SL>(g, pots, p, fac_count, (int)f, ctx, pe_c, pe_d, pf);
-}
-
-constexpr int NP_MAX = MAX_K * (MAX_K + 1) / 2;
-constexpr int COLS_MAX = NP_MAX > MAX_K + 1 ? NP_MAX : MAX_K + 1;
-constexpr int WAVES = BLOCK / WAVE;
-
-// the workgroup's total of column `col` of the threads' values -> sh[wave][col]; block_cols_flush then adds the waves in index order
-__device__ __forceinline__ void block_col_put(double* sh, int C, int col, double v) {
-    const double t = dpp_wave_reduce(v, SumOp());
-    if (threadIdx.x % WAVE == 0) sh[(threadIdx.x / WAVE) * C + col] = t;
-}
-__device__ __forceinline__ void block_cols_flush(const double* sh, int C, double* __restrict__ out) {
-    __syncthreads();
-    for (int col = threadIdx.x; col < C; col += BLOCK) {
-        double t = sh[col];
-        for (int wv = 1; wv < WAVES; ++wv) t += sh[wv * C + col];
-        out[col] = t;
-    }
-}
 
 __global__ void __launch_bounds__(BLOCK) npvi_colsum_kernel(const double* __restrict__ in, int64_t N, int C, double* __restrict__ part) {
     __shared__ double sh[WAVES * COLS_MAX];
@@ -141,68 +68,11 @@ __global__ void __launch_bounds__(BLOCK) npvi_weights_kernel(lhvi_vi_t p, const 
     if (threadIdx.x == 0) finish_weights(K, tot, p.w, lse, U, SS, obj, g_tau);
 }
 
-__global__ void __launch_bounds__(BLOCK) npvi_gather_kernel(lhvi_graph_t g, lhvi_vi_t p, const double* __restrict__ var_count,
-                                                            const double* __restrict__ SS, const double* __restrict__ pe_c,
-                                                            const double* __restrict__ pe_d, double* __restrict__ g_c,
-                                                            double* __restrict__ g_rho) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
-    if (i >= (int64_t)g.V * p.K) return;
-    const int v = (int)(i / p.K), m = (int)(i % p.K);
-    const int lo = g.var_ptr[v], hi = g.var_ptr[v + 1];
-    if (g.n_hubs > 0 && hi - lo > LHVI_HUB_DEGREE) return;          // a wavefront's (npvi_gather_hub_kernel)
-    const VarInfo vi = var_info(g, v);
-    double c0 = 0.0, c1 = 0.0;
-    if (vi.hidden && vi.cont) {
-        for (int j = lo; j < hi; ++j) {
-            const double2 t = ld2(pe_c, (int64_t)g.var_edge[j] * p.K + m);
-            c0 += t.x; c1 += t.y;
-        }
-    } else if (vi.hidden) {
-        for (int t = 0; t < vi.n; ++t) {
-            double s = 0.0;
-            for (int j = lo; j < hi; ++j) s += pe_d[((int64_t)g.var_edge[j] * p.K + m) * p.Dmax + t];
-            g_rho[i * p.Dmax + t] = s;
-        }
-    }
-    gather_finish(g, p, var_count, SS, v, m, vi, c0, c1, g_c, g_rho);
-}
-
-__global__ void __launch_bounds__(BLOCK) npvi_gather_hub_kernel(lhvi_graph_t g, lhvi_vi_t p, const double* __restrict__ var_count,
-                                                                const double* __restrict__ SS, const double* __restrict__ pe_c,
-                                                                const double* __restrict__ pe_d, double* __restrict__ g_c,
-                                                                double* __restrict__ g_rho) {
-    const int64_t item = ((int64_t)blockIdx.x * BLOCK + threadIdx.x) / WAVE;
-    const int lane = threadIdx.x % WAVE;
-    if (item >= (int64_t)g.n_hubs * p.K) return;                    // (whole wavefronts)
-    const int v = g.hub_vars[item / p.K], m = (int)(item % p.K);
-    const int lo = g.var_ptr[v], hi = g.var_ptr[v + 1];
-    const VarInfo vi = var_info(g, v);
-    double c0 = 0.0, c1 = 0.0;
-    if (vi.hidden && vi.cont) {
-        for (int j = lo + lane; j < hi; j += WAVE) {
-            const double2 t = ld2(pe_c, (int64_t)g.var_edge[j] * p.K + m);
-            c0 += t.x; c1 += t.y;
-        }
-        c0 = dpp_wave_reduce(c0, SumOp());
-        c1 = dpp_wave_reduce(c1, SumOp());
-    } else if (vi.hidden) {
-        for (int t = 0; t < vi.n; ++t) {
-            double s = 0.0;
-            for (int j = lo + lane; j < hi; j += WAVE) s += pe_d[((int64_t)g.var_edge[j] * p.K + m) * p.Dmax + t];
-            s = dpp_wave_reduce(s, SumOp());
-            if (lane == 0) g_rho[((int64_t)v * p.K + m) * p.Dmax + t] = s;
-        }
-    }
-    if (lane == 0) gather_finish(g, p, var_count, SS, v, m, vi, c0, c1, g_c, g_rho);
-}
-
 __global__ void __launch_bounds__(BLOCK) npvi_update_kernel(lhvi_graph_t g, int K, int Dmax, lhvi_npvi_opt_t o, Step a) {
     const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     if (i == 0) update_tau(K, o, a);
     if (i < (int64_t)g.V * K) update_row(g, K, Dmax, o, a, (int)(i / K), (int)(i % K));
 }
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 struct Layout { size_t pe_c, pe_d, pf, partF, partV, SS, total; int nbF, nbV; };
 static Layout layout(const lhvi_graph_t* g, const lhvi_vi_t* p) {
@@ -220,41 +90,6 @@ static Layout layout(const lhvi_graph_t* g, const lhvi_vi_t* p) {
     return l;
 }
 
-static int check_args(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* obj, const double* g_tau,
-                      const double* g_c, const double* g_rho) {
-    if (!g || !pots || !p || !obj || !g_tau || !g_c || !g_rho) return LHVI_E_ARG;
-    if (p->K < 1 || p->K > LHVI_NPVI_MAX_K || p->T < 1 || p->Dmax < 1 || g->V < 1 || g->F < 0) return LHVI_E_ARG;
-    if (!p->gh_x || !p->gh_w || !p->w || !p->eta_c || !p->eta_d || (g->E > 0 && !p->edge_axis) || p->obs_var) return LHVI_E_ARG;
-    return LHVI_OK;
-}
-
-static int check_opt(const lhvi_npvi_opt_t* o, int32_t iterations) {
-    if (!o || iterations < 0) return LHVI_E_ARG;
-    if (!o->tau || !o->theta_c || !o->rho || !o->m_tau || !o->s_tau || !o->m_c || !o->s_c || !o->m_rho || !o->s_rho || !o->g_tau ||
-        !o->g_c || !o->g_rho || !o->obj || !o->w || !o->eta_c || !o->eta_d || !o->mu_lo || !o->mu_hi)
-        return LHVI_E_ARG;
-    return LHVI_OK;
-}
-
-static Step make_step(const lhvi_npvi_opt_t* o, int it, int32_t fix_mix_its) {
-    const double t = (double)(o->t + it + 1);
-    return Step{o->lr * sqrt(1.0 - pow(o->b2, t)) / (1.0 - pow(o->b1, t)), o->b1, o->b2, o->eps, it < fix_mix_its ? 1 : 0};
-}
-
-template <int SL, int MA, bool INTERP>
-static void launch_factors(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* fac_count, double* pe_c,
-                           double* pe_d, double* pf, hipStream_t st) {
-    constexpr int BLK = FacBlock<SL>::value;
-#define LHVI_NPVI_LAUNCH(KP) \
-    hipLaunchKernelGGL((npvi_factor_kernel<KP, SL, MA, INTERP>), dim3(grid_for(g->F, BLK / KP)), dim3(BLK), 0, st, *g, *pots, *p, \
-                       fac_count, pe_c, pe_d, pf)
-    if (p->K == 1) LHVI_NPVI_LAUNCH(1);
-    else if (p->K == 2) LHVI_NPVI_LAUNCH(2);
-    else if (p->K <= 4) LHVI_NPVI_LAUNCH(4);
-    else LHVI_NPVI_LAUNCH(16);
-#undef LHVI_NPVI_LAUNCH
-}
-
 static int grad_device(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* var_count,
                        const double* fac_count, int32_t max_slots, int32_t max_arity, double* obj, double* g_tau, double* g_c,
                        double* g_rho, void* ws, hipStream_t st) {
@@ -267,18 +102,15 @@ static int grad_device(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhv
     double* partV = reinterpret_cast<double*>(b + l.partV);
     double* SS = reinterpret_cast<double*>(b + l.SS);
     if (g->F > 0) {
-        const bool lean = pots->interpreted == 0 && max_arity > 0 && max_arity <= 3;
-        if (lean && max_slots > 0 && max_slots <= 8) launch_factors<8, 3, false>(g, pots, p, fac_count, pe_c, pe_d, pf, st);
-        else if (lean) launch_factors<SLOTS, 3, false>(g, pots, p, fac_count, pe_c, pe_d, pf, st);
-        else launch_factors<SLOTS, MAXA, true>(g, pots, p, fac_count, pe_c, pe_d, pf, st);
+        launch_factor_build<false>(g, pots, p, fac_count, max_slots, max_arity, pe_c, pe_d, pf, st);
         hipLaunchKernelGGL(npvi_colsum_kernel, dim3(l.nbF), dim3(BLOCK), 0, st, pf, (int64_t)g->F, p->K + 1, partF);
     }
     hipLaunchKernelGGL(npvi_entropy_kernel, dim3(l.nbV), dim3(BLOCK), 0, st, *g, *p, var_count, partV);
     hipLaunchKernelGGL(npvi_weights_kernel, dim3(1), dim3(BLOCK), 0, st, *p, partF, g->F > 0 ? l.nbF : 0, partV, l.nbV, SS, obj, g_tau);
-    hipLaunchKernelGGL(npvi_gather_kernel, dim3(grid_for((int64_t)g->V * p->K)), dim3(BLOCK), 0, st, *g, *p, var_count, SS, pe_c, pe_d,
+    hipLaunchKernelGGL(npvi_gather_kernel<false>, dim3(grid_for((int64_t)g->V * p->K)), dim3(BLOCK), 0, st, *g, *p, var_count, SS, pe_c, pe_d,
                        g_c, g_rho);
     if (g->n_hubs > 0)
-        hipLaunchKernelGGL(npvi_gather_hub_kernel, dim3(grid_for((int64_t)g->n_hubs * p->K * WAVE)), dim3(BLOCK), 0, st, *g, *p,
+        hipLaunchKernelGGL(npvi_gather_hub_kernel<false>, dim3(grid_for((int64_t)g->n_hubs * p->K * WAVE)), dim3(BLOCK), 0, st, *g, *p,
                            var_count, SS, pe_c, pe_d, g_c, g_rho);
     return check_launch();
 }

@@ -82,8 +82,9 @@ LHVI_HD T* opaque_ptr(T* q) {
 
 // pe_c [E][K][2], pe_d [E][K][Dmax], pf [F][K + 1] (d aux / d w_m of the factor, then its objective)
 // MA, SCAP: the arity and the slots this build serves (a longer factor is reported through its objective); INTERP: formulas without a
-// conditional-quadratic block are interpreted (lhvi_pots_t.interpreted != 0)
-template <int MA, bool INTERP, int SCAP, class Ctx>
+// conditional-quadratic block are interpreted (lhvi_pots_t.interpreted != 0); BFE: the expectant is -log phi + log b (OneShot's Bethe
+// free energy, csrc/oneshot.hip) instead of -log phi
+template <int MA, bool INTERP, int SCAP, bool BFE = false, class Ctx>
 LHVI_HD void factor_item(const lhvi_graph_t& g, const lhvi_pots_t& pots, const lhvi_vi_t& p, const double* __restrict__ fac_count,
                          int f, Ctx& ctx, double* pe_c, double* pe_d, double* pf) {
     constexpr int NM = Ctx::NM;
@@ -201,9 +202,9 @@ LHVI_HD void factor_item(const lhvi_graph_t& g, const lhvi_pots_t& pots, const l
                 coef *= ctx.c(off[a] + it[a]);
                 idx[a] = NPVI_HID(a) ? (NPVI_CONT(a) ? 0 : it[a]) : fix[a];
             }
-            const double F = neg_log_phi<INTERP>(kind, par, x, idx, ctx.stack());
-            const double omega = (wk * coef) * F;
-            obj += omega;
+            double F = neg_log_phi<INTERP>(kind, par, x, idx, ctx.stack());
+            double omega = (wk * coef) * F;
+            if constexpr (!BFE) obj += omega;
             double pm[NM], loo[NM][MA];
             double mine = 0.0;
 #pragma unroll
@@ -224,6 +225,11 @@ LHVI_HD void factor_item(const lhvi_graph_t& g, const lhvi_pots_t& pots, const l
                 mine += p.w[m] * pre;
             }
             const double b = ctx.sum_m(mine);
+            if constexpr (BFE) {            // every lane has b now: the expectant takes log b in
+                F += log(b);
+                omega = (wk * coef) * F;
+                obj += omega;
+            }
             const double rb = omega / b;
 #pragma unroll
             for (int i = 0; i < NM; ++i) {
@@ -349,7 +355,9 @@ LHVI_HD void finish_weights(int K, const double* tot, const double* w, const dou
 }
 
 // the gradient rows of (v, m) from the sums over the variable's edges: c0, c1 (continuous) or the raw d / d pi already in
-// g_rho[v][m][:] (discrete); adds the entropy term through SS and chains a discrete row through its softmax
+// g_rho[v][m][:] (discrete); adds the entropy term through SS and chains a discrete row through its softmax.
+// BFE: SS is instead the variable term's rows (oneshot.hpp's var_item), [V][K][2] followed by [V][K][Dmax], added as they stand
+template <bool BFE = false>
 LHVI_HD void gather_finish(const lhvi_graph_t& g, const lhvi_vi_t& p, const double* __restrict__ var_count, const double* __restrict__ SS,
                            int v, int m, const VarInfo& vi, double c0, double c1, double* __restrict__ g_c, double* __restrict__ g_rho) {
     const int K = p.K;
@@ -358,6 +366,23 @@ LHVI_HD void gather_finish(const lhvi_graph_t& g, const lhvi_vi_t& p, const doub
     if (!vi.hidden) {
         g_c[2 * row] = 0.0; g_c[2 * row + 1] = 0.0;
         for (int t = 0; t < p.Dmax; ++t) g_rho[row * p.Dmax + t] = 0.0;
+        return;
+    }
+    if constexpr (BFE) {
+        const double* __restrict__ pv_d = SS + (int64_t)g.V * K * 2;
+        if (vi.cont) {
+            g_c[2 * row] = c0 + SS[2 * row];
+            g_c[2 * row + 1] = c1 + SS[2 * row + 1];
+            for (int t = 0; t < p.Dmax; ++t) g_rho[row * p.Dmax + t] = 0.0;
+            return;
+        }
+        g_c[2 * row] = 0.0; g_c[2 * row + 1] = 0.0;
+        const double* pk = p.eta_d + row * p.Dmax;
+        double* gr = g_rho + row * p.Dmax;
+        double dot = 0.0;
+        for (int t = 0; t < vi.n; ++t) { gr[t] += pv_d[row * p.Dmax + t]; dot += pk[t] * gr[t]; }
+        for (int t = 0; t < vi.n; ++t) gr[t] = pk[t] * (gr[t] - dot);
+        for (int t = vi.n; t < p.Dmax; ++t) gr[t] = 0.0;
         return;
     }
     if (vi.cont) {

@@ -1,0 +1,110 @@
+"""Time per update of OneShot (lhvi_oneshot_run) next to NPVI (lhvi_npvi_run) and the mixture VI step (lhvi_vi_adam_run) on the same
+graph, K and T, in one process: the 1.0 M-factor ground RGM of scripts/bench_configs.py (`vi_ground`) at (K, T) = (1, 3), (2, 3),
+(4, 3), and the scaled cfg-3 HMLN (`vi_scaled`) at K = 2 -- the graphs of docs/kernels_npvi.md §5.  Not the contract benchmark (that
+is bench.py).  Writes profiles/oneshot_bench.json and prints one JSON line per measurement; docs/kernels_oneshot.md quotes the numbers.
+
+    python scripts/bench_oneshot.py [--updates 20] [--copies 286] [--out profiles/oneshot_bench.json] [--small] [--only-k2]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd')]
+import numpy as np
+import torch
+from lhvi import _abi, synth
+from lhvi.npvi import NPVI
+from lhvi.oneshot import OneShot
+from lhvi.vi import VarInference
+
+
+def timed(fn, updates, reps=3):
+    """median device time per update over `reps` windows of `updates` updates (events around the enqueued loop), after a warm-up"""
+    fn(2)
+    times = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        a.record()
+        fn(updates)
+        b.record()
+        torch.cuda.synchronize()
+        times.append(a.elapsed_time(b) / updates)
+    return float(np.median(times)), [float(t) for t in times]
+
+
+def time_solver(cls, flat, K, T, updates):
+    s = cls(flat, K, T, seed=0)
+    s._ensure_dev()
+    d, l = s._dev, _abi.lib()
+    log = torch.zeros(updates, dtype=torch.float64, device=s.dg.device)
+
+    def loop(n):
+        o = s._opt_struct(d, _abi.ptr, 0.05)
+        if cls is OneShot:
+            _abi.check(l.lhvi_oneshot_run(s.dg.g, s.dg.p, s._struct(), C.byref(o), _abi.ptr(d['var_coef']), n, 0, _abi.ptr(log),
+                                          _abi.ptr(d['ws']), d['ws_bytes'], _abi.stream_ptr()))
+        else:
+            _abi.check(l.lhvi_npvi_run(s.dg.g, s.dg.p, s._struct(), C.byref(o), n, 0, _abi.ptr(log), _abi.ptr(d['ws']), d['ws_bytes'],
+                                       _abi.stream_ptr()))
+        s.t += n
+    t, w = timed(loop, updates)
+    obj = float(log[updates - 1].item())
+    kernel = 'interpreter' if s.dg.p.interpreted or s.max_arity > 3 else ('lean, 8 slots' if s.max_slots <= 8 else 'lean, 24 slots')
+    skipped = int((s.var_coef[s.flat.var_hidden] == 0).sum()) if cls is OneShot else None
+    del s, d, log
+    torch.cuda.empty_cache()
+    return t, w, obj, kernel, skipped
+
+
+def measure(label, flat, K, T, updates):
+    base = dict(model=label, rvs=int(flat.V), factors=int(flat.F), edges=int(flat.E), hidden=int(flat.var_hidden.sum()), K=K, T=T,
+                updates_per_window=updates)
+    t_os, w_os, obj_os, kernel, skipped = time_solver(OneShot, flat, K, T, updates)
+    t_np, w_np, obj_np, _, _ = time_solver(NPVI, flat, K, T, updates)
+    vi = VarInference(None, K, T)
+    vi._setup_flat(flat)
+    np.random.seed(0)
+    vi.init_param()
+    vi.is_log, vi.log_fe = False, False
+    vi.alpha, vi.b1, vi.b2, vi.eps, vi.t = 0.05, 0.9, 0.999, 1e-8, 0
+    t_vi, w_vi = timed(vi.ADAM_update, updates)
+    del vi
+    torch.cuda.empty_cache()
+    return dict(base, oneshot_ms_per_update=t_os, oneshot_windows_ms=w_os, factor_kernel=kernel, oneshot_obj_last=obj_os,
+                hidden_rows_skipped_by_the_variable_kernel=skipped, npvi_ms_per_update=t_np, npvi_windows_ms=w_np, npvi_obj_last=obj_np,
+                vi_ms_per_update=t_vi, vi_windows_ms=w_vi, oneshot_over_npvi=t_os / t_np, oneshot_over_vi=t_os / t_vi)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--updates', type=int, default=20)
+    ap.add_argument('--copies', type=int, default=286)
+    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'oneshot_bench.json'))
+    ap.add_argument('--small', action='store_true', help='a rehearsal at toy sizes (the numbers mean nothing)')
+    ap.add_argument('--only-k2', action='store_true', help='the RGM at K = 2 alone, nothing written (for a kernel trace)')
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), 'bench_oneshot.py needs a GPU'
+    C_, B_, copies = (1000, 500, args.copies) if not args.small else (20, 10, 1)
+    rgm = synth.rgm_flat(C=C_, B=B_, n_values=0, evidence_ratio=0.1, seed=0)[0]
+    results = []
+    for K in ((2,) if args.only_k2 else (1, 2, 4)):
+        results.append(measure('RGM C=%d B=%d ground (Gaussian pairwise)' % (C_, B_), rgm, K, 3, args.updates))
+        print(json.dumps(results[-1]), flush=True)
+    del rgm
+    if args.only_k2:
+        return
+    hmln = synth.paper_popularity_copies(copies, 300, 10, seed=0, points=20)
+    results.append(measure('scaled cfg 3: %d x paper-popularity 300 x 10' % copies, hmln, 2, 3, args.updates))
+    print(json.dumps(results[-1]), flush=True)
+    if not args.small:
+        with open(args.out, 'w') as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), results=results), f, indent=1)
+            f.write('\n')
+
+
+if __name__ == '__main__':
+    main()

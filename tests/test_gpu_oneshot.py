@@ -1,0 +1,204 @@
+"""GPU suite of OneShot (csrc/oneshot.hip through lhvi/oneshot.py): the kernels against their host twin and against the torch twin of
+tests/oneshot_models.py on the cases and bounds of tests/test_oneshot_host.py, the launch-shape edges of the variable kernel (a
+chain that crosses its block boundaries, a hub of degree 70, an idle lane, K = 16, T = 1, every row skipped, isolated variables),
+the optimiser loop, the analytic optimum at K = 1, run-to-run bits, and the queries on a fitted model."""
+import functools
+
+import numpy as np
+import pytest
+
+import npvi_models as nm
+import oneshot_models as om
+import test_oneshot_host as th
+from lhvi import mixture
+from lhvi.graph import RV, F
+from lhvi.mixture import MixtureBelief
+from lhvi.oneshot import OneShot, LiftedOneShot
+from lhvi.potentials import QuadraticPotential
+
+pytestmark = pytest.mark.gpu
+U = 2.0 ** -53
+
+
+def long_chain(n=1025):
+    """1 025 continuous variables of degree 2 and 3: at K = 2 the variable kernel takes 128 variables a block -- nine blocks, the
+    last one holding a single group -- and the column sums five blocks of 256"""
+    rvs = [RV(nm.cdom()) for _ in range(n)]
+    unary = [QuadraticPotential(np.array([[-0.5 - 0.05 * i]]), np.array([0.3 * i - 0.6]), 0.0) for i in range(5)]
+    pair = [QuadraticPotential(np.array([[-0.4, a], [a, -0.6]]), np.array([0.1, -0.1]), 0.0) for a in (0.25, -0.2, 0.1)]
+    fs = [F(unary[i % 5], nb=[rvs[i]]) for i in range(n)] + [F(pair[i % 3], nb=[rvs[i], rvs[i + 1]]) for i in range(n - 1)]
+    return nm._graph(rvs, fs)
+
+
+def hub_graph(deg=70):
+    """one variable of degree 70 (> LHVI_HUB_DEGREE = 64, kappa = -69): its gather takes the wavefront path; the leaves have
+    degree 1 and are skipped"""
+    hub = RV(nm.cdom())
+    leaves = [RV(nm.cdom()) for _ in range(deg - 1)]
+    pair = QuadraticPotential(np.array([[-0.05, 0.02], [0.02, -0.6]]), np.array([0.01, -0.2]), 0.0)
+    fs = [F(pair, nb=[hub, x]) for x in leaves] + [F(QuadraticPotential(np.array([[-0.4]]), np.array([0.2]), 0.0), nb=[hub])]
+    return nm._graph([hub] + leaves, fs)
+
+
+SHAPES = {
+    'chain1025': (long_chain, 2, 3),
+    'hub70': (hub_graph, 3, 3),                     # K = 3: an idle lane in a KP = 4 group
+    'chain67-K16': (lambda: long_chain(67), 16, 3),          # five blocks of 16 groups, the last one of three
+    'hybrid-T1': (lambda: nm.hybrid_graph(seed=5), 3, 1),
+    'leaves_only': (om.leaves_only_graph, 2, 3),    # every hidden variable has degree 1: all rows skipped
+    'isolated': (om.isolated_graph, 3, 3),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def shape_case(name):
+    """(solver, twin reference) of a launch-shape case, computed once"""
+    make, K, T = SHAPES[name]
+    g = make()
+    tw, s = om.Twin(g, K, T), OneShot(g, K, T)
+    params = nm.start_params(tw, 21, spread=0.5)
+    tw.set_params(*params)
+    s.set_params(*params)
+    return s, tw.obj_and_grads()
+
+
+@pytest.mark.parametrize('name,K,T', th.CASES, ids=['%s-K%d-T%d' % c for c in th.CASES])
+def test_grad_against_the_host_twin_and_the_torch_twin(name, K, T):
+    g, tw, s = th.build(name, K, T)
+    params = nm.start_params(tw, 11 + K + T)
+    tw.set_params(*params)
+    s.set_params(*params)
+    dev = s.grad()
+    th.compare(dev, s.grad(host=True), s)
+    th.compare(dev, tw.obj_and_grads(), s)
+
+
+@pytest.mark.parametrize('name', sorted(SHAPES))
+def test_grad_at_the_launch_shape_edges(name):
+    s, want = shape_case(name)
+    if name == 'hub70':
+        assert s.flat.var_ptr[1] - s.flat.var_ptr[0] == 70 and s.var_coef[0] == -69.0 and np.all(s.var_coef[1:] == 0.0)
+    if name == 'leaves_only':
+        assert np.all(s.var_coef == 0.0) and s.flat.var_hidden.sum() == 4
+    if name == 'isolated':
+        assert (s.var_coef == 1.0).sum() == 2
+    dev = s.grad()
+    th.compare(dev, s.grad(host=True), s)
+    th.compare(dev, want, s)
+
+
+def test_run_against_the_host_run():
+    """20 updates with fix_mix_its = 5 and a start outside the domain, against lhvi_oneshot_run_host: the bound of
+    tests/test_oneshot_host.py::test_run_host_follows_the_twins_adam (100 times the difference measured there)"""
+    g, tw, s, params = th.run_case()
+    host = OneShot(g, 3, 3)
+    s.set_params(*params)
+    host.set_params(*params)
+    rd = s.run(its=20, lr=0.05, fix_mix_its=5)
+    rh = host.run(its=20, lr=0.05, fix_mix_its=5, host=True)
+    d = max(float(np.max(np.abs(s._h[n] - host._h[n]))) for n in ('tau', 'theta_c', 'rho'))
+    print('largest parameter difference between the device and the host run after 20 updates: %.3g' % d)
+    assert d <= th.RUN_TOL
+    np.testing.assert_allclose(rd['record']['obj'], rh['record']['obj'], rtol=1e-9)
+
+
+def test_gaussian_optimum_on_the_device():
+    g, J, h = nm.dense_gaussian_mrf(4)
+    s = OneShot(g, 1, 3, Var_bds=[1e-3, 100])
+    tw = nm.Twin(g, 1, 3)
+    s.set_params(*nm.start_params(tw, th.OPTIMUM_SEED))
+    res = s.run(its=3000, lr=0.05)
+    print('mean error %.3g, variance error %.3g' % (np.max(np.abs(res['Mu'][:, 0] - np.linalg.solve(J, h))),
+                                                    np.max(np.abs(res['Var'][:, 0] - 1 / np.diag(J)))))
+    np.testing.assert_allclose(res['Mu'][:, 0], np.linalg.solve(J, h), rtol=0, atol=1e-8)
+    np.testing.assert_allclose(res['Var'][:, 0], 1 / np.diag(J), rtol=0, atol=1e-8)
+
+
+def fitted_hybrid(its=30):
+    g = nm.hybrid_graph(seed=8)
+    s = OneShot(g, 3, 3, seed=4)
+    res = s.run(its=its, lr=0.05, fix_mix_its=3)
+    return g, s, res
+
+
+def test_two_runs_give_the_same_bits():
+    _, a, ra = fitted_hybrid()
+    _, b, rb = fitted_hybrid()
+    assert len(ra['record']['obj']) == 30 and np.all(np.isfinite(ra['record']['obj']))
+    assert ra['record']['obj'] == rb['record']['obj']
+    for n in ('tau', 'theta_c', 'rho', 'w', 'eta_c', 'eta_d'):
+        assert np.array_equal(a._h[n], b._h[n]), n
+    s, _ = shape_case('chain1025')
+    first = s.grad()
+    for x, y in zip(first, s.grad()):
+        assert np.array_equal(x, y)
+
+
+def test_queries_on_a_fitted_model():
+    g, s, res = fitted_hybrid()
+    flat, K = s.flat, s.K
+    belief = MixtureBelief.from_solver(s)
+    assert belief.V == flat.V
+    assert belief.normaliser == 'gaussian' and s.mixture_belief().normaliser == 'gaussian'
+    # the marginal log beliefs of the continuous rows against the fitted mixture evaluated on the host in extended precision; each
+    # term is off by a few units of roundoff times its exponent
+    crow = np.flatnonzero(s._cont)
+    x = np.linspace(-3.0, 3.0, 7)
+    got = belief.log_belief_all(np.zeros((1, 0)), [], crow, x)[0]
+    LD = np.longdouble
+    mu, var, w = s._h['eta_c'][crow, :, 0].astype(LD), s._h['eta_c'][crow, :, 1].astype(LD), s._h['w'].astype(LD)
+    expo = -(x[None, None, :].astype(LD) - mu[:, :, None]) ** 2 / (2 * var[:, :, None])
+    want = np.log(np.sum(w[None, :, None] * np.exp(expo) / np.sqrt(2 * LD(np.pi) * var[:, :, None]), axis=1))
+    bound = 4 * U * (K + 8) * (1 + np.max(np.abs(expo.astype(np.float64)), axis=1))
+    assert np.all(np.abs(got - want.astype(np.float64)) <= bound + 4 * U * np.abs(want.astype(np.float64)))
+    # conditioning on a discrete row: the device against the module's host side
+    a, xr = flat.rvs[0], flat.rvs[2]
+    cw_d, lp_d = belief.condition(np.array([[1.0]]), [belief.row(a)])
+    cw_h, lp_h = belief.condition(np.array([[1.0]]), [belief.row(a)], host=True)
+    np.testing.assert_allclose(cw_d, cw_h, rtol=4 * U * (K + 8), atol=0)
+    np.testing.assert_allclose(lp_d, lp_h, rtol=4 * U * (K + 8), atol=0)
+    # the variational MAP of every row in one launch against the host path (the bounds of tests/test_gpu_vi_map.py)
+    xm = s.map_rows_device()
+    host = s.map_rows()
+    for v in crow:                              # the answer is a maximum of the normal mixture (a step either way lowers it)
+        f = lambda t: s._row_belief(v, t)
+        assert f(xm[v]) >= f(xm[v] + 1e-4) and f(xm[v]) >= f(xm[v] - 1e-4)
+    hid = flat.var_hidden
+    assert np.isnan(xm[~hid]).all()
+    np.testing.assert_array_equal(xm[s._disc], host[s._disc])
+    np.testing.assert_allclose(xm[s._cont], host[s._cont], rtol=1e-7, atol=1e-7)
+    # the reference's convenience query (OneShot.py:312-326)
+    a.value = 1
+    try:
+        got = s.map([a], xr)
+        assert got == mixture.marginal_map(np.array([1.0]), [a], xr, s.w) and -4.0 <= got <= 4.0
+    finally:
+        a.value = None
+
+
+def test_lifted_solver_on_the_device():
+    """colour passing on the device finds the clusters of the symmetric graph; the lifted objective is the ground one and the
+    members carry their cluster's parameters after a run"""
+    g, _ = om.symmetric_rgm()
+    ground, lifted = OneShot(g, 2, 3), LiftedOneShot(g, 2, 3)
+    assert lifted.flat.V == 3 and ground.flat.V == 5
+    member = np.array([lifted._var_index(rv) for rv in ground.flat.rvs])
+    np.testing.assert_array_equal(lifted.var_coef[member], [-3.0, 0.0, -3.0, -3.0, -3.0])
+    rng = np.random.RandomState(4)
+    tau, Mu, lVar = rng.randn(2) * 0.3, rng.randn(3, 2), np.log(rng.uniform(0.3, 2.0, size=(3, 2)))
+    lifted.set_params(tau, Mu, lVar)
+    ground.set_params(tau, Mu[member], lVar[member])
+    ol, gl_tau, gl_c, _ = lifted.grad()
+    og, gg_tau, gg_c, _ = ground.grad()
+    assert abs(ol - og) <= 1e-9 * max(abs(og), 1.0)
+    th.assert_close(gl_tau, gg_tau, 1e-9, 'g_tau')
+    summed = np.zeros_like(gl_c)
+    np.add.at(summed, member, gg_c)
+    th.assert_close(gl_c, summed, 1e-9, 'g_c')
+    lifted.adam_eps = ground.adam_eps = 0.0
+    ground.run(its=10, lr=0.05)
+    lifted.run(its=10, lr=0.05)
+    hid = ground.flat.var_hidden
+    np.testing.assert_allclose(ground._h['theta_c'][hid], lifted._h['theta_c'][member][hid], rtol=0, atol=1e-9)
+    for rv in np.array(ground.flat.rvs, dtype=object)[hid]:
+        np.testing.assert_array_equal(rv.belief_params['mu'], lifted._h['eta_c'][lifted._var_index(rv), :, 0])
