@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 21  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 22  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -44,7 +44,8 @@ extern "C" {
                               * 18: lhvi_mix_t, lhvi_mix_*, LHVI_MIX_*;
                               * 19: lhvi_gm_fit, lhvi_gm_fit_host, LHVI_GMFIT_MAX_K;
                               * 20: lhvi_npvi_opt_t, lhvi_npvi_*, LHVI_NPVI_MAX_K, LHVI_NPVI_MAX_SLOTS, LHVI_VI_GAUSSIAN_PDF;
-                              * 21: lhvi_oneshot_* */
+                              * 21: lhvi_oneshot_*;
+                              * 22: lhvi_pbp_var_fused64 */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -482,6 +483,13 @@ int lhvi_pbp_belief_points(const lhvi_graph_t* g, const lhvi_pots_t* pots, const
 int lhvi_pbp_var_fused(const lhvi_graph_t* g, const lhvi_pbp_t* s, const double* f2v, double* v2f, double* eta, double* q,
                        const int64_t* var_gid, uint64_t seed, uint32_t iteration, double* particles_out, uint8_t* uniq_out,
                        const int32_t* desc, int32_t n16, int32_t n32_t32, int32_t n32_t64, void* stream);
+/* lhvi_pbp_var_fused for 32 < s->n <= 64 particles: one variable per wavefront, lane = particle.  Same bits as lhvi_pbp_v2f +
+ * lhvi_pbp_proposal + lhvi_pbp_resample_uniq on the listed variables.  desc: records of SIXTEEN 32-bit words per variable whatever
+ * LHVI_PBP_FUSED_RECORDS16 says (words 0-7 as above, 8 particles  9 var_ptr[v]  10-15 the first six incident edges), in two blocks:
+ * n64_t32 variables with T <= 32, then n64_t64 with 32 < T <= 64.  Everything else as for lhvi_pbp_var_fused. */
+int lhvi_pbp_var_fused64(const lhvi_graph_t* g, const lhvi_pbp_t* s, const double* f2v, double* v2f, double* eta, double* q,
+                         const int64_t* var_gid, uint64_t seed, uint32_t iteration, double* particles_out, uint8_t* uniq_out,
+                         const int32_t* desc, int32_t n64_t32, int32_t n64_t64, void* stream);
 /* The normaliser of EPBP.belief for nq query rows in ONE launch: EPBP.py:325-328 calls scipy.integrate.quad on e ** belief_rv over
  * [lo, hi] (= the domain widened by 20 on both sides).  A thread per row runs QUADPACK's 21-point Gauss-Kronrod rule (dqk21 and
  * its error estimate) inside dqage's globally adaptive bisection (at most 50 intervals) until the summed error estimate meets

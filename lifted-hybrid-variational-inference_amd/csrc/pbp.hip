@@ -2887,17 +2887,58 @@ constexpr int FUSED_CH = 8;          // edges of a row whose loads are in flight
 #ifndef LHVI_FUSED_NB
 #define LHVI_FUSED_NB 2          // (scripts/diag/fused_batch.sh: 2 passes in flight at 4 waves/SIMD beat 4 passes, which spill)
 #endif
+// W = 64 (32 < np <= 64: the benchmark's particle count): ONE variable per wavefront, lane = particle.
+//   step 1 = the body of pbp_v2f_kernel for nchunk == 1 (its wave_sum / wave_max networks);
+//   step 2 = pbp_proposal_kernel with its own lane groups: group `lane / PW` takes the edges k = group (mod 64 / PW), one sum per
+//            group, folded by that kernel's xor network;
+//   step 3 = the draw of pbp_resample_uniq_kernel (Philox block j & 31, cosine for j < 32, sine for j >= 32) and an exact
+//            first-occurrence mask: every live lane writes its lane number into a wave-private LDS byte table at a hash of its
+//            particle's bit pattern and reads the slot back; a lane that reads another lane's number is a suspect.  Of several equal
+//            particles (one slot) at most one reads its own number, so every group of equal particles holds a suspect, and the
+//            sampler's exact pass over the suspects' values (ballots on the 64-bit patterns) finds every group.  The table needs
+//            no clearing: a lane only reads a slot it has just written.
+// The rows are walked in chunks of FUSED_CH64 edges (the benchmark's graph is 4-regular: a chunk of eight would fetch four rows for
+// nothing), the records always have sixteen words, and with LHVI_FUSED64_PRE the first proposal pass's loads (eta and the integral
+// points of the first 64 / PW edges) are issued together with the first chunk's rows, ahead of step 1's arithmetic.
+#ifndef LHVI_FUSED64_WAVES
+#define LHVI_FUSED64_WAVES 8     // (the 'simple' rule at T <= 32; the cavity branch and the two-points-over-32-lanes form need LHVI_FUSED_WAVES' registers)
+#endif
+#ifndef LHVI_FUSED64_CH
+#define LHVI_FUSED64_CH 4
+#endif
+#ifndef LHVI_FUSED64_PRE
+#define LHVI_FUSED64_PRE 1
+#endif
+#ifndef LHVI_FUSED64_EARLY
+#define LHVI_FUSED64_EARLY 1
+#endif
+#ifndef LHVI_FUSED64_LATE_TABLE
+#define LHVI_FUSED64_LATE_TABLE 1
+#endif
+constexpr int FUSED_CH64 = LHVI_FUSED64_CH;
+constexpr int FUSED64_HASH_BITS = 12;   // 4 KiB per wavefront: 64^2 / 2 / 4096 = 0.5 false suspects per variable, ten instructions each
 template <int W, int PW, bool EP, bool R16>
-__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LHVI_FUSED_WAVES, 8)))
+__global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(W == 64 ? (PW == 32 || EP ? LHVI_FUSED_WAVES : LHVI_FUSED64_WAVES) : LHVI_FUSED_WAVES, 8)))
 pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2v, double* __restrict__ v2f, double* __restrict__ eta,
                      double* __restrict__ q, const int64_t* __restrict__ gid, uint64_t seed, uint32_t iteration,
                      double* __restrict__ out, uint8_t* __restrict__ uniq, const int32_t* __restrict__ list, int count) {
     __shared__ LogRec sh_log[LOG_TAB_N];
-    load_log_table(sh_log);
-    __syncthreads();
+    __shared__ uint8_t sh_owner[W == 64 ? (BLOCK / WAVE) << FUSED64_HASH_BITS : 1];      // (W = 64: step 3's table of lane numbers)
+    // W = 64 with LHVI_FUSED64_LATE_TABLE: the log table -- step 3's alone -- is asked for here and put into LDS just before that
+    // step, so that a workgroup's record and row loads do not wait behind the table's round trip and a barrier
+    constexpr bool LATE_TABLE = W == 64 && LHVI_FUSED64_LATE_TABLE != 0;
+    double tab_inv = 0.0, tab_log = 0.0;
+    if constexpr (LATE_TABLE) {
+        if (threadIdx.x < LOG_TAB_N) { tab_inv = LOG_TAB[2 * threadIdx.x]; tab_log = LOG_TAB[2 * threadIdx.x + 1]; }
+    } else {
+        load_log_table(sh_log);
+        __syncthreads();
+    }
     constexpr int G = WAVE / W, SL = W / PW;                 // variables per wavefront; edges of a variable per proposal pass
     const int lane = threadIdx.x & 63;
-    const int64_t slot = ((int64_t)blockIdx.x * (BLOCK / WAVE) + (threadIdx.x >> 6)) * G + lane / W;
+    // (W = 64: the wavefront's number as a scalar, so that its record and everything read through it are scalar loads)
+    const int wave = W == 64 ? __builtin_amdgcn_readfirstlane(threadIdx.x >> 6) : (int)(threadIdx.x >> 6);
+    const int64_t slot = ((int64_t)blockIdx.x * (BLOCK / WAVE) + wave) * G + lane / W;
     const int j = lane % W;
     const bool on = slot < count;
     // R16 (LHVI_PBP_FUSED_RECORDS16): records of sixteen words -- the eight above, then 8 particles (np)  9 var_ptr[v]  10-15 the
@@ -2932,8 +2973,9 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
     // dependent global round trips in step 1 and as many again in step 2, and the kernel's time is those latencies (2.6 ms at
     // n = 16 on the headline graph whatever its occupancy).  The arithmetic is the same expressions in the same order on the same
     // values as in the three kernels.
-    constexpr int CH = FUSED_CH;
+    constexpr int CH = W == 64 ? FUSED_CH64 : FUSED_CH;
     static_assert(W >= CH && CH % SL == 0, "lane j of a group holds edge j of the chunk");
+    static_assert(W < 64 || R16, "the one-variable-per-wavefront form reads sixteen-word records");
     const int first_lane = lane / W * W;
     const int nch = (maxdeg + CH - 1) / CH;                    // (wave-uniform, like maxdeg)
     int my_e = 0, held = -1;
@@ -2946,7 +2988,20 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
         }
         my_e = (j < CH && c * CH + j < deg) ? g.var_edge[lo + c * CH + j] : 0;
     };
-    // ---- step 1: v -> f (pbp_v2f_packed_kernel<W>)
+    // W = 64: the loads of the first proposal pass, asked for while step 1 waits for its rows
+    constexpr bool PRE = W == 64 && LHVI_FUSED64_PRE != 0;
+    int pre_e = 0;
+    double pre_b0 = 0.0, pre_b1 = 1.0, pre_g0 = 0.0, pre_g1 = 0.0;
+    auto preload = [&]() {
+        const int psub = j / PW, ptl = j % PW;
+        const int pt0 = min(ptl, max(T - 1, 0)), pt1 = min(ptl + PW, max(T - 1, 0));
+        pre_e = __shfl(my_e, first_lane + min(psub, CH - 1));
+        if (psub >= CH || psub >= deg) pre_e = 0;             // (beyond the row: edge 0's, loaded and dropped)
+        const double* msg = f2v + (int64_t)pre_e * S + n;
+        pre_b0 = eta[2 * pre_e]; pre_b1 = eta[2 * pre_e + 1];
+        pre_g0 = msg[pt0]; pre_g1 = msg[pt1];
+    };
+    // ---- step 1: v -> f (pbp_v2f_packed_kernel<W>; W = 64: pbp_v2f_kernel)
     {
         double total = 0.0;
         int ee[CH];
@@ -2959,25 +3014,43 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
 #pragma unroll
             for (int i = 0; i < CH; ++i) mm[i] = f2v[(int64_t)ee[i] * S + (valid ? j : 0)];        // (beyond the row: edge 0's row, never used)
         };
+        // W = 64 with LHVI_FUSED64_EARLY: the particle and its mask byte are asked for ahead of the rows, and the importance weight
+        // (a chain of dependent loads through var_dom and the domain's bounds) is formed while the rows are on their way
+        constexpr bool EARLY = W == 64 && LHVI_FUSED64_EARLY != 0;
+        double logw = 0.0, early_x = 0.0;
+        bool uq = false;
+        auto importance = [&](double xp) {
+            const int d = g.var_dom[v];
+            const double sd = sqrt_pos(q1);
+            return log_importance(g, s, v, d, xp, q0, rcp_newton(sd), log_pos(2.506628274631 * sd));
+        };
+        if (EARLY && valid) {
+            early_x = s.particles[(int64_t)v * n + j];
+            uq = s.uniq[(int64_t)v * n + j] != 0;
+        }
         for (int c = 0; c < nch; ++c) {
             load_rows(c);
+            if (PRE && c == 0) preload();
+            if (EARLY && c == 0 && valid) logw = importance(early_x);
 #pragma unroll
             for (int i = 0; i < CH; ++i) {
                 const double m = valid ? mm[i] : 0.0;
                 if (c * CH + i < deg) total += lifted ? m * g.edge_count[ee[i]] : m;
             }
         }
-        double logw = 0.0;
-        bool uq = false;
-        if (valid) {
-            const int d = g.var_dom[v];
-            const double sd = sqrt_pos(q1);
-            logw = log_importance(g, s, v, d, s.particles[(int64_t)v * n + j], q0, rcp_newton(sd), log_pos(2.506628274631 * sd));
+        if (!EARLY && valid) {
+            logw = importance(s.particles[(int64_t)v * n + j]);
             uq = s.uniq[(int64_t)v * n + j] != 0;
         }
-        auto group_sum = [&](double x) { return W == 16 ? dpp_move<0x15F>(dpp_row_reduce(x, SumOp())) : dpp_half_reduce(x, SumOp(), lane); };
-        auto group_max = [&](double x) { return W == 16 ? dpp_row_reduce(x, MaxOp()) : dpp_half_reduce(x, MaxOp(), lane); };
-        const uint64_t mine = (W == 16 ? 0xffffull : 0xffffffffull) << (lane / W * W);
+        auto group_sum = [&](double x) {
+            if constexpr (W == 64) return wave_sum(x);
+            else return W == 16 ? dpp_move<0x15F>(dpp_row_reduce(x, SumOp())) : dpp_half_reduce(x, SumOp(), lane);
+        };
+        auto group_max = [&](double x) {
+            if constexpr (W == 64) return wave_max(x);
+            else return W == 16 ? dpp_row_reduce(x, MaxOp()) : dpp_half_reduce(x, MaxOp(), lane);
+        };
+        const uint64_t mine = W == 64 ? ~0ull : (W == 16 ? 0xffffull : 0xffffffffull) << (lane / W * W);
         const double rcnt = rcp_newton(fmax((double)__builtin_popcountll(__ballot(uq) & mine), 1.0));
         for (int c = 0; c < nch; ++c) {
             if (nch > 1) load_rows(c);                          // (a one-chunk row still holds its messages)
@@ -3008,7 +3081,7 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
     // an edge's T integral points over PW lanes: at most two per lane (T <= 2 PW by the lists' definition, include/lhvi.h)
     const int t0 = min(tl, max(T - 1, 0)), t1 = min(tl + PW, max(T - 1, 0));           // (clamped: the loads need no branch)
     const double xg0 = g.dom_val[gb + t0], xg1 = g.dom_val[gb + t1];
-    constexpr int NB = LHVI_FUSED_NB;                          // passes (SL edges of a variable each) whose loads are in flight together
+    constexpr int NB = W == 64 ? (LHVI_FUSED_NB < CH / SL ? LHVI_FUSED_NB : CH / SL) : LHVI_FUSED_NB;   // passes (SL edges of a variable each) whose loads are in flight together
     for (int c = 0; c < nch; ++c) {
         hold_chunk(c);
 #pragma unroll
@@ -3024,6 +3097,10 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
             }
 #pragma unroll
             for (int i = 0; i < NB; ++i) {
+                if (PRE && p0 + i == 0 && c == 0) {                // (asked for before step 1)
+                    b0[i] = pre_b0; b1[i] = pre_b1; g0[i] = pre_g0; g1[i] = pre_g1;
+                    continue;
+                }
                 const double* msg = f2v + (int64_t)ee[i] * S + n;
                 b0[i] = eta[2 * ee[i]]; b1[i] = eta[2 * ee[i] + 1];
                 g0[i] = msg[t0]; g1[i] = msg[t1];
@@ -3066,19 +3143,28 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
                     const double p = rcp_newton(sig);
                     const int slot4 = k & (WAVE / PW - 1);             // the lane group of pbp_proposal_kernel this edge would fall to
                     const double cnt = lifted ? g.edge_count[e] : 1.0;
+                    if constexpr (W == 64) {                           // (slot4 == sub: the lane's own group, one sum)
+                        if (lifted) { ps[0] += p * cnt; pm[0] += p * mu * cnt; }
+                        else { ps[0] += p; pm[0] += p * mu; }
+                    } else {
 #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (r == slot4) {
-                            if (lifted) { ps[r] += p * cnt; pm[r] += p * mu * cnt; }
-                            else { ps[r] += p; pm[r] += p * mu; }
-                        }
+                        for (int r = 0; r < 4; ++r)
+                            if (r == slot4) {
+                                if (lifted) { ps[r] += p * cnt; pm[r] += p * mu * cnt; }
+                                else { ps[r] += p; pm[r] += p * mu; }
+                            }
+                    }
                 }
             }
         }
     }
     // that kernel's fold of its lane groups: PW = 16: (g0 + g1) + (g2 + g3); PW = 32: g0 + g1
     double fs, fm;
-    if (PW == 16 && SL == 1) { fs = (ps[0] + ps[1]) + (ps[2] + ps[3]); fm = (pm[0] + pm[1]) + (pm[2] + pm[3]); }
+    if constexpr (W == 64) {                                   // SL == 4: xor 16, then xor 32; SL == 2: xor 32
+        fs = ps[0]; fm = pm[0];
+#pragma unroll
+        for (int off = PW; off < 64; off <<= 1) { fs += __shfl_xor(fs, off); fm += __shfl_xor(fm, off); }
+    } else if (PW == 16 && SL == 1) { fs = (ps[0] + ps[1]) + (ps[2] + ps[3]); fm = (pm[0] + pm[1]) + (pm[2] + pm[3]); }
     else if (PW == 16) {
         // slot 0 holds g0 and g2, slot 1 (sixteen lanes on) g1 and g3
         const double s01 = (sub == 0 ? ps[0] : ps[1]), s23 = (sub == 0 ? ps[2] : ps[3]);
@@ -3090,19 +3176,44 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
     const double mu_new = fs * fm, var_new = fs;
     if (on && j == 0) { q[2 * v] = mu_new; q[2 * v + 1] = var_new; }
     // ---- step 3: the new particles and their first-occurrence mask (pbp_resample_uniq_kernel)
+    if constexpr (LATE_TABLE) {
+        static_assert(LOG_TAB_N <= BLOCK, "one table entry per thread");
+        if (threadIdx.x < LOG_TAB_N) { sh_log[threadIdx.x].inv_c = tab_inv; sh_log[threadIdx.x].log_c = tab_log; }
+        __syncthreads();
+    }
     // (the values every lane of the group needs are the ones its first lane formed: that lane wrote q)
     const double mu_b = __shfl(mu_new, first_lane), sd_b = sqrt_pos(__shfl(var_new, first_lane));
     double x = 0.0;
     if (valid) {
         double zc, zs;
-        philox_normal_pair(seed, gid ? (uint64_t)gid[v] : (uint64_t)v, (uint32_t)j, iteration, sh_log, zc, zs);
+        philox_normal_pair(seed, gid ? (uint64_t)gid[v] : (uint64_t)v, (uint32_t)(W == 64 ? j & 31 : j), iteration, sh_log, zc, zs);
+        if (W == 64 && (j & 32)) zc = zs;                         // (particles j and j + 32 share a block: cosine and sine)
         x = fmin(fmax(fma(sd_b, zc, mu_b), dlo), dhi) + 0.0;      // + 0.0: no -0, so that equality below is equality of the patterns
         out[(int64_t)v * n + j] = x;
     }
     int u = valid;
-    for (int k = 0; k + 1 < W; ++k) {
-        const double xk = __shfl(x, first_lane + k);
-        if (k < j && k < np && xk == x) u = 0;
+    if constexpr (W == 64) {
+        volatile uint8_t* owner = sh_owner + ((threadIdx.x >> 6) << FUSED64_HASH_BITS);
+        const int xlo = __double2loint(x), xhi = __double2hiint(x);
+        const uint32_t h = (((uint32_t)xlo * 0x9E3779B1u) ^ ((uint32_t)xhi * 0x85EBCA6Bu)) >> (32 - FUSED64_HASH_BITS);
+        if (valid) owner[h] = (uint8_t)lane;
+        LHVI_WAVE_SYNC();
+        const bool suspect = valid && owner[h] != (uint8_t)lane;
+        const uint64_t live = __ballot(valid);
+        uint64_t todo = __ballot(suspect), dp = 0;
+        while (todo) {                                         // one step per distinct suspect value -- in practice the two domain bounds
+            const int k = __builtin_ctzll(todo);
+            const int klo = __builtin_amdgcn_readlane(xlo, k), khi = __builtin_amdgcn_readlane(xhi, k);
+            const uint64_t same = __ballot(xlo == klo && xhi == khi) & live;      // every lane holding this value
+            dp |= same & (same - 1);                                              // all but its first occurrence
+            todo &= ~same;
+        }
+        u = valid && !((dp >> lane) & 1);
+    } else {
+        for (int k = 0; k + 1 < W; ++k) {
+            const double xk = __shfl(x, first_lane + k);
+            if (k < j && k < np && xk == x) u = 0;
+        }
     }
     if (on && j < n) uniq[(int64_t)v * n + j] = (uint8_t)u;
 }
@@ -3547,6 +3658,30 @@ int lhvi_pbp_var_fused(const lhvi_graph_t* g, const lhvi_pbp_t* s, const double*
     LHVI_FUSED(32, 16, desc + rw * (int64_t)n16, n32_t32)
     LHVI_FUSED(32, 32, desc + rw * ((int64_t)n16 + n32_t32), n32_t64)
 #undef LHVI_FUSED
+    return check_launch();
+}
+
+int lhvi_pbp_var_fused64(const lhvi_graph_t* g, const lhvi_pbp_t* s, const double* f2v, double* v2f, double* eta, double* q,
+                         const int64_t* var_gid, uint64_t seed, uint32_t iteration, double* particles_out, uint8_t* uniq_out,
+                         const int32_t* desc, int32_t n64_t32, int32_t n64_t64, void* stream) {
+    if (int rc = validate_pbp(g, s)) return rc;
+    if (!f2v || !v2f || !eta || !q || !particles_out || !uniq_out || !s->uniq || !s->q || !g->dom_lo || !g->dom_hi || !g->dom_val) return LHVI_E_ARG;
+    if (n64_t32 < 0 || n64_t64 < 0 || s->n <= 32 || s->n > 64 || s->bslot || s->var_hi > s->var_lo || particles_out == s->particles) return LHVI_E_ARG;
+    if ((int64_t)n64_t32 + n64_t64 == 0) return LHVI_OK;
+    if (!desc) return LHVI_E_ARG;
+    hipStream_t st = as_stream(stream);
+    const bool ep = (s->flags & LHVI_PBP_EP) != 0;
+#define LHVI_FUSED64(PW, list, cnt)                                                                                                   \
+    if ((cnt) > 0) {                                                                                                                  \
+        const dim3 grid(grid_for((int64_t)(cnt) * WAVE));                                                                             \
+        if (ep) hipLaunchKernelGGL((pbp_var_fused_kernel<64, PW, true, true>), grid, dim3(BLOCK), 0, st, *g, *s, f2v, v2f, eta, q, var_gid, \
+                                   seed, iteration, particles_out, uniq_out, list, cnt);                                             \
+        else hipLaunchKernelGGL((pbp_var_fused_kernel<64, PW, false, true>), grid, dim3(BLOCK), 0, st, *g, *s, f2v, v2f, eta, q, var_gid,   \
+                                seed, iteration, particles_out, uniq_out, list, cnt);                                                \
+    }
+    LHVI_FUSED64(16, desc, n64_t32)
+    LHVI_FUSED64(32, desc + 16 * (int64_t)n64_t32, n64_t64)
+#undef LHVI_FUSED64
     return check_launch();
 }
 

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 21            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 22            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -212,6 +212,7 @@ SIGNATURES = {
     'lhvi_pbp_belief_points': (C.c_int, [_G, _P, _S, _vp, _i32, _vp, _i32, _vp, _vp, _vp]),
     'lhvi_pbp_map_brent': (C.c_int, [_G, _P, _S, _vp, _i64, _vp, _vp, _vp, _vp, _f64, _i32, _vp, _vp, _vp, _vp]),
     'lhvi_pbp_var_fused': (C.c_int, [_G, _S, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
+    'lhvi_pbp_var_fused64': (C.c_int, [_G, _S, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _i32, _i32, _vp]),
     'lhvi_pbp_quad': (C.c_int, [_G, _P, _S, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
     'lhvi_vi_workspace_bytes': (_sz, [_G, _VI]),
     'lhvi_vi_grad': (C.c_int, [_G, _P, _VI, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

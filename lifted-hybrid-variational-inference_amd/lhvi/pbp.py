@@ -57,9 +57,10 @@ class _ParticleSweep:
     overlap_min_heavy = 1 << 16     # least this many edges: the few-particle kernels lose by it (4.55 -> 4.60 ms at n = 16), small graphs gain nothing
     fused_var_kernel = True         # few particles, device sampler: v -> f, proposal update and the new sample of a continuous variable in
                                     # ONE pass over its rows (lhvi_pbp_var_fused) instead of three launches; same bits
-    fused_max_particles = 32        # ... up to this many particles.  With a row's loads in flight together (csrc/pbp.hip, FUSED_CH) the fused kernel
+    fused_max_particles = 64        # ... up to this many particles.  With a row's loads in flight together (csrc/pbp.hip, FUSED_CH) the fused kernel
                                     # wins at every width: n = 10 / 16 / 20 / 32: 5.65 / 5.83 / 8.56 / 9.53 -> 4.97 / 5.03 / 8.25 / 9.30 ms per sweep
-                                    # (profiles/r05_experiments.md item 7; walked edge by edge it was a draw at n <= 16 and a loss beyond)
+                                    # (profiles/r05_experiments.md item 7; walked edge by edge it was a draw at n <= 16 and a loss beyond); 33 - 64
+                                    # particles take lhvi_pbp_var_fused64, one variable per wavefront (profiles/fused64_experiments.md)
     exact_queries = False           # map / probability / belief answer per-variable calls from ONE batched pass over all
                                     # variables, made at the first call after run() (True: one fminbound / log_area / quad per call)
     map_mode = 'fminbound'          # what the batched map() runs per variable: the reference's fminbound iteration (lhvi_pbp_map_brent)
@@ -171,12 +172,15 @@ class _ParticleSweep:
         self._fused = None
         pT = sizes[pdom] if pv.size else np.zeros(0, dtype=np.int64)
         fused_max = int(os.environ.get('LHVI_PBP_FUSED_MAX', self.fused_max_particles))          # (tuning aid: scripts/diag/fused_batch.sh)
-        fz = (pdeg <= min(64, self.prop_slice)) & (pT <= 64) & (n <= min(32, fused_max)) if pv.size else np.zeros(0, dtype=bool)
+        fz = (pdeg <= min(64, self.prop_slice)) & (pT <= 64) & (n <= min(64, fused_max)) if pv.size else np.zeros(0, dtype=bool)
         if (self.fused_var_kernel and os.environ.get('LHVI_PBP_FUSED', '1') != '0') and owned is None and self.sampler == 'device' and self.listed_proposal and self.listed_resample \
                 and 'v2f_wide' in host_lists and fz.any():
             k16 = fz & (n <= 16) & (pT <= 32)
-            k32a = fz & ~k16 & (pT <= 32)
-            k32b = fz & ~k16 & ~k32a
+            k32a = fz & (n <= 32) & ~k16 & (pT <= 32)
+            k32b = fz & (n <= 32) & ~k16 & ~k32a
+            # 32 < n <= 64: one variable per wavefront (lhvi_pbp_var_fused64), a list of its own, always in the sixteen-word layout
+            k64a = fz & (n > 32) & (pT <= 32)
+            k64b = fz & (n > 32) & ~k64a
             # sixteen words per variable (LHVI_PBP_FUSED_RECORDS16): the eight of include/lhvi.h, then np, var_ptr[v] and the first six
             # incident edges -- the kernel's row loads then hang on one load behind the record (LHVI_PBP_FUSED_REC16=0: eight words)
             wide_rec = os.environ.get('LHVI_PBP_FUSED_REC16', '1') != '0'
@@ -184,13 +188,25 @@ class _ParticleSweep:
             fd[:, 0], fd[:, 1], fd[:, 2], fd[:, 3] = pv, pdeg, flat.dom_ptr[pdom], pT
             fd[:, 4:6] = np.ascontiguousarray(flat.dom_lo[pdom], dtype=np.float64).view(np.int32).reshape(-1, 2)
             fd[:, 6:8] = np.ascontiguousarray(flat.dom_hi[pdom], dtype=np.float64).view(np.int32).reshape(-1, 2)
+            def sixteen(rec8):
+                rec = np.zeros((pv.size, 16), dtype=np.int32)
+                rec[:, :8] = rec8
+                rec[:, 8], rec[:, 9] = self.np_host[pv], flat.var_ptr[pv]
+                for k in range(6):
+                    has = pdeg > k
+                    rec[has, 10 + k] = flat.var_edge[pbase[has] + k]
+                return rec
             if wide_rec:
                 fd[:, 8], fd[:, 9] = self.np_host[pv], flat.var_ptr[pv]
                 for k in range(6):
                     has = pdeg > k
                     fd[has, 10 + k] = flat.var_edge[pbase[has] + k]
                 self.flags |= _abi.PBP_FUSED_RECORDS16
-            host_lists['fused_desc'] = np.ascontiguousarray(np.concatenate([fd[k16], fd[k32a], fd[k32b]]))
+            small = np.concatenate([fd[k16], fd[k32a], fd[k32b]])
+            host_lists['fused_desc'] = np.ascontiguousarray(small) if small.size else np.zeros((1, fd.shape[1]), dtype=np.int32)
+            if k64a.any() or k64b.any():
+                fd64 = fd if wide_rec else sixteen(fd[:, :8])
+                host_lists['fused64_desc'] = np.ascontiguousarray(np.concatenate([fd64[k64a], fd64[k64b]]))
             fused_var = np.zeros(flat.V, dtype=bool)
             fused_var[pv[fz]] = True
             # the rest: proposal records (slices of hub rows sit at the head of pd and are never fused), sampler records, v -> f lists
@@ -206,14 +222,15 @@ class _ParticleSweep:
                     host_lists['v2f_rest_' + name] = (self._v2f_records(flat, vs) if name == 'wide' and os.environ.get('LHVI_PBP_V2F_REC', '1') != '0' else
                                                       vs.astype(np.int32) if vs.size else np.zeros(1, dtype=np.int32))
                     rest_parts.append((name, int(vs.size)))
-            self._fused = dict(counts=(int(k16.sum()), int(k32a.sum()), int(k32b.sum())), n_prop_rest=int(keep.sum()),
-                               n_resample_rest=int(rkeep.sum()), rest_parts=rest_parts)
+            self._fused = dict(counts=(int(k16.sum()), int(k32a.sum()), int(k32b.sum())), counts64=(int(k64a.sum()), int(k64b.sum())),
+                               n_prop_rest=int(keep.sum()), n_resample_rest=int(rkeep.sum()), rest_parts=rest_parts)
         dev_lists = _abi.upload(host_lists)
         for name in ('np_dev', 'resample_vars', '_static_idx', 'prop_desc'):
             setattr(self, name, dev_lists[name])
         if self._fused is not None:
             F = self._fused
             F['desc'], F['prop_desc_rest'], F['resample_rest'] = dev_lists['fused_desc'], dev_lists['prop_desc_rest'], dev_lists['resample_rest']
+            F['desc64'] = dev_lists.get('fused64_desc')
             F['v2f_rest'] = tuple(x for name, cnt in F['rest_parts'] for x in (dev_lists['v2f_rest_' + name], cnt)) if F['rest_parts'] else None
         if 'prop_hub' in dev_lists:
             self.prop_hub = dev_lists['prop_hub']
@@ -506,9 +523,15 @@ class _ParticleSweep:
             F = self._fused
             s = self._struct()
             n16, n32a, n32b = F['counts']
-            _abi.check(l.lhvi_pbp_var_fused(g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev),
-                                            _abi.ptr(getattr(self, 'var_gid', None)), int(self.seed), int(self._draws),
-                                            _abi.ptr(self.old_particles), _abi.ptr(self.uniq), _abi.ptr(F['desc']), n16, n32a, n32b, st))
+            if n16 + n32a + n32b:
+                _abi.check(l.lhvi_pbp_var_fused(g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev),
+                                                _abi.ptr(getattr(self, 'var_gid', None)), int(self.seed), int(self._draws),
+                                                _abi.ptr(self.old_particles), _abi.ptr(self.uniq), _abi.ptr(F['desc']), n16, n32a, n32b, st))
+            if F['desc64'] is not None:
+                n64a, n64b = F['counts64']
+                _abi.check(l.lhvi_pbp_var_fused64(g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev),
+                                                  _abi.ptr(getattr(self, 'var_gid', None)), int(self.seed), int(self._draws),
+                                                  _abi.ptr(self.old_particles), _abi.ptr(self.uniq), _abi.ptr(F['desc64']), n64a, n64b, st))
             w, nw, nr, nn, hb, nh, m16, c16, m32, c32 = F['v2f_rest']
             s.v2f_wide, s.n_v2f_wide, s.v2f_narrow, s.n_v2f_narrow = _abi.ptr(w), nw, _abi.ptr(nr), nn
             s.v2f_hub, s.n_v2f_hub = _abi.ptr(hb), nh
