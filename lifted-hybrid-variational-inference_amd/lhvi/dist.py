@@ -12,6 +12,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
+from .pbp_plan import V2fLists
 
 
 def joint_terms(flat, np_host, edge_mask=None):
@@ -434,8 +435,7 @@ class ShardedRunner:
             s.brow_ptr, s.brow_off, s.recv = _abi.ptr(self.one_ptr), _abi.ptr(self.total_off), _abi.ptr(self.bufB)
         s.prop_desc, s.n_prop_desc = None, 0                 # the sharded proposal addresses variables by range
         s.prop_hub, s.n_prop_hub, s.prop_partial = None, 0, None
-        s.v2f_wide, s.n_v2f_wide, s.v2f_narrow, s.n_v2f_narrow, s.v2f_hub, s.n_v2f_hub = None, 0, None, 0, None, 0     # ... and so does the sharded v -> f half
-        s.v2f_mid16, s.n_v2f_mid16, s.v2f_mid32, s.n_v2f_mid32 = None, 0, None, 0
+        V2fLists().install(s)                                # ... and so does the sharded v -> f half
         if part is not None:
             s.var_lo, s.var_hi = (0, self.n_int) if part == 0 else (self.n_int, self.plan.flat.V)
         return s
@@ -1033,8 +1033,7 @@ class OwnerRunner:
             s.flags |= _abi.PBP_LEAVE_ROOM
         s.prop_desc, s.n_prop_desc = None, 0                 # variables are addressed by range: owned [0, n_owned), ghosts after them
         s.prop_hub, s.n_prop_hub, s.prop_partial = None, 0, None
-        s.v2f_wide, s.n_v2f_wide, s.v2f_narrow, s.n_v2f_narrow, s.v2f_hub, s.n_v2f_hub = None, 0, None, 0, None, 0
-        s.v2f_mid16, s.n_v2f_mid16, s.v2f_mid32, s.n_v2f_mid32 = None, 0, None, 0
+        V2fLists().install(s)
         s.var_lo, s.var_hi = int(lo), int(hi)
         return s
 

@@ -22,7 +22,7 @@ from math import e, log, sqrt
 
 import numpy as np
 
-from . import _abi
+from . import _abi, pbp_plan
 from .flat import flatten
 
 # Schedules of the f -> v half sweep (_ParticleSweep._launch_f2v): the lhvi_pbp_f2v calls in issue order, each as (stream, kernel
@@ -82,17 +82,9 @@ class _ParticleSweep:
         self.dg = dg = _abi.DeviceGraph(flat)
         torch = _abi.require_gpu()
         n = self.n
-        sizes = np.diff(flat.dom_ptr)
-        cont = flat.dom_cont.astype(bool)
-        self.T = int(sizes[cont].max()) if cont.any() else 0
-        nst = flat.var_nstates
-        if (flat.var_hidden & ~flat.var_cont & (nst > n)).any():
-            raise _abi.LhviError('a discrete variable has more states than particle slots n=%d' % n)
-        if (flat.var_hidden & flat.var_cont & (np.diff(flat.var_ptr) == 0)).any():
-            # the reference fails in gaussian_product (`0 ** -1`, EPBP:30-41) on the first proposal update of such a variable
-            raise ZeroDivisionError('a hidden continuous variable has no incident factor: its proposal is an empty product')
-        self.np_host = np.where(flat.var_hidden, np.where(flat.var_cont, n, nst), 0).astype(np.int32)
-        host_lists = {'np_dev': self.np_host}          # the per-variable lists below go to the device in one copy (_abi.upload)
+        # which variable goes to which kernel, and the records those kernels read (lhvi/pbp_plan.py)
+        plan = pbp_plan.var_side_plan(flat, n, owned=owned, opts=self._plan_options())
+        self.np_host, self.T = plan.np_host, plan.T
         S = n + self.T
         self.f2v = dg.zeros(flat.E, S)
         self.v2f = dg.zeros(flat.E, n)
@@ -102,142 +94,23 @@ class _ParticleSweep:
         self.old_particles = dg.zeros(flat.V, n)
         self.uniq = torch.zeros(flat.V, n, dtype=torch.uint8, device=dg.device)
         self.f2v_ticket = torch.zeros(16, dtype=torch.int32, device=dg.device)    # work counters + statistics of the heavy f2v kernel (LHVI_PBP_TICKET_WORDS)
+        self.prop_partial = dg.zeros(plan.n_prop_partial, 2) if plan.n_prop_partial else None
         self.flags = (_abi.PBP_EP if self.proposal_approximation == 'EP' else 0) | \
                      (_abi.PBP_EPBP_DISCRETE if self._epbp_discrete else 0) | \
                      (_abi.PBP_CQ if self.cq_routing and bool((flat.pot_kind == 8).any()) else 0) | \
-                     (_abi.PBP_POW2_GROUPS if os.environ.get('LHVI_PBP_POW2_GROUPS', '0') == '1' else 0)   # (tuning aid: scripts/diag/narrow_groups.sh)
+                     (_abi.PBP_POW2_GROUPS if os.environ.get('LHVI_PBP_POW2_GROUPS', '0') == '1' else 0) | \
+                     plan.flags                                 # (LHVI_PBP_POW2_GROUPS: tuning aid, scripts/diag/narrow_groups.sh)
         self._views, self._batched = {}, {}
         self._draws = 0
+        self._static_rows = False           # the rows no listed draw writes are filled once, by the first draw (_generate_sample)
         self.cq_desc, self.n_cq = None, 0
         self.fast_edges = self.generic_edges = self._fast_list = self._generic_list = torch.zeros(1, dtype=torch.int32, device=dg.device)
-        # records of the hidden continuous variables for the proposal kernel (include/lhvi.h, lhvi_pbp_t.prop_desc)
-        pv_all = np.flatnonzero(flat.var_hidden & flat.var_cont)
-        pv = pv_all if owned is None else pv_all[pv_all < owned]
-        pd = np.zeros((pv.size, 8), dtype=np.int32)
-        pdeg = np.diff(flat.var_ptr)[pv]
-        pdom = flat.var_dom[pv]
-        pd[:, 0], pd[:, 1], pd[:, 2], pd[:, 3] = pv, pdeg, flat.dom_ptr[pdom], sizes[pdom]
-        pbase = flat.var_ptr[pv].astype(np.int64)
-        for k in range(4):
-            if flat.var_edge.size:
-                pd[:, 4 + k] = flat.var_edge[np.minimum(pbase + np.minimum(k, np.maximum(pdeg - 1, 0)), flat.var_edge.size - 1)]
-        # the device sampler's list (include/lhvi.h, lhvi_pbp_t.resample_vars); the other rows are filled once, by the first draw
-        rdom = flat.var_dom[pv_all]
-        rr = np.zeros((pv_all.size, 8), dtype=np.int32)
-        rr[:, 0], rr[:, 1] = pv_all, self.np_host[pv_all]
-        rr[:, 2:4] = np.ascontiguousarray(flat.dom_lo[rdom], dtype=np.float64).view(np.int32).reshape(-1, 2)
-        rr[:, 4:6] = np.ascontiguousarray(flat.dom_hi[rdom], dtype=np.float64).view(np.int32).reshape(-1, 2)
-        host_lists['resample_vars'] = rr if pv_all.size else None
-        self._static_rows = False
-        static = np.flatnonzero(~(flat.var_hidden & flat.var_cont))
-        host_lists['_static_idx'] = static.astype(np.int64) if static.size else None
-        # rows longer than prop_slice entries go in as slices of that length, a wavefront each, ahead of the ordinary records
-        self.prop_hub = self.prop_partial = None
-        self.n_prop_hub = 0
-        hubs = np.flatnonzero(pdeg > self.prop_slice) if self.sliced_proposal else np.zeros(0, dtype=np.int64)
-        if hubs.size:
-            L = int(self.prop_slice)
-            nsl = (pdeg[hubs] + L - 1) // L
-            first = np.concatenate([[0], np.cumsum(nsl)[:-1]])
-            owner = np.repeat(np.arange(hubs.size), nsl)
-            within = np.arange(int(nsl.sum())) - first[owner]
-            sl = np.zeros((owner.size, 8), dtype=np.int32)
-            sl[:, 0], sl[:, 2], sl[:, 3] = pd[hubs[owner], 0], pd[hubs[owner], 2], pd[hubs[owner], 3]
-            sl[:, 1] = -np.minimum(L, pdeg[hubs][owner] - within * L)
-            sl[:, 4], sl[:, 5] = within * L, np.arange(owner.size)
-            ph = np.zeros((hubs.size, 4), dtype=np.int32)
-            ph[:, 0], ph[:, 1], ph[:, 2] = pv[hubs], first, nsl
-            pd = np.concatenate([sl, np.delete(pd, hubs, axis=0)])
-            host_lists['prop_hub'], self.n_prop_hub = ph, int(hubs.size)
-            self.prop_partial = dg.zeros(owner.size, 2)
-        host_lists['prop_desc'] = np.ascontiguousarray(pd) if pv.size else None
-        self.n_prop_desc = int(pd.shape[0])
-        # the v -> f half's split of the hidden variables (include/lhvi.h, lhvi_pbp_t.v2f_wide / v2f_narrow)
-        hidden_v = np.flatnonzero(flat.var_hidden)
-        if owned is not None:
-            hidden_v = hidden_v[hidden_v < owned]
-        narrow = self.np_host[hidden_v] <= 4
-        self.v2f_lists = None
-        hub = ~narrow & (np.diff(flat.var_ptr)[hidden_v] > 64) & (self.np_host[hidden_v] <= 64)
-        mid16 = ~narrow & ~hub & (self.np_host[hidden_v] <= 16)
-        mid32 = ~narrow & ~hub & ~mid16 & (self.np_host[hidden_v] <= 32)
-        if self.packed_v2f and hidden_v.size and (narrow.any() or hub.any() or mid16.any() or mid32.any()):
-            wide = ~narrow & ~hub & ~mid16 & ~mid32
-            parts = (('wide', wide), ('narrow', narrow), ('hub', hub), ('mid16', mid16), ('mid32', mid32))
-            for name, m in parts:
-                host_lists['v2f_' + name] = hidden_v[m].astype(np.int32) if m.any() else np.zeros(1, dtype=np.int32)
-            if os.environ.get('LHVI_PBP_V2F_REC', '1') != '0':
-                host_lists['v2f_wide'] = self._v2f_records(flat, hidden_v[wide])
-        # ---- the fused per-variable kernel's records (lhvi_pbp_var_fused) and what is left for the three kernels
-        self._fused = None
-        pT = sizes[pdom] if pv.size else np.zeros(0, dtype=np.int64)
-        fused_max = int(os.environ.get('LHVI_PBP_FUSED_MAX', self.fused_max_particles))          # (tuning aid: scripts/diag/fused_batch.sh)
-        fz = (pdeg <= min(64, self.prop_slice)) & (pT <= 64) & (n <= min(64, fused_max)) if pv.size else np.zeros(0, dtype=bool)
-        if (self.fused_var_kernel and os.environ.get('LHVI_PBP_FUSED', '1') != '0') and owned is None and self.sampler == 'device' and self.listed_proposal and self.listed_resample \
-                and 'v2f_wide' in host_lists and fz.any():
-            k16 = fz & (n <= 16) & (pT <= 32)
-            k32a = fz & (n <= 32) & ~k16 & (pT <= 32)
-            k32b = fz & (n <= 32) & ~k16 & ~k32a
-            # 32 < n <= 64: one variable per wavefront (lhvi_pbp_var_fused64), a list of its own, always in the sixteen-word layout
-            k64a = fz & (n > 32) & (pT <= 32)
-            k64b = fz & (n > 32) & ~k64a
-            # sixteen words per variable (LHVI_PBP_FUSED_RECORDS16): the eight of include/lhvi.h, then np, var_ptr[v] and the first six
-            # incident edges -- the kernel's row loads then hang on one load behind the record (LHVI_PBP_FUSED_REC16=0: eight words)
-            wide_rec = os.environ.get('LHVI_PBP_FUSED_REC16', '1') != '0'
-            fd = np.zeros((pv.size, 16 if wide_rec else 8), dtype=np.int32)
-            fd[:, 0], fd[:, 1], fd[:, 2], fd[:, 3] = pv, pdeg, flat.dom_ptr[pdom], pT
-            fd[:, 4:6] = np.ascontiguousarray(flat.dom_lo[pdom], dtype=np.float64).view(np.int32).reshape(-1, 2)
-            fd[:, 6:8] = np.ascontiguousarray(flat.dom_hi[pdom], dtype=np.float64).view(np.int32).reshape(-1, 2)
-            def sixteen(rec8):
-                rec = np.zeros((pv.size, 16), dtype=np.int32)
-                rec[:, :8] = rec8
-                rec[:, 8], rec[:, 9] = self.np_host[pv], flat.var_ptr[pv]
-                for k in range(6):
-                    has = pdeg > k
-                    rec[has, 10 + k] = flat.var_edge[pbase[has] + k]
-                return rec
-            if wide_rec:
-                fd[:, 8], fd[:, 9] = self.np_host[pv], flat.var_ptr[pv]
-                for k in range(6):
-                    has = pdeg > k
-                    fd[has, 10 + k] = flat.var_edge[pbase[has] + k]
-                self.flags |= _abi.PBP_FUSED_RECORDS16
-            small = np.concatenate([fd[k16], fd[k32a], fd[k32b]])
-            host_lists['fused_desc'] = np.ascontiguousarray(small) if small.size else np.zeros((1, fd.shape[1]), dtype=np.int32)
-            if k64a.any() or k64b.any():
-                fd64 = fd if wide_rec else sixteen(fd[:, :8])
-                host_lists['fused64_desc'] = np.ascontiguousarray(np.concatenate([fd64[k64a], fd64[k64b]]))
-            fused_var = np.zeros(flat.V, dtype=bool)
-            fused_var[pv[fz]] = True
-            # the rest: proposal records (slices of hub rows sit at the head of pd and are never fused), sampler records, v -> f lists
-            keep = ~fused_var[pd[:, 0]]
-            host_lists['prop_desc_rest'] = np.ascontiguousarray(pd[keep]) if keep.any() else np.zeros((1, 8), dtype=np.int32)
-            rkeep = ~fused_var[rr[:, 0]]
-            host_lists['resample_rest'] = np.ascontiguousarray(rr[rkeep]) if rkeep.any() else np.zeros((1, 8), dtype=np.int32)
-            rest_parts = []
-            if 'v2f_wide' in host_lists:
-                for name, m in parts:
-                    vs = hidden_v[m]
-                    vs = vs[~fused_var[vs]]
-                    host_lists['v2f_rest_' + name] = (self._v2f_records(flat, vs) if name == 'wide' and os.environ.get('LHVI_PBP_V2F_REC', '1') != '0' else
-                                                      vs.astype(np.int32) if vs.size else np.zeros(1, dtype=np.int32))
-                    rest_parts.append((name, int(vs.size)))
-            self._fused = dict(counts=(int(k16.sum()), int(k32a.sum()), int(k32b.sum())), counts64=(int(k64a.sum()), int(k64b.sum())),
-                               n_prop_rest=int(keep.sum()), n_resample_rest=int(rkeep.sum()), rest_parts=rest_parts)
-        dev_lists = _abi.upload(host_lists)
+        dev_lists = _abi.upload(plan.host)                      # the per-variable lists go to the device in one copy
         for name in ('np_dev', 'resample_vars', '_static_idx', 'prop_desc'):
             setattr(self, name, dev_lists[name])
-        if self._fused is not None:
-            F = self._fused
-            F['desc'], F['prop_desc_rest'], F['resample_rest'] = dev_lists['fused_desc'], dev_lists['prop_desc_rest'], dev_lists['resample_rest']
-            F['desc64'] = dev_lists.get('fused64_desc')
-            F['v2f_rest'] = tuple(x for name, cnt in F['rest_parts'] for x in (dev_lists['v2f_rest_' + name], cnt)) if F['rest_parts'] else None
-        if 'prop_hub' in dev_lists:
-            self.prop_hub = dev_lists['prop_hub']
-        if 'v2f_wide' in dev_lists:
-            self.v2f_lists = tuple(x for name, m in parts for x in (dev_lists['v2f_' + name], int(m.sum())))
-            if os.environ.get('LHVI_PBP_V2F_REC', '1') != '0':          # (tuning aid: scripts/diag/v2f_records.sh)
-                self.flags |= _abi.PBP_V2F_RECORDS         # the wide list travels as records: _v2f_records
+        self.n_prop_desc, self.n_prop_hub, self.prop_hub = plan.n_prop_desc, plan.n_prop_hub, dev_lists.get('prop_hub')
+        self.v2f_lists = plan.v2f.on(dev_lists, 'v2f_') if plan.v2f is not None else None
+        self._fused = plan.fused.on(dev_lists) if plan.fused is not None else None
         # static work lists of the f -> v half sweep (which kernel serves which edge)
         pad = torch.zeros(1, dtype=torch.int32, device=dg.device)       # keeps the pointers non-null when a list is empty
         self.cq_edges = pad[:0]
@@ -293,40 +166,18 @@ class _ParticleSweep:
             desc = torch.empty(nf * _abi.PBP_DESC_BYTES, dtype=torch.uint8, device=dg.device)
             _abi.check(_abi.lib().lhvi_pbp_describe(dg.g, dg.p, self._struct(), _abi.ptr(self.fast_edges), nf,
                                                     _abi.ptr(desc), _abi.stream_ptr()))
-            # split off the edges the specialised kernel serves (descriptor words: 4 = class, 6 = potential kind, 7 = nj, 8 = np, 9 = T)
-            words = desc.view(torch.int32).view(nf, _abi.PBP_DESC_BYTES // 4)
-            # (a uniform grid of up to 128 integral points is tabulated by the recurrence, whatever np + T; otherwise two rounds of 64 points)
-            base = (words[:, 4] == 1) & (words[:, 6] != 4)
-            # edges with few particles on both sides go four / two to a wavefront, whatever their number of integral points
-            # (include/lhvi.h, small16_desc)
-            small16 = small32 = torch.zeros_like(base)
-            if self.small_f2v:
-                small16 = base & (words[:, 7] <= 16) & (words[:, 8] <= 16)
-                small32 = base & ~small16 & (words[:, 7] <= 32) & (words[:, 8] <= 32)
+            # split off the edges the specialised kernels serve (lhvi/pbp_plan.py, f2v_split)
+            heavy, small16, small32, light, rest, self.heavy_terms, self.heavy_grid_terms = pbp_plan.f2v_split(
+                desc.view(torch.int32).view(nf, _abi.PBP_DESC_BYTES // 4), self.small_f2v, self.long_grid_min_edges)
             small = small16 | small32
-            on_recurrence = (words[:, 15] == 1) & (words[:, 7] >= 24) & (words[:, 9] <= 128) & (words[:, 8] <= 128)
-            two_rounds = words[:, 8] + words[:, 9] <= 128
-            if int((on_recurrence & ~two_rounds & ~small).sum().item()) < self.long_grid_min_edges:
-                on_recurrence = two_rounds          # (a short list would only add a launch to a launch-bound sweep)
-            heavy = (base & (words[:, 7] <= 64) & (two_rounds | on_recurrence)) | small       # the heavy CLASS: the three lists together
             rows = desc.view(nf, _abi.PBP_DESC_BYTES)
             self.small16_desc, self.small32_desc = rows[small16].contiguous(), rows[small32].contiguous()
             self.n_small16, self.n_small32 = int(self.small16_desc.shape[0]), int(self.small32_desc.shape[0])
             self.n_heavy_class = int(heavy.sum().item())
             self.heavy_desc = rows[heavy & ~small].contiguous()
             self.n_heavy = int(self.heavy_desc.shape[0])
-            # (output point, partner particle) terms of the heavy kernel: sum over its edges of (np + T) * nj
-            hw = words[heavy].to(torch.int64)
-            self.heavy_terms = int(((hw[:, 8] + hw[:, 9]) * hw[:, 7]).sum().item())
-            # of those, the terms at the integral points of edges served by the grid recurrence (word 15: uniform grid;
-            # at least 24 partner particles, T <= 128; the kernel's range guard is data dependent and assumed to pass)
-            # (the few-particle kernel takes the recurrence for every edge with a uniform grid, whatever its particle count)
-            on_grid = (hw[:, 15] == 1) & (hw[:, 9] <= 128) & ((hw[:, 7] >= 24) | small[heavy])
-            self.heavy_grid_terms = int((hw[:, 9] * hw[:, 7])[on_grid].sum().item())
-            light = ~heavy & (words[:, 14] != 0)          # word 14: set by lhvi_pbp_describe for the light kernel's edges
             self.light_desc = rows[light].contiguous()
             self.n_light = int(self.light_desc.shape[0])
-            rest = ~heavy & ~light
             self.fast_desc = rows[rest].contiguous()
             all_fast = self.fast_edges
             self.fast_edges = all_fast[rest].contiguous()
@@ -336,19 +187,6 @@ class _ParticleSweep:
                                     fast=first_part(self.fast_edges), small16=first_part(all_fast[small16]),
                                     small32=first_part(all_fast[small32]))
             self._build_pairs(key_dev)
-
-    def _v2f_records(self, flat, vs):
-        """``lhvi_pbp_t.v2f_wide`` as records (LHVI_PBP_V2F_RECORDS, include/lhvi.h): variable, incident edges, particles, domain and
-        the first four incident edges in row order, so that the kernel's row loads hang on one scalar load"""
-        rec = np.zeros((max(int(vs.size), 1), 8), dtype=np.int32)
-        if vs.size:
-            deg = np.diff(flat.var_ptr)[vs]
-            rec[:, 0], rec[:, 1], rec[:, 2], rec[:, 3] = vs, deg, self.np_host[vs], flat.var_dom[vs]
-            base = flat.var_ptr[vs].astype(np.int64)
-            for k in range(4):
-                if flat.var_edge.size:
-                    rec[:, 4 + k] = flat.var_edge[np.minimum(base + np.minimum(k, np.maximum(deg - 1, 0)), flat.var_edge.size - 1)]
-        return rec
 
     def _build_pairs(self, key_dev):
         """``lhvi_pbp_t.pair_desc``: one record per HybridQuadratic(1 discrete, 1 continuous) factor from the per-edge light
@@ -402,6 +240,17 @@ class _ParticleSweep:
         self.pair_desc, self.n_pair = out, n1 + n2
         self.part_counts['pair'] = first
 
+    def _plan_options(self):
+        """what the variable-side plan depends on besides the graph: the class attributes and the tuning variables, each read here"""
+        env = os.environ.get
+        return pbp_plan.PlanOptions(
+            sampler_on_device=self.sampler == 'device', listed_proposal=self.listed_proposal, listed_resample=self.listed_resample,
+            sliced_proposal=self.sliced_proposal, prop_slice=self.prop_slice, packed_v2f=self.packed_v2f,
+            v2f_records=env('LHVI_PBP_V2F_REC', '1') != '0',                                   # (tuning aid: scripts/diag/v2f_records.sh)
+            fused=self.fused_var_kernel and env('LHVI_PBP_FUSED', '1') != '0',
+            fused_max_particles=int(env('LHVI_PBP_FUSED_MAX', self.fused_max_particles)),      # (tuning aid: scripts/diag/fused_batch.sh)
+            fused_records16=env('LHVI_PBP_FUSED_REC16', '1') != '0')
+
     def _struct(self):
         s = _abi.PbpStruct()
         s.n, s.T, s.flags = self.n, self.T, self.flags
@@ -422,10 +271,7 @@ class _ParticleSweep:
             s.pair_desc, s.n_pair = _abi.ptr(self.pair_desc), int(self.n_pair)
         s.cq_desc, s.n_cq = _abi.ptr(getattr(self, 'cq_desc', None)), int(getattr(self, 'n_cq', 0))
         if getattr(self, 'v2f_lists', None) is not None:
-            w, nw, nr, nn, hb, nh, m16, n16, m32, n32 = self.v2f_lists
-            s.v2f_wide, s.n_v2f_wide, s.v2f_narrow, s.n_v2f_narrow = _abi.ptr(w), nw, _abi.ptr(nr), nn
-            s.v2f_hub, s.n_v2f_hub = _abi.ptr(hb), nh
-            s.v2f_mid16, s.n_v2f_mid16, s.v2f_mid32, s.n_v2f_mid32 = _abi.ptr(m16), n16, _abi.ptr(m32), n32
+            self.v2f_lists.install(s)
         s.f2v_ticket = _abi.ptr(self.f2v_ticket) if self.dynamic_f2v else None
         if self.listed_proposal and getattr(self, 'prop_desc', None) is not None:
             s.prop_desc, s.n_prop_desc = _abi.ptr(self.prop_desc), self.n_prop_desc
@@ -471,28 +317,25 @@ class _ParticleSweep:
         if self.sampler == 'device':
             self.old_particles, self.particles = self.particles, self.old_particles
             s = self._struct()
-            gid = _abi.ptr(getattr(self, 'var_gid', None))
+            listed = self.listed_resample and self.n <= 64 and getattr(self, 'resample_vars', None) is not None
+            lst = None
             if rest_only:
-                F = self._fused
-                if F['n_resample_rest']:
-                    s.resample_vars, s.n_resample_vars = _abi.ptr(F['resample_rest']), int(F['n_resample_rest'])
-                    _abi.check(l.lhvi_pbp_resample_uniq(self.dg.g, s, gid, int(self.seed), int(k), _abi.ptr(self.particles), _abi.ptr(self.uniq), st))
-                self._views, self._batched = {}, {}
-                return
-            if self.listed_resample and self.n <= 64 and getattr(self, 'resample_vars', None) is not None:
-                if not self._static_rows:
-                    # first device draw of this state: the full (unlisted) draw into the CURRENT buffer only -- the other one may
-                    # hold the particles the v -> f messages were evaluated at (a coarse-to-fine state, or one a host sampler
-                    # filled) and must keep them; it only receives the rows no later listed draw writes: the states of the
-                    # discrete variables and the rows of the observed ones
-                    _abi.check(l.lhvi_pbp_resample_uniq(self.dg.g, s, gid, int(self.seed), int(k), _abi.ptr(self.particles), _abi.ptr(self.uniq), st))
-                    if self._static_idx is not None:
-                        self.old_particles.index_copy_(0, self._static_idx, self.particles.index_select(0, self._static_idx))
-                    self._static_rows = True
-                    self._views, self._batched = {}, {}
-                    return
-                s.resample_vars, s.n_resample_vars = _abi.ptr(self.resample_vars), int(self.resample_vars.shape[0])
-            _abi.check(l.lhvi_pbp_resample_uniq(self.dg.g, s, gid, int(self.seed), int(k), _abi.ptr(self.particles), _abi.ptr(self.uniq), st))
+                lst = (self._fused.resample_rest, self._fused.n_resample_rest)
+            elif listed and self._static_rows:
+                lst = (self.resample_vars, int(self.resample_vars.shape[0]))
+            # else the full (unlisted) draw.  As the first device draw of a listed state it goes into the CURRENT buffer only -- the
+            # other one may hold the particles the v -> f messages were evaluated at (a coarse-to-fine state, or one a host sampler
+            # filled) and must keep them; it only receives the rows no later listed draw writes: the states of the discrete
+            # variables and the rows of the observed ones
+            if lst is not None:
+                s.resample_vars, s.n_resample_vars = _abi.ptr(lst[0]), lst[1]
+            if lst is None or lst[1]:
+                _abi.check(l.lhvi_pbp_resample_uniq(self.dg.g, s, _abi.ptr(getattr(self, 'var_gid', None)), int(self.seed), int(k),
+                                                    _abi.ptr(self.particles), _abi.ptr(self.uniq), st))
+            if listed and not self._static_rows:
+                if self._static_idx is not None:
+                    self.old_particles.index_copy_(0, self._static_idx, self.particles.index_select(0, self._static_idx))
+                self._static_rows = True
             self._views, self._batched = {}, {}
             return
         elif callable(self.sampler):
@@ -522,22 +365,15 @@ class _ParticleSweep:
             # (lhvi_pbp_var_fused, into the buffer the swap below makes current); the three kernels serve the other variables
             F = self._fused
             s = self._struct()
-            n16, n32a, n32b = F['counts']
-            if n16 + n32a + n32b:
-                _abi.check(l.lhvi_pbp_var_fused(g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev),
-                                                _abi.ptr(getattr(self, 'var_gid', None)), int(self.seed), int(self._draws),
-                                                _abi.ptr(self.old_particles), _abi.ptr(self.uniq), _abi.ptr(F['desc']), n16, n32a, n32b, st))
-            if F['desc64'] is not None:
-                n64a, n64b = F['counts64']
-                _abi.check(l.lhvi_pbp_var_fused64(g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev),
-                                                  _abi.ptr(getattr(self, 'var_gid', None)), int(self.seed), int(self._draws),
-                                                  _abi.ptr(self.old_particles), _abi.ptr(self.uniq), _abi.ptr(F['desc64']), n64a, n64b, st))
-            w, nw, nr, nn, hb, nh, m16, c16, m32, c32 = F['v2f_rest']
-            s.v2f_wide, s.n_v2f_wide, s.v2f_narrow, s.n_v2f_narrow = _abi.ptr(w), nw, _abi.ptr(nr), nn
-            s.v2f_hub, s.n_v2f_hub = _abi.ptr(hb), nh
-            s.v2f_mid16, s.n_v2f_mid16, s.v2f_mid32, s.n_v2f_mid32 = _abi.ptr(m16), c16, _abi.ptr(m32), c32
+            args = (g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev), _abi.ptr(getattr(self, 'var_gid', None)),
+                    int(self.seed), int(self._draws), _abi.ptr(self.old_particles), _abi.ptr(self.uniq))
+            if sum(F.counts):
+                _abi.check(l.lhvi_pbp_var_fused(*args, _abi.ptr(F.desc), *F.counts, st))
+            if F.desc64 is not None:
+                _abi.check(l.lhvi_pbp_var_fused64(*args, _abi.ptr(F.desc64), *F.counts64, st))
+            F.v2f_rest.install(s)
             _abi.check(l.lhvi_pbp_v2f(g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), st))
-            s.prop_desc, s.n_prop_desc = _abi.ptr(F['prop_desc_rest']), int(F['n_prop_rest'])
+            s.prop_desc, s.n_prop_desc = _abi.ptr(F.prop_desc_rest), F.n_prop_rest
             _abi.check(l.lhvi_pbp_proposal(g, s, _abi.ptr(self.f2v), _abi.ptr(self.eta), _abi.ptr(self.q_dev), st))
             self._generate_sample(rest_only=True)
             self._launch_f2v(self._struct(), f2v_events)

@@ -1083,11 +1083,11 @@ def test_packed_v2f_kernel_does_not_change_results(api, solver):
             bp.run(4)
         runs.append(bp)
     a, b = runs
-    assert a.v2f_lists is not None and a.v2f_lists[3] > 0 and a.v2f_lists[5] == 0 and b.v2f_lists is None
+    assert a.v2f_lists is not None and a.v2f_lists.n_narrow > 0 and a.v2f_lists.n_hub == 0 and b.v2f_lists is None
     if solver in ('hlbp', 'epbp10', 'epbp16'):
-        assert a.v2f_lists[7] > 0 and a.v2f_lists[1] == 0
+        assert a.v2f_lists.n_mid16 > 0 and a.v2f_lists.n_wide == 0
     if solver in ('epbp24', 'epbp32'):
-        assert a.v2f_lists[9] > 0 and a.v2f_lists[1] == 0
+        assert a.v2f_lists.n_mid32 > 0 and a.v2f_lists.n_wide == 0
     for name in ('v2f', 'f2v', 'q_dev', 'eta', 'particles'):
         assert torch.equal(getattr(a, name), getattr(b, name)), name
 
@@ -1248,7 +1248,7 @@ def test_v2f_hub_kernel_matches_the_one_wave_path(api):
             bp.sweep(last=False)
         runs.append(bp)
     a, b, c = runs
-    assert a.v2f_lists[5] > 0
+    assert a.v2f_lists.n_hub > 0
     hid = flat.var_hidden[flat.edge_var]
     live = hid[:, None] & (np.arange(n)[None, :] < a.np_host[flat.edge_var][:, None])
     np.testing.assert_allclose(a.v2f.cpu().numpy()[live], b.v2f.cpu().numpy()[live], rtol=1e-11, atol=1e-10)
