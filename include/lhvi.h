@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 22  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 23  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -45,7 +45,8 @@ extern "C" {
                               * 19: lhvi_gm_fit, lhvi_gm_fit_host, LHVI_GMFIT_MAX_K;
                               * 20: lhvi_npvi_opt_t, lhvi_npvi_*, LHVI_NPVI_MAX_K, LHVI_NPVI_MAX_SLOTS, LHVI_VI_GAUSSIAN_PDF;
                               * 21: lhvi_oneshot_*;
-                              * 22: lhvi_pbp_var_fused64 */
+                              * 22: lhvi_pbp_var_fused64;
+                              * 23: lhvi_gauss_chain_*, LHVI_GAUSS_CHAIN_MAX_BLOCK */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -805,6 +806,25 @@ int lhvi_gauss_exact_cov(int64_t N, const double* Xt, int32_t S, const int32_t* 
  * row-major (its lower triangle is read), b, mu, var [N], logdet [1]; bad_col (may be NULL): the first column with a pivot <= 0
  * or NaN, else -1.  LHVI_E_NOT_PD when there is one. */
 int lhvi_gauss_exact_host(int64_t N, const double* J, const double* b, double* mu, double* var, double* logdet, int64_t* bad_col);
+
+/* ---- Exact Gaussian chains: batched block-tridiagonal fp64 Cholesky with the covariance recursion (the conditioned relational
+ * Kalman filters of Demo/RKF; csrc/gauss_chain.hip, csrc/gauss_chain.hpp, docs/kernels_gauss_chain.md) --------------------------
+ * B independent systems of M blocks of edge n, all row-major: D [B][M][n][n] the symmetric diagonal blocks of J (the lower
+ * triangle is read), O [B][M-1][n][n] = J[block t, block t + 1] (rows: block t; may be NULL when M == 1), h [B][M][n].
+ * Results: mu, var [B][M][n]; cov [B][M][n][n] = Sig[t, t] and cross [B][M-1][n][n] = Sig[t, t + 1], each written unless NULL;
+ * logdet [B] = log det J; bad [B][2] = (block, column) of the first pivot <= 0 or NaN of a system, (-1, -1) when there is
+ * none: such a pivot is taken as 1, the kernel ends normally, that system's results are meaningless and the others' are
+ * untouched.  ws: lhvi_gauss_chain_ws_doubles(B, M, n) doubles (W_t, C_t, y_t of every block for the backward pass, and
+ * the working tiles of a system when n > 32).  One workgroup per system, time sequential; fixed order, no atomics: a
+ * system's bits do not depend on B or on its position.  B == 0 or M == 0: nothing is launched.
+ * LHVI_E_ARG: n < 1, negative B or M, a NULL array.  LHVI_E_UNSUPPORTED: n > LHVI_GAUSS_CHAIN_MAX_BLOCK. */
+#define LHVI_GAUSS_CHAIN_MAX_BLOCK 128
+size_t lhvi_gauss_chain_ws_doubles(int64_t B, int64_t M, int64_t n);
+int lhvi_gauss_chain_solve(int64_t B, int64_t M, int64_t n, const double* D, const double* O, const double* h, double* ws, double* mu,
+                           double* var, double* cov, double* cross, double* logdet, int32_t* bad, void* stream);
+/* the same on the HOST through the same code with one "lane" (host pointers); LHVI_E_NOT_PD when some system has a bad pivot */
+int lhvi_gauss_chain_host(int64_t B, int64_t M, int64_t n, const double* D, const double* O, const double* h, double* ws, double* mu,
+                          double* var, double* cov, double* cross, double* logdet, int32_t* bad);
 
 /* ---- Conditional queries on a fitted mixture belief (osi/mixture_beliefs.py:505-746, osi/utils.py:21-98; csrc/mixture.hip,
  * csrc/mixture.hpp) ---------------------------------------------------------------------------------------------------------

@@ -3,8 +3,10 @@
 ``KalmanFilter(domain, A, q, C, r).grounded_graph(T, data)`` -> ``(Graph, rv table [t][i])``.  The transition density
 exp(-|x_{t+1} - A' x_t|^2 / 2q) is expanded into pairwise ``XYPotential`` and unary ``X2Potential`` factors, the
 observation density into one ``LinearGaussianPotential`` per observed entry; ``data[i, t] == 5000`` marks "missing".
-Model construction only (host side).  ``grounded_flat`` builds the same graph straight into a ``FlatGraph`` (no per-node
-objects): same variable order, same factor order, potentials deduplicated by value.
+Model construction on the host; ``exact`` / ``exact_batch`` solve the conditioned filter exactly on the device through its
+closed-form block-tridiagonal precision matrix (``block_tridiagonal``, lhvi/gauss_chain.py).  ``grounded_flat`` builds the same
+graph straight into a ``FlatGraph`` (no per-node objects): same variable order, same factor order,
+potentials deduplicated by value.
 """
 from __future__ import annotations
 
@@ -137,3 +139,65 @@ class KalmanFilter:
         flat = build_flat(fac_ptr, np.concatenate(edge_parts).astype(np.int32), np.concatenate(pot_parts).astype(np.int32), specs, value,
                           np.zeros(V, dtype=np.int32), [self.domain])
         return flat, state_id
+
+    def block_tridiagonal(self, num_t_steps, data):
+        """The conditioned model of ``grounded_flat`` in closed form: ``(D [T-1][n][n], O [T-2][n][n], h [T-1][n], const)`` of
+        ``log p = -x' J x / 2 + h' x + const`` over the hidden states, block t - 1 = the states of step t (``J`` block tridiagonal
+        with diagonal blocks ``D`` and ``J[block, next block] = O``).  With G = A A', c = diag(C) and has[t, i] = "entry i of step t
+        is observed": D_t = (I + [t < T-1] G) / q + diag(has_t c^2 / r), O_t = -A / q, h_t = has_t c y_t / r (+ A' x_0 / q at
+        t = 1), const = -sum_obs y^2 / (2 r)."""
+        A, q = np.asarray(self.transition_coeff, dtype=np.float64), float(self.transition_variance)
+        c, r = np.diag(np.asarray(self.observation_coeff, dtype=np.float64)).copy(), float(self.observation_variance)
+        data = np.asarray(data, dtype=np.float64)
+        n, T = A.shape[0], int(num_t_steps)
+        M = max(T - 1, 0)
+        y = data[:, 1:T].T                                        # [M][n]
+        has = y != MISSING
+        yo = np.where(has, y, 0.0)
+        G = A @ A.T
+        D = np.empty((M, n, n))
+        D[:] = (np.eye(n) + G) / q
+        if M:
+            D[M - 1] = np.eye(n) / q
+        idx = np.arange(n)
+        D[:, idx, idx] += has * (c * c / r)
+        O = np.empty((max(M - 1, 0), n, n))
+        O[:] = -A / q
+        h = has * (c / r) * yo
+        if M:
+            h[0] += A.T @ data[:, 0] / q
+        return D, O, h, float(-(yo * yo).sum() / (2 * r))
+
+    def exact(self, num_t_steps, data, keep_cov=False, host=False):
+        """Exact smoothed marginals of the conditioned filter on the device: ``mu [T][n]``, ``var [T][n]``, ``logZ`` (and, with
+        ``keep_cov``, ``cov [T-1][n][n]`` and ``cross [T-2][n][n]`` of the hidden steps); row 0 is the evidence with variance 0.
+        ``host=True``: the CPU twin (the CPU suite's route)."""
+        out = exact_batch([self], num_t_steps, data, keep_cov=keep_cov, host=host)
+        return tuple(o[0] for o in out)
+
+
+def exact_batch(filters, num_t_steps, data, keep_cov=False, host=False):
+    """``KalmanFilter.exact`` for several filters of equal n on the same data in one launch (the demos' loop over parameter sets):
+    ``mu [B][T][n]``, ``var [B][T][n]``, ``logZ [B]`` (and ``cov``, ``cross`` with ``keep_cov``)"""
+    from .gauss_chain import LOG_2PI, _bad_error, host_solve_block_tridiagonal, solve_block_tridiagonal
+    data = np.asarray(data, dtype=np.float64)
+    T, n = int(num_t_steps), data.shape[0]
+    parts = [kf.block_tridiagonal(T, data) for kf in filters]
+    for kf, p in zip(filters, parts):
+        if p[0].shape[1:] != (n, n):
+            raise ValueError('a filter of %d states on data of %d rows: exact_batch takes filters of equal n' % (p[0].shape[1], n))
+    B, M = len(filters), max(T - 1, 0)
+    D, h = np.stack([p[0] for p in parts]), np.stack([p[2] for p in parts])
+    O = np.stack([p[1] for p in parts]) if M > 1 else None
+    if host:
+        out = host_solve_block_tridiagonal(D, O, h, keep_cov=keep_cov)
+        if (out[-1][:, 0] >= 0).any():
+            raise _bad_error(out[-1], 'filter')
+        out = out[:-1]
+    else:
+        out = solve_block_tridiagonal(D, O, h, keep_cov=keep_cov)
+    mu, var = np.zeros((B, T, n)), np.zeros((B, T, n))
+    mu[:, 0], mu[:, 1:], var[:, 1:] = data[:, 0], out[0], out[1]
+    const = np.array([p[3] for p in parts])
+    logZ = M * n / 2 * LOG_2PI - 0.5 * out[2] + 0.5 * (out[0] * h).reshape(B, -1).sum(axis=1) + const
+    return (mu, var, logZ) + tuple(out[3:])
