@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 23  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 24  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -46,7 +46,8 @@ extern "C" {
                               * 20: lhvi_npvi_opt_t, lhvi_npvi_*, LHVI_NPVI_MAX_K, LHVI_NPVI_MAX_SLOTS, LHVI_VI_GAUSSIAN_PDF;
                               * 21: lhvi_oneshot_*;
                               * 22: lhvi_pbp_var_fused64;
-                              * 23: lhvi_gauss_chain_*, LHVI_GAUSS_CHAIN_MAX_BLOCK */
+                              * 23: lhvi_gauss_chain_*, LHVI_GAUSS_CHAIN_MAX_BLOCK;
+                              * 24: lhvi_gm_kl, lhvi_gm_kl_ws_doubles, lhvi_gm_kl_host, LHVI_GMKL_MAX_PANELS */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -922,6 +923,37 @@ int lhvi_gm_fit(int32_t R, int64_t n, int32_t K, const double* x, const double* 
 int lhvi_gm_fit_host(int32_t R, int64_t n, int32_t K, const double* x, const double* init, double reg_covar, double tol,
                      int32_t max_iter, int32_t kmeans_its, double* w, double* mu, double* var, double* lower_bound,
                      int32_t* n_iter, int32_t* flags);
+
+/* ---- KL(p || q) of scalar Gaussian mixtures, a batch of rows in one launch (utils.kl_continuous_logpdf where both sides are
+ * mixture marginals; csrc/gmkl.hip, csrc/gmkl.hpp, docs/kernels_gmkl.md) ------------------------------------------------------
+ * Row r: p = (wp, mup, varp)[r][0 .. Kp), q = (wq, muq, varq)[r][0 .. Kq) (row-major [R][K]; a component of weight 0 is skipped,
+ * so ragged rows are padded with zeros), bounds a[r] <= b[r] (+-inf allowed).  The integrand is f(x) = exp(lp) (lp - lq) with
+ * lp, lq the log densities by a max-shifted log-sum-exp, and f = 0 where exp(lp) == 0.
+ *   range     L = max(a, min_k(mu_k - 10 sd_k)), U = min(b, max_k(mu_k + 10 sd_k)) over p's components; U <= L: kl = 0, status 0
+ *   panels    P = ceil((U - L) / (8 sd_min)) equal panels, sd_min of p's narrowest component, at least 1 and at most
+ *             LHVI_GMKL_MAX_PANELS (the cap sets status bit 1; the result is still returned): no component of p can fall
+ *             between the nodes of the first pass
+ *   pass 1    QUADPACK's 21-point Gauss-Kronrod rule with its error estimate (dqk21) on every panel; area0 = the sum of the
+ *             panel results in order; bound = max(epsabs, epsrel |area0|)
+ *   pass 2    panel by panel, left to right, depth-first bisection: an interval is accepted when its estimate is
+ *             <= bound * width / (U - L), or at depth 40 (status bit 0 when the estimate is not met there); an interval whose
+ *             estimate is not finite, and every interval after 4096 bisections of the row, is accepted as it stands (status
+ *             bit 0).  Accepted results and estimates are added in that left-to-right order.
+ * Outputs per row: kl, abserr (the sum of the accepted estimates), status, neval (integrand evaluations); abserr, status and
+ * neval may be NULL.  A row with a non-finite parameter or bound NaN, a variance <= 0, a negative weight or all-zero weights
+ * on either side gets kl = abserr = NaN and status bit 2; the other rows are unaffected.  Where q underflows and p does not the
+ * integrand, and with it kl, is +inf.  One wavefront per row, no atomics: a row's bits depend neither on R, nor on its position,
+ * nor on the run.  ws: lhvi_gm_kl_ws_doubles(R) doubles, or NULL when that is 0 (it is: the panel list and the stack of a row are
+ * in LDS).  LHVI_E_ARG: R < 1, Kp < 1, Kq < 1, a NULL required pointer, epsabs or epsrel negative or NaN. */
+#define LHVI_GMKL_MAX_PANELS 1024
+size_t lhvi_gm_kl_ws_doubles(int32_t R);
+int lhvi_gm_kl(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp, int32_t Kq, const double* wq,
+               const double* muq, const double* varq, const double* a, const double* b, double epsabs, double epsrel, double* ws,
+               double* kl, double* abserr, int32_t* status, int32_t* neval, void* stream);
+/* the same on the HOST through the device's code (csrc/gmkl.hpp), the nodes one after another */
+int lhvi_gm_kl_host(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp, int32_t Kq, const double* wq,
+                    const double* muq, const double* varq, const double* a, const double* b, double epsabs, double epsrel,
+                    double* kl, double* abserr, int32_t* status, int32_t* neval);
 
 /* ---- Nonparametric variational inference (osi/NPVI.py: Gershman-style NPVI on a K-component product mixture; csrc/npvi.hip,
  * csrc/npvi.hpp, docs/kernels_npvi.md) -----------------------------------------------------------------------------------------

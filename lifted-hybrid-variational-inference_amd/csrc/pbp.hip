@@ -22,6 +22,7 @@
 #include "potential.hpp"
 #include "fastmath.hpp"
 #include "cq.hpp"
+#include "gk21.hpp"
 
 namespace lhvi {
 
@@ -2227,59 +2228,7 @@ __global__ void __launch_bounds__(BLOCK) pbp_map_brent_kernel(lhvi_graph_t g, lh
 // 3 the integrand overflowed (e ** belief_rv = inf: the reference raises OverflowError there).
 constexpr int QUAD_LIMIT = 50;
 
-struct Gk21 { double result, abserr, resabs, resasc; bool overflow; };
-
-template <typename F>
-__device__ Gk21 gk21(F&& f, double a, double b) {
-    const double xgk[11] = {0.995657163025808080735527280689003, 0.973906528517171720077964012084452,
-                            0.930157491355708226001207180059508, 0.865063366688984510732096688423493,
-                            0.780817726586416897063717578345042, 0.679409568299024406234327365114874,
-                            0.562757134668604683339000099272694, 0.433395394129247190799265943165784,
-                            0.294392862701460198131126603103866, 0.148874338981631210884826001129720, 0.0};
-    const double wgk[11] = {0.011694638867371874278064396062192, 0.032558162307964727478818972459390,
-                            0.054755896574351996031381300244580, 0.075039674810919952767043140916190,
-                            0.093125454583697605535065465083366, 0.109387158802297641899210590325805,
-                            0.123491976262065851077958109585166, 0.134709217311473325928054001771707,
-                            0.142775938577060080797094273138717, 0.147739104901338491374841515972068,
-                            0.149445554002916905664936468389821};
-    const double wg[5] = {0.066671344308688137593568809893332, 0.149451349150580593145776339657697,
-                          0.219086362515982043995534934228163, 0.269266719309996355091226921569469,
-                          0.295524224714752870173815619188769};
-    const double epmach = 2.220446049250313e-16, uflow = 2.2250738585072014e-308;
-    const double centr = 0.5 * (a + b), hlgth = 0.5 * (b - a), dhlgth = fabs(hlgth);
-    double fv1[10], fv2[10];
-    const double fc = f(centr);
-    double resg = 0.0, resk = wgk[10] * fc, resabs = fabs(resk);
-    for (int j = 0; j < 5; ++j) {
-        const int jtw = 2 * j + 1;
-        const double absc = hlgth * xgk[jtw];
-        const double f1 = f(centr - absc), f2 = f(centr + absc);
-        fv1[jtw] = f1; fv2[jtw] = f2;
-        resg += wg[j] * (f1 + f2);
-        resk += wgk[jtw] * (f1 + f2);
-        resabs += wgk[jtw] * (fabs(f1) + fabs(f2));
-    }
-    for (int j = 0; j < 5; ++j) {
-        const int jtwm1 = 2 * j;
-        const double absc = hlgth * xgk[jtwm1];
-        const double f1 = f(centr - absc), f2 = f(centr + absc);
-        fv1[jtwm1] = f1; fv2[jtwm1] = f2;
-        resk += wgk[jtwm1] * (f1 + f2);
-        resabs += wgk[jtwm1] * (fabs(f1) + fabs(f2));
-    }
-    const double reskh = resk * 0.5;
-    double resasc = wgk[10] * fabs(fc - reskh);
-    for (int j = 0; j < 10; ++j) resasc += wgk[j] * (fabs(fv1[j] - reskh) + fabs(fv2[j] - reskh));
-    Gk21 r;
-    r.result = resk * hlgth;
-    r.resabs = resabs * dhlgth;
-    r.resasc = resasc * dhlgth;
-    r.abserr = fabs((resk - resg) * hlgth);
-    if (r.resasc != 0.0 && r.abserr != 0.0) r.abserr = r.resasc * fmin(1.0, pow(200.0 * r.abserr / r.resasc, 1.5));
-    if (r.resabs > uflow / (50.0 * epmach)) r.abserr = fmax((epmach * 50.0) * r.resabs, r.abserr);
-    r.overflow = !(fabs(resk) < __builtin_huge_val());
-    return r;
-}
+// Gk21, gk21: csrc/gk21.hpp (shared with the mixture KL, csrc/gmkl.hpp)
 
 __global__ void __launch_bounds__(BLOCK) pbp_quad_kernel(lhvi_graph_t g, lhvi_pots_t pots, lhvi_pbp_t s,
                                                         const double* __restrict__ v2f, int64_t nq, QueryRows rows,

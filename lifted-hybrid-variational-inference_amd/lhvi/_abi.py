@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 23            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 24            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -142,6 +142,7 @@ GAUSS_CHAIN_MAX_BLOCK = 128 # LHVI_GAUSS_CHAIN_MAX_BLOCK
 MIX_MAX_K, MIX_TILE, MIX_ROWS = 128, 64, 4     # LHVI_MIX_MAX_K / LHVI_MIX_TILE / LHVI_MIX_ROWS
 MIX_GAUSSIAN, MIX_VI = 0, 1                     # normaliser of lhvi_mix_prepare
 GMFIT_MAX_K = 16            # LHVI_GMFIT_MAX_K
+GMKL_MAX_PANELS = 1024      # LHVI_GMKL_MAX_PANELS
 VI_GAUSSIAN_PDF = 2         # LHVI_VI_GAUSSIAN_PDF (lhvi_vi_t.quirks)
 NPVI_MAX_K, NPVI_MAX_SLOTS = 16, 24             # LHVI_NPVI_MAX_K / LHVI_NPVI_MAX_SLOTS
 
@@ -268,6 +269,9 @@ SIGNATURES = {
     'lhvi_gibbs_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit_host': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gm_kl_ws_doubles': (_sz, [_i32]),
+    'lhvi_gm_kl': (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gm_kl_host': (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
     'lhvi_npvi_workspace_bytes': (_sz, [_G, _VI]),
     'lhvi_npvi_grad': (C.c_int, [_G, _P, _VI, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'lhvi_npvi_run': (C.c_int, [_G, _P, _VI, _NO, _i32, _i32, _vp, _vp, _sz, _vp]),

@@ -522,6 +522,16 @@ class ExactHybridGaussian:
         lb = float(r.mixture(pts)[self.Vc_idx[rv], 0, 0].item())
         return lb if log_belief else float(np.exp(lb))
 
+    def marginals(self):
+        """the exact marginals of the continuous hidden variables ``self.Vc`` as ``ScalarMixtures`` [Nc, M] on the device: one
+        component per discrete configuration, weights the configuration table (shared by the rows), means and variances the
+        transposes of the run's arrays -- views, nothing is copied or downloaded.  Evidence has no row, as in ``belief_all``
+        (an observed variable is a point mass there); ``marginals().kl(other)`` is the reference's ``kl_err`` per variable."""
+        r = self._need_run()
+        from .gmfit import ScalarMixtures
+        Nc, M = len(self.Vc), self.model.M
+        return ScalarMixtures(r.table[None, :].expand(Nc, M), r.means.t(), r.vars.t())
+
     def belief_all(self, x):
         """exact marginals of every variable of ``self.rvs``: x (V, m).  Continuous hidden rows: the mixture density at x[v, :];
         discrete hidden rows: the marginal of the states in columns [0, #states) (x ignored, 0 beyond); observed rows: 1 where

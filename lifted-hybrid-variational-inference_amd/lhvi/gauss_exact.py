@@ -345,6 +345,13 @@ class ExactGaussian:
         self._need_run()
         return self._mean, self._var
 
+    def marginals(self):
+        """the marginals of the hidden variables (``self.hidden``, in index order) as K = 1 ``ScalarMixtures``:
+        ``ScalarMixtures.from_normals`` of their ``mu_var``.  Evidence has no row (its variance is 0)."""
+        from .gmfit import ScalarMixtures
+        mean, var = self.mu_var
+        return ScalarMixtures.from_normals(mean[self.hidden], var[self.hidden])
+
     def get_belief_params(self, rv):
         self._need_run()
         i = self._index(rv)

@@ -5,7 +5,7 @@ docs/kernels_gmfit.md).
 ``GaussianMixture(n_components=K, covariance_type='diag')`` on one column): the same E- and M-step, ``reg_covar``, ``tol``
 and ``max_iter``, on centred samples and from a deterministic start (quantile centres, Lloyd iterations) instead of a
 randomly seeded k-means.  ``ScalarMixtures`` holds the fits and answers densities and modes through the mixture kernels
-(``csrc/mixture.hip``).
+(``csrc/mixture.hip``) and the KL divergence to other mixtures through ``lhvi.gmkl``.
 
 ``host=True`` runs the host twin (``lhvi_gm_fit_host``: the device's code with one "lane") on NumPy arrays and needs no GPU;
 it is what the CPU tests use.  Nothing switches to it by itself: without a GPU the default raises ``LhviError``."""
@@ -43,6 +43,26 @@ class ScalarMixtures:
         self.R, self.K = int(w.shape[0]), int(w.shape[1])
         self._np = None
         self._modes = {}
+
+    @classmethod
+    def from_normals(cls, mu, var, host=False):
+        """one normal per row as K = 1 mixtures: ``mu``, ``var`` [R] (arrays or device tensors), weight 1"""
+        if _is_tensor(mu):
+            mu, var = mu.reshape(-1, 1), var.reshape(-1, 1)
+            w = mu.new_ones(mu.shape)
+        else:
+            mu, var = np.asarray(mu, dtype=np.float64).reshape(-1, 1), np.asarray(var, dtype=np.float64).reshape(-1, 1)
+            w = np.ones(mu.shape)
+        if tuple(mu.shape) != tuple(var.shape):
+            raise ValueError('mu and var must have the same length')
+        return cls(w, mu, var, host=host)
+
+    def kl(self, other, a=-np.inf, b=np.inf, **kw):
+        """``KL(self[r] || other[r])`` over ``[a, b]`` for every row (``lhvi.gmkl.kl_scalar_mixtures``; ``other``: a
+        ``ScalarMixtures`` or a ``(w, mu, var)`` tuple).  ``host`` defaults to this object's."""
+        from .gmkl import kl_scalar_mixtures
+        kw.setdefault('host', self.host)
+        return kl_scalar_mixtures(self, other, a, b, **kw)
 
     def _params(self):
         if self._np is None:

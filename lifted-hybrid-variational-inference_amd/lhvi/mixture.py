@@ -128,6 +128,7 @@ class MixtureBelief:
             raise ValueError("normaliser must be 'gaussian' or 'vi', not %r" % (normaliser,))
         self.K, self.Dmax, self.normaliser = int(K), int(Dmax), normaliser
         self._src = {True: host_src, False: dev_src}
+        self._from_arrays = host_src is not None
         self._sides = {}
         self.values = {}            # row -> the state values of a discrete row (from_solver): answers are values, not indices
         self.row_value = None       # [V] the value of a row without parameters (evidence of the solver), NaN elsewhere
@@ -192,6 +193,33 @@ class MixtureBelief:
     @property
     def V(self):
         return int(self.nstates.shape[0])
+
+    def scalar_mixtures(self, rows=None, host=False):
+        """The marginals of the continuous rows ``rows`` (default: every continuous row, in row order) as ``ScalarMixtures``
+        [R, K]: the shared weights ``w`` for every row, the row's means and variances.  A belief read from a solver gives
+        device tensors (nothing is downloaded), one built from arrays gives arrays; ``host``: whether the result's queries
+        (``kl``, ``log_pdf``, ``modes``) run the host twins.  ``ValueError`` unless the normaliser is 'gaussian' (only then is
+        a component the normal density) and for a row that is not continuous."""
+        from .gmfit import ScalarMixtures
+        if self.normaliser != 'gaussian':
+            raise ValueError("scalar_mixtures needs the normaliser 'gaussian', not %r: the components of this belief are not "
+                             'normal densities' % (self.normaliser,))
+        nstates = self.nstates
+        rows = np.flatnonzero(nstates == 0) if rows is None else self._rows(rows, 'rows')
+        if rows.size and (nstates[rows] != 0).any():
+            raise ValueError('rows names a row that is not continuous')
+        src = self._src[self._from_arrays]             # the side the belief was built on (the other one is a lazy copy)
+        w, eta_c = src['w'], src['eta_c']
+        if eta_c is None:
+            raise ValueError('the belief has no continuous rows')
+        if self._from_arrays:
+            mu, var = np.ascontiguousarray(eta_c[rows, :, 0]), np.ascontiguousarray(eta_c[rows, :, 1])
+            return ScalarMixtures(np.broadcast_to(w, mu.shape), mu, var, host=host)
+        if host:
+            raise ValueError('host=True needs a belief built from arrays')
+        idx = _abi.to_dev(rows.astype(np.int64), eta_c.device)
+        mu, var = eta_c[idx, :, 0].contiguous(), eta_c[idx, :, 1].contiguous()
+        return ScalarMixtures(w.reshape(1, -1).expand(mu.shape), mu, var)
 
     def row(self, rv):
         """the row of a variable of the solver's graph (``from_solver``): a lifted solver answers through ``rv.cluster``"""
