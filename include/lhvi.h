@@ -1041,7 +1041,8 @@ int lhvi_oneshot_run_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const 
  * One half-round each; colours are dense int32 ids (the rank of the item's 64-bit signature fingerprint among the distinct
  * fingerprints).  ws: lhvi_color_workspace_bytes(g) bytes.
  * result: device int32[4] = {number of colours, fingerprint collision (two items agree on the first 64-bit fingerprint and
- * differ on the second: retry), table overflow (method 0 only: repeat the call with method 1), 0}.
+ * differ on the second: the Python callers raise LhviError -- the seed is a constant, nothing is retried), table overflow
+ * (method 0 only: repeat the call with method 1), 0}.
  * method 0: the signature kernel finds-or-inserts each fingerprint in a 1 M-slot hash table and only the distinct keys are
  *           sorted (the answer has few of them: ~30 k on a 10 M-edge relational graph);
  * method 1: radix sort of all items' fingerprints.  Both give the same colours. */

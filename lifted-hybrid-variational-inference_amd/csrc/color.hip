@@ -9,7 +9,7 @@
 //
 // Exactness: signatures are reduced to two independent 64-bit fingerprints (h1, h2).  Items are ranked by
 // h1 (radix sort); if two adjacent items agree on h1 but not on h2 a collision flag is raised and the
-// host retries with another seed, so a wrong merge needs a simultaneous 128-bit collision.  The rv
+// host gives up with an error (the seed is the constant 0), so a wrong merge needs a simultaneous 128-bit collision.  The rv
 // fingerprint is a *sum* of per-neighbour mixes: integer addition commutes, so the multiset needs no
 // sorting and the atomics below are deterministic.
 //
@@ -333,7 +333,7 @@ __global__ void __launch_bounds__(BLOCK) assign_kernel(int n, Table t, const uin
         s = (s + 1) & (TABLE_SLOTS - 1);
     }
     color_out[i] = t.rank[s];
-    if (t.h2[s] != h2[i]) result[1] = 1;               // equal h1, different h2: the host retries with another seed
+    if (t.h2[s] != h2[i]) result[1] = 1;               // equal h1, different h2: the host raises an error
 }
 
 __global__ void __launch_bounds__(BLOCK) flag_kernel(int n, const uint64_t* __restrict__ key_sorted,
@@ -345,7 +345,7 @@ __global__ void __launch_bounds__(BLOCK) flag_kernel(int n, const uint64_t* __re
     int fl = 1;
     if (i > 0 && key_sorted[i] == key_sorted[i - 1]) {
         fl = 0;
-        if (h2[idx_sorted[i]] != h2[idx_sorted[i - 1]]) result[1] = 1;   // h1 collision: host retries
+        if (h2[idx_sorted[i]] != h2[idx_sorted[i - 1]]) result[1] = 1;   // h1 collision: the host raises an error
     }
     flag[i] = fl;
 }
@@ -522,7 +522,7 @@ size_t lhvi_color_workspace_bytes(const lhvi_graph_t* g) {
     return carve(&w, nullptr, n < 1 ? 1 : n);
 }
 
-// result: device int32[4] = {number of colours, collision flag (retry with another seed if 1), table overflow (repeat the
+// result: device int32[4] = {number of colours, collision flag (the host raises an error if 1), table overflow (repeat the
 // half round with method 1), 0}
 int lhvi_color_refine_factors(const lhvi_graph_t* g, const uint8_t* symmetric, const int32_t* rv_color,
                               const int32_t* f_color, int32_t* f_color_out, int32_t* n_colors_out,

@@ -263,6 +263,8 @@ def build_flat(fac_ptr, edge_var, fac_pot, pot_specs, var_value, var_dom, domain
     edge_var = np.asarray(edge_var, dtype=np.int32)
     F, E, V = fac_ptr.size - 1, edge_var.size, int(np.asarray(var_value).size)
     arity = np.diff(fac_ptr)
+    if F and arity.max() > MAX_ARITY:                # (the kernels read a scope's first MAX_ARITY entries only)
+        raise NotImplementedError('factor arity %d exceeds LHVI_MAX_ARITY=%d' % (arity.max(), MAX_ARITY))
     edge_fac = np.repeat(np.arange(F, dtype=np.int32), arity)
     edge_pos = (np.arange(E, dtype=np.int64) - fac_ptr[:-1][edge_fac]).astype(np.int32)
     order = np.argsort(edge_var, kind='stable').astype(np.int32)
