@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 24  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 25  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -47,7 +47,8 @@ extern "C" {
                               * 21: lhvi_oneshot_*;
                               * 22: lhvi_pbp_var_fused64;
                               * 23: lhvi_gauss_chain_*, LHVI_GAUSS_CHAIN_MAX_BLOCK;
-                              * 24: lhvi_gm_kl, lhvi_gm_kl_ws_doubles, lhvi_gm_kl_host, LHVI_GMKL_MAX_PANELS */
+                              * 24: lhvi_gm_kl, lhvi_gm_kl_ws_doubles, lhvi_gm_kl_host, LHVI_GMKL_MAX_PANELS;
+                              * 25: lhvi_hg_energy, lhvi_hg_energy_host, lhvi_argmax_first, lhvi_argmax_first_ws_bytes, lhvi_argmax_first_host */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -954,6 +955,28 @@ int lhvi_gm_kl(int32_t R, int32_t Kp, const double* wp, const double* mup, const
 int lhvi_gm_kl_host(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp, int32_t Kq, const double* wq,
                     const double* muq, const double* varq, const double* a, const double* b, double epsabs, double epsrel,
                     double* kl, double* abserr, int32_t* status, int32_t* neval);
+
+/* ---- Joint log potentials of assignments of a hybrid Gaussian MRF and the first-index arg-max (the joint MAP of the exact and
+ * Gibbs baselines, osi/hybrid_mln_experiment.py:267-279 with osi/utils.py::eval_joint_assignment_energy; csrc/hg_energy.hip,
+ * csrc/hg_energy.hpp, docs/kernels_hg_energy.md) ----------------------------------------------------------------------------
+ * Row s of S is one joint assignment of the flat model m.  Its discrete state: with x_d == NULL the digits of configuration
+ * cfg_begin + s (from dstride / dstates, as lhvi_exact_configs numbers them), else x_d [S][Nd] and cfg_begin is ignored (m->M and
+ * m->dstride are then not read).  Its continuous point: x_c [S][Nc] (may be NULL when Nc == 0).
+ * out [s] = the sum of the quadratic descriptors, in descriptor order, each (sum_a sum_j P[a][j] x_a x_j, row-major, one term
+ * after the other) + (sum_a b_a x_a) + c at the local discrete state, then the table descriptors in descriptor order: the same
+ * order on the device and on the host.  One lane per row; a row's bits depend neither on S nor on its position.
+ * S == 0: LHVI_OK without a launch.  LHVI_E_UNSUPPORTED: Nc > LHVI_EXACT_MAX_NC.  LHVI_E_ARG: a NULL required pointer, S < 0,
+ * cfg_begin < 0 without x_d.  Nd is not limited.  A digit outside its variable's range is the caller's error. */
+int lhvi_hg_energy(const lhvi_exact_t* m, int64_t S, int64_t cfg_begin, const int32_t* x_d, const double* x_c, double* out,
+                   void* stream);
+/* the same on the HOST through the device's code (csrc/hg_energy.hpp); every pointer is host memory */
+int lhvi_hg_energy_host(const lhvi_exact_t* m, int64_t S, int64_t cfg_begin, const int32_t* x_d, const double* x_c, double* out);
+/* index [0] = the smallest index that attains the maximum over the non-NaN entries of v [n], value [0] = that entry; n == 0 or
+ * all NaN: index -1, value NaN.  -inf wins when nothing is larger; +0 and -0 tie.  Two stages, 64-bit indices; a comparison
+ * reduction, so the result is the definition's for every n.  ws: lhvi_argmax_first_ws_bytes(n) bytes of device memory. */
+size_t lhvi_argmax_first_ws_bytes(int64_t n);
+int lhvi_argmax_first(int64_t n, const double* v, int64_t* index, double* value, void* ws, void* stream);
+int lhvi_argmax_first_host(int64_t n, const double* v, int64_t* index, double* value);
 
 /* ---- Nonparametric variational inference (osi/NPVI.py: Gershman-style NPVI on a K-component product mixture; csrc/npvi.hip,
  * csrc/npvi.hpp, docs/kernels_npvi.md) -----------------------------------------------------------------------------------------

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 24            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 25            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -272,6 +272,11 @@ SIGNATURES = {
     'lhvi_gm_kl_ws_doubles': (_sz, [_i32]),
     'lhvi_gm_kl': (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_kl_host': (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
+    'lhvi_hg_energy': (C.c_int, [C.POINTER(ExactStruct), _i64, _i64, _vp, _vp, _vp, _vp]),
+    'lhvi_hg_energy_host': (C.c_int, [C.POINTER(ExactStruct), _i64, _i64, _vp, _vp, _vp]),
+    'lhvi_argmax_first_ws_bytes': (_sz, [_i64]),
+    'lhvi_argmax_first': (C.c_int, [_i64, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_argmax_first_host': (C.c_int, [_i64, _vp, _vp, _vp]),
     'lhvi_npvi_workspace_bytes': (_sz, [_G, _VI]),
     'lhvi_npvi_grad': (C.c_int, [_G, _P, _VI, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'lhvi_npvi_run': (C.c_int, [_G, _P, _VI, _NO, _i32, _i32, _vp, _vp, _sz, _vp]),

@@ -19,7 +19,7 @@ import itertools
 
 import numpy as np
 
-from . import _abi, expr
+from . import _abi, expr, hg_energy
 from .potentials import LogHybridQuadratic, LogQuadratic, LogTable
 from .utils import get_conditional_quadratic
 
@@ -315,6 +315,29 @@ class _DeviceRun:
         self.marg = torch.empty(max(n_states, 1), dtype=f64, device=dev)[:n_states]
         _abi.check(l.lhvi_exact_marginals(s, n_states, _abi.ptr(self.table), _abi.ptr(self.marg), st))
         self._mix = None
+        self._energies = None
+
+    def config_energies(self):
+        """[M] device tensor: the joint log potential of every configuration at its conditional mean (``lhvi_hg_energy`` on the
+        run's means, a launch per chunk of the enumeration; computed once)"""
+        if self._energies is None:
+            torch = _abi._torch()
+            M, Nc = self.model.M, self.model.Nc
+            out = torch.empty(M, dtype=torch.float64, device=self.logp.device)
+            for b in range(0, M, CHUNK):
+                n = min(CHUNK, M - b)
+                hg_energy.energies(self.s, cfg_range=(b, n), x_c=self.means[b:b + n] if Nc else None, out=out[b:b + n])
+            self._energies = out
+        return self._energies
+
+    def joint_map(self):
+        """(flat configuration index, its energy, its conditional mean [Nc] as an ndarray): the first arg-max of
+        ``config_energies()``; only the winner's mean is downloaded"""
+        index, value = hg_energy.argmax_first(self.config_energies())
+        index = int(index.item())
+        if index < 0:
+            raise ValueError('every configuration\'s energy is NaN')
+        return index, float(value.item()), self.means[index].cpu().numpy()
 
     def mix(self):
         if self._mix is None:
@@ -420,12 +443,67 @@ def get_scalar_gm_log_prob(x, w, mu, var):
     return out.cpu().numpy().reshape(x.shape)
 
 
+def joint_map_from_bn(factors, Vd, Vc):
+    """the exact joint MAP as the experiment drivers find it (``osi/hybrid_mln_experiment.py:267-279``): the largest
+    ``eval_joint_assignment_energy`` over the discrete configurations at their conditional means ``bn[1][disc_config]``, all on
+    the device.  Returns (map_energy, config: tuple of state indices over Vd, xc: ndarray [Nc]); on ties the first
+    configuration in C order wins.  The continuous part is not clipped to its domain, as the reference's is not."""
+    dstates = [rv.dstates for rv in Vd]
+    run = _DeviceRun(flatten_factors(factors, dstates, len(Vc)), keep_cov=False)
+    index, energy, xc = run.joint_map()
+    return energy, tuple(int(k) for k in np.unravel_index(index, dstates)) if dstates else (), xc
+
+
+def joint_map_dict(solver, config, index, xc, energy, **extra):
+    """the result of ``joint_map()`` of the exact and Gibbs solvers: config (state indices over ``solver.Vd``), index (the flat
+    configuration index, None when the configurations cannot be numbered), xd (domain values), xc [Nc], inside (xc within every
+    ``rv.values``), energy, assignment ({rv: value} over ``solver.rvs``, evidence included), and what the caller adds"""
+    config = tuple(int(k) for k in config)
+    xc = np.asarray(xc, dtype=np.float64).reshape(len(solver.Vc))
+    xd = tuple(rv.domain.values[k] for rv, k in zip(solver.Vd, config))
+    inside = all(rv.domain.values[0] <= x <= rv.domain.values[1] for rv, x in zip(solver.Vc, xc))
+    assignment = {}
+    for rv in solver.rvs:
+        if rv.value is not None:
+            assignment[rv] = rv.value
+        elif rv in solver.Vd_idx:
+            assignment[rv] = xd[solver.Vd_idx[rv]]
+        else:
+            assignment[rv] = float(xc[solver.Vc_idx[rv]])
+    out = dict(config=config, index=index, xd=xd, xc=xc, inside=bool(inside), energy=float(energy), assignment=assignment)
+    out.update(extra)
+    return out
+
+
+def states_of(solver, X):
+    """(x_d [S, Nd] int32 state indices, x_c [S, Nc]) of the assignments X [S, V] over ``solver.rvs``: discrete columns hold domain
+    values, observed columns are ignored; a discrete value that is no state raises ``ValueError``"""
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim != 2 or X.shape[1] != len(solver.rvs):
+        raise ValueError('X must be [S, %d] over the solver\'s rvs' % len(solver.rvs))
+    x_d = np.zeros((X.shape[0], len(solver.Vd)), dtype=np.int32)
+    x_c = np.zeros((X.shape[0], len(solver.Vc)))
+    for v, rv in enumerate(solver.rvs):
+        if rv.value is not None:
+            continue
+        if rv in solver.Vc_idx:
+            x_c[:, solver.Vc_idx[rv]] = X[:, v]
+            continue
+        hit = X[:, v][:, None] == np.asarray(rv.domain.values, dtype=np.float64)[None, :]
+        if not hit.any(axis=1).all():
+            row = int(np.flatnonzero(~hit.any(axis=1))[0])
+            raise ValueError('%s: %r in row %d is none of its states' % (rv, X[row, v], row))
+        x_d[:, solver.Vd_idx[rv]] = hit.argmax(axis=1)
+    return x_d, x_c
+
+
 # ---- the solver-shaped class ---------------------------------------------------------------------------------------------------
 class ExactHybridGaussian:
     """Exact marginals of a hybrid Gaussian MRF.  ``ExactHybridGaussian(g)`` or ``ExactHybridGaussian(factors=, Vd=, Vc=)``;
     variables with ``rv.value`` set are evidence.  After ``run()``: ``logZ`` (of the conditioned model, constants of fully
     observed factors included), ``disc_table``, ``means``, ``variances`` (NumPy, shaped [v1..vNd(, Nc)]), ``covs`` with
-    ``keep_cov``; ``map`` / ``belief`` / ``map_all`` / ``belief_all``."""
+    ``keep_cov``; ``map`` / ``belief`` / ``map_all`` / ``belief_all``; ``config_energies`` / ``joint_map`` (the exact joint MAP, which is
+    not ``argmax(disc_table)``: the table carries the mass term -1/2 log det J) and ``energy`` (docs/kernels_hg_energy.md)."""
 
     def __init__(self, g=None, factors=None, Vd=None, Vc=None):
         if g is not None:
@@ -453,6 +531,7 @@ class ExactHybridGaussian:
                                         tuple(self.Vc_idx[rv] for rv in hidden if rv.domain.continuous)))
         self.model = flatten_factors(self.factors, self.dstates, len(self.Vc))
         self._run = None
+        self._dev_model = None
 
     def run(self, keep_cov=False, lanes=None):
         self._run = r = _DeviceRun(self.model, keep_cov=keep_cov, lanes=lanes)
@@ -466,7 +545,39 @@ class ExactHybridGaussian:
         off = np.concatenate([[0], np.cumsum(self.dstates)]).astype(int)
         self.disc_marginals = [marg[off[i]:off[i + 1]] for i in range(len(self.Vd))]
         self._maps = None
+        self._config_energies = None
         return self
+
+    def config_energies(self):
+        """the joint log potential of every configuration at its conditional mean, ``(x_d, mu(x_d))`` with the evidence in place
+        (``log_const`` included, like ``logZ``): an ndarray shaped like ``disc_table``, computed on the device from the run's
+        means once per ``run()``"""
+        r = self._need_run()
+        if self._config_energies is None:
+            self._config_energies = (r.config_energies().cpu().numpy() + self.log_const).reshape(self.dstates)
+        return self._config_energies
+
+    def joint_map(self):
+        """the exact joint MAP: the configuration of largest ``config_energies()`` (the first in C order on ties) with its
+        conditional mean, which is not clipped to the domain (``inside`` tells).  A dict: config, index, xd, xc, inside,
+        energy, assignment (``joint_map_dict``)."""
+        index, energy, xc = self._need_run().joint_map()
+        config = np.unravel_index(index, self.dstates) if self.dstates else ()
+        return joint_map_dict(self, config, index, xc, energy + self.log_const)
+
+    def energy(self, X, host=False):
+        """the joint log potential (``log_const`` included) of the assignments X [S, V] over ``self.rvs`` as an ndarray [S]:
+        the driver's ``map_energy`` of any solver's joint MAP on this model.  Discrete columns hold domain values, observed
+        columns are ignored.  ``host=True`` runs the kernel's host twin."""
+        x_d, x_c = states_of(self, X)
+        if host:
+            return hg_energy.energies(self.model.host_struct(), x_d=x_d, x_c=x_c, host=True) + self.log_const
+        if self._dev_model is None:
+            t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype))
+                             for n, a in ((n, getattr(self.model, n)) for n in ExactModel.FIELDS)})
+            self._dev_model = (t, self.model.struct(lambda n: _abi.ptr(t[n])))
+        out = hg_energy.energies(self._dev_model[1], x_d=_abi.to_dev(x_d), x_c=_abi.to_dev(x_c))
+        return out.cpu().numpy() + self.log_const
 
     def _need_run(self):
         if self._run is None:

@@ -22,8 +22,8 @@ import types
 
 import numpy as np
 
-from . import _abi
-from .exact import MAX_NC, ExactHybridGaussian, ExactModel, _Factor, flatten_factors
+from . import _abi, hg_energy
+from .exact import MAX_NC, ExactHybridGaussian, ExactModel, _Factor, flatten_factors, joint_map_dict
 from .potentials import LogTable
 
 LDS_LIMIT = 64 * 1024
@@ -317,6 +317,26 @@ class HybridGaussianSampler:
         return get_rv_marg_map_from_bn_params(w, mu[:, None], var[:, None, None], {}, {rv: 0}, rv)
 
 
+    def joint_map(self):
+        """the sample of largest joint log potential among ``disc_samples`` / ``cont_samples`` (the reference leaves this as a
+        TODO, ``osi/hybrid_mln_experiment.py:306``): the host arrays go to the device, one launch evaluates every sample, the
+        first one wins on ties.  A dict: config (state indices), xd (domain values), xc, energy, sample (its row)."""
+        model = flatten_factors(self.factors, self.dstates, len(self.Vc))
+        disc = np.asarray(self.disc_samples)
+        if disc.size and (disc.min() < 0 or (disc >= np.asarray(self.dstates)[None, :]).any()):
+            raise ValueError('disc_samples holds a state outside its variable\'s range')
+        t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype)) for n, a in ((n, getattr(model, n)) for n in ExactModel.FIELDS)})
+        e = hg_energy.energies(model.struct(lambda n: _abi.ptr(t[n])), x_d=_abi.to_dev(disc.astype(np.int32)),
+                               x_c=_abi.to_dev(np.asarray(self.cont_samples, dtype=np.float64)))
+        index, value = hg_energy.argmax_first(e)
+        row = int(index.item())
+        if row < 0:
+            raise ValueError('no sample has a finite energy')
+        config = tuple(int(k) for k in disc[row])
+        return dict(config=config, xd=tuple(rv.domain.values[k] for rv, k in zip(self.Vd, config)),
+                    xc=np.array(self.cont_samples[row], dtype=np.float64), energy=float(value.item()), sample=row)
+
+
 def gibbs_sample(lpot_tables, scopes, nbr_factor_ids, dstates, x, num_burnin, num_samples, seed=None, chains=1):
     """``disc_mrf.gibbs_sample``: samples [num_samples, N] of a discrete MRF of log tables, one sweep per sample, from the
     state x (which ends as the last state when chains = 1, like the reference's).  nbr_factor_ids is checked against the
@@ -340,14 +360,15 @@ class GibbsHybridGaussian:
     ``GibbsHybridGaussian(factors=, Vd=, Vc=)``; variables with ``rv.value`` set are evidence, potentials are converted as in
     ``ExactHybridGaussian``.  After ``run()``: ``disc_marginals()``, ``moments()``, ``rhat()``, ``map`` / ``map_all`` /
     ``belief``, and with ``keep_samples`` ``disc_samples`` [chains, num_samples, Nd] / ``cont_samples`` and
-    ``fit_marginals(K)``: the mixtures of the continuous variables fitted to the kept samples on the device."""
+    ``fit_marginals(K)``: the mixtures of the continuous variables fitted to the kept samples on the device, and
+    ``sample_energies()`` / ``joint_map()``: the joint log potential of every kept sample and the best of them."""
 
     def __init__(self, g=None, factors=None, Vd=None, Vc=None):
         if g is None and (factors is None or Vd is None or Vc is None):
             raise ValueError('GibbsHybridGaussian needs a graph, or factors=, Vd= and Vc=')
         ex = ExactHybridGaussian(g=g, factors=factors, Vd=Vd, Vc=Vc)           # the flattening, evidence included
         self.rvs, self.Vd, self.Vc, self.Vd_idx, self.Vc_idx = ex.rvs, ex.Vd, ex.Vc, ex.Vd_idx, ex.Vc_idx
-        self.dstates, self.factors = ex.dstates, ex.factors
+        self.dstates, self.factors, self.log_const = ex.dstates, ex.factors, ex.log_const
         self.model = GibbsModel(ex.model)
         self._run = None
         self.marginals, self._fits = None, {}
@@ -360,6 +381,7 @@ class GibbsHybridGaussian:
                                 init_x_d=init_x_d).run(its_per_launch)
         self.chains, self.num_samples = r.chains, r.num_samples
         self.marginals, self._fits = None, {}           # fits of an earlier run's samples
+        self._energies = None
         self.counts = r.counts.cpu().numpy()
         self.sum1, self.sum2 = r.sum1.cpu().numpy(), r.sum2.cpu().numpy()
         self.disc_samples = r.disc.cpu().numpy() if keep_samples else None
@@ -441,6 +463,37 @@ class GibbsHybridGaussian:
         if not fit_args:
             self._fits[int(K)] = self.marginals
         return self.marginals
+
+    def sample_energies(self):
+        """[chains, num_samples] device tensor: the joint log potential of every kept sample with the evidence in place
+        (``log_const`` included, like ``ExactHybridGaussian.config_energies``), one launch over all of them.  Needs
+        ``run(keep_samples=True)``."""
+        r = self._need_run()
+        if r.disc is None:
+            raise RuntimeError('sample_energies needs the kept samples: call run(keep_samples=True)')
+        if self._energies is None:
+            S, Nd, Nc = r.chains * r.num_samples, len(self.Vd), len(self.Vc)
+            e = hg_energy.energies(r.s.ex, x_d=r.disc.reshape(S, Nd), x_c=r.cont.reshape(S, Nc))
+            self._energies = (e + self.log_const).reshape(r.chains, r.num_samples)
+        return self._energies
+
+    def joint_map(self):
+        """the kept sample of largest joint log potential, the first in chain-major order on ties: the dict of
+        ``ExactHybridGaussian.joint_map`` (index: the flat configuration index, None when the configurations cannot be
+        numbered) plus chain and sample.  Only the winner's row is downloaded.  Needs ``run(keep_samples=True)``."""
+        r = self._need_run()
+        if r.disc is None:
+            raise RuntimeError('joint_map needs the kept samples: call run(keep_samples=True)')
+        index, value = hg_energy.argmax_first(self.sample_energies().reshape(-1))
+        row = int(index.item())
+        if row < 0:
+            raise ValueError('no sample has a finite energy')
+        chain, sample = divmod(row, r.num_samples)
+        config = tuple(int(k) for k in r.disc[chain, sample].cpu().numpy())
+        ex = self.model.ex
+        flat = int(np.dot(np.asarray(config, dtype=object), ex.dstride.astype(object))) if ex.M else None
+        return joint_map_dict(self, config, flat, r.cont[chain, sample].cpu().numpy(), float(value.item()), chain=chain,
+                              sample=sample)
 
     def _bds(self):
         return np.array([[rv.domain.values[0] for rv in self.Vc], [rv.domain.values[1] for rv in self.Vc]], dtype=np.float64)

@@ -142,6 +142,17 @@ def log_likelihood_flat(dg, x):
     return float(out.item())
 
 
+def eval_joint_assignment_energy(factors, rvs2vals):
+    """``osi/utils.py:164-169``: the sum of ``factor.log_potential_fun`` over the factors at the assignment ``rvs2vals``
+    ({rv: value}; a discrete variable of a LogTable / LogHybridQuadratic by its state index, as the reference passes it).  Pure
+    host code for any ``log_potential_fun``; the batched form on the exact baseline's model is
+    ``ExactHybridGaussian.energy`` (``lhvi/hg_energy.py``)."""
+    energy = 0
+    for f in factors:           # in factor order, like the reference's loop
+        energy = energy + f.log_potential_fun([rvs2vals[rv] for rv in f.nb])
+    return energy
+
+
 def set_log_potential_funs(factors, skip_existing=True):
     """``osi/utils.py:188-205``: set ``factor.log_potential_fun`` from ``factor.potential.to_log_potential()``, one object per
     distinct potential (the potentials' own hash / eq), skipping a group whose factors all have one unless told otherwise"""
