@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 25  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 26  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -48,7 +48,8 @@ extern "C" {
                               * 22: lhvi_pbp_var_fused64;
                               * 23: lhvi_gauss_chain_*, LHVI_GAUSS_CHAIN_MAX_BLOCK;
                               * 24: lhvi_gm_kl, lhvi_gm_kl_ws_doubles, lhvi_gm_kl_host, LHVI_GMKL_MAX_PANELS;
-                              * 25: lhvi_hg_energy, lhvi_hg_energy_host, lhvi_argmax_first, lhvi_argmax_first_ws_bytes, lhvi_argmax_first_host */
+                              * 25: lhvi_hg_energy, lhvi_hg_energy_host, lhvi_argmax_first, lhvi_argmax_first_ws_bytes, lhvi_argmax_first_host;
+                              * 26: lhvi_pbp_kl, lhvi_gm_kl_fn_host */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -506,6 +507,20 @@ int lhvi_pbp_quad(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp
 int lhvi_pbp_map_brent(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_t* s, const double* v2f, int64_t nq,
                        const int32_t* row_var, const int64_t* qptr, const int32_t* qedge, const double* qmult, double xtol,
                        int32_t maxfun, double* xout, double* fout, int32_t* nfev, void* stream);
+/* KL(p[r] || belief of query row r) for nq rows in ONE launch: the drivers' kl_err = kl_continuous_logpdf(log_p, log_q) with an EPBP /
+ * HybridLBP belief as log_q (osi/hybrid_mln_experiment.py:326-338, osi/utils.py:724-729) and p a scalar Gaussian mixture
+ * (wp, mup, varp)[r][0 .. Kp).  Rows exactly as for lhvi_pbp_quad (row_var, or the (edge, multiplicity) lists qptr / qedge / qmult).
+ * The method is lhvi_gm_kl's below, unchanged -- the range and the panels from p alone, pass 1, left-to-right depth-first bisection,
+ * the two guards, the status bits, neval -- with log q(x) = belief_rv(x) - logz[r] in the place of the second mixture's log density
+ * (logz: log of the belief's normaliser, e.g. of lhvi_pbp_quad's z).  One wavefront per row, the lanes on the quadrature nodes, the
+ * panel list and the stack in LDS (csrc/gmkl_dev.hpp); no atomics: a row's bits depend neither on nq, nor on its position, nor on the
+ * run.  A row whose logz is not finite, whose variable is observed, discrete or not a variable of g, or whose p is invalid (as for
+ * lhvi_gm_kl) gets kl = abserr = NaN and status bit 2; the other rows are unaffected.  abserr, status and neval may be NULL.
+ * LHVI_E_ARG: nq < 1, Kp < 1, a NULL required pointer, epsabs or epsrel negative or NaN.  docs/kernels_pbkl.md. */
+int lhvi_pbp_kl(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_t* s, const double* v2f, int64_t nq,
+                const int32_t* row_var, const int64_t* qptr, const int32_t* qedge, const double* qmult, const double* logz,
+                int32_t Kp, const double* wp, const double* mup, const double* varp, const double* a, const double* b,
+                double epsabs, double epsrel, double* kl, double* abserr, int32_t* status, int32_t* neval, void* stream);
 
 /* ---- owner-computes exchange of the edge-sharded sweep (lhvi/dist.py::OwnerRunner; csrc/halo.hip) ----------------------------
  * The reference is one process; these two calls move its `message[(rv, f)]` tables (EPBPLogVersion.py:250-258) and proposals
@@ -955,6 +970,12 @@ int lhvi_gm_kl(int32_t R, int32_t Kp, const double* wp, const double* mup, const
 int lhvi_gm_kl_host(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp, int32_t Kq, const double* wq,
                     const double* muq, const double* varq, const double* a, const double* b, double epsabs, double epsrel,
                     double* kl, double* abserr, int32_t* status, int32_t* neval);
+/* the same on the HOST with ANY log density as q: logq(x, r, user) is log q(x) of row r (the reference's kl_continuous_logpdf with
+ * log_p a mixture and log_q any callable).  p, the bounds, the tolerances, the outputs and the invalid rows as above; where logq
+ * returns -inf and p does not vanish the integrand, and with it kl, is +inf (status bit 0).  LHVI_E_ARG also for logq == NULL. */
+int lhvi_gm_kl_fn_host(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp,
+                       double (*logq)(double x, int64_t row, void* user), void* user, const double* a, const double* b,
+                       double epsabs, double epsrel, double* kl, double* abserr, int32_t* status, int32_t* neval);
 
 /* ---- Joint log potentials of assignments of a hybrid Gaussian MRF and the first-index arg-max (the joint MAP of the exact and
  * Gibbs baselines, osi/hybrid_mln_experiment.py:267-279 with osi/utils.py::eval_joint_assignment_energy; csrc/hg_energy.hip,

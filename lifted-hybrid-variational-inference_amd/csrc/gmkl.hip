@@ -3,141 +3,16 @@
 //                  every panel, depth-first bisection against the bound -- is csrc/gmkl.hpp's, shared with the host twin at the
 //                  end of this file; this file supplies the lane mapping.  docs/kernels_gmkl.md.
 //
-// Lanes take the quadrature nodes, 3 x 21 of 64: lane l works on interval l / 21 of the step at node l % 21 (lane 63 repeats
-// lane 42 and is never read).  Pass 1 takes three panels per step, a bisection its two children side by side (the third group
-// repeats the right child).  Every lane runs the components past its own node and keeps the running log-sum-exp; the
-// components are wave-uniform values read from LDS: resident for the whole row when Kp + Kq <= CHUNK, else prepared in chunks
-// of CHUNK (a lane per component: the logarithm and the division) in front of every evaluation.  The 21 values of a group go
-// through LDS and every lane of the group forms the rule's sums itself, in QUADPACK's order (gk21_from_values): no cross-lane
-// arithmetic, so the order of every sum is the host twin's.  The panel list and the stack are in LDS too: 20 024 bytes per
-// wave, 8 waves per CU.  No atomics, no allocation, no private arrays, no scratch (tests/test_gmkl_kernel_resources.py).
-//
-// Control flow is wave-uniform: every decision is taken on values all lanes read from the same LDS words and made a scalar
-// before the branch (uniform()), so the barriers (one wave per workgroup: they order the LDS traffic for the compiler) are
-// reached by all lanes.  The scalar register file is the scarce resource here (the exp / log polynomials and the rule's
-// weights are scalar constants): what lives as long as the kernel -- the row's pointers and bounds, the range, the children
-// of a bisection -- goes through LDS into vector registers instead.
-#include "common.hpp"
-#include "gmkl.hpp"
+// The lane mapping (DevCtx: 3 x 21 nodes on 64 lanes, the component list, the panel list and the stack in LDS, wave-uniform
+// control flow) is csrc/gmkl_dev.hpp, shared with pbp_kl_kernel of csrc/pbp.hip; here its q side is the second mixture
+// (MixtureQ).  20 024 bytes of LDS per wave, 8 waves per CU.  No atomics, no allocation, no private arrays, no scratch
+// (tests/test_gmkl_kernel_resources.py).  The scalar register file is the scarce resource here (the exp / log polynomials and
+// the rule's weights are scalar constants): what lives as long as the kernel -- the row's pointers and bounds, the range, the
+// children of a bisection -- goes through LDS into vector registers instead.
+#include "gmkl_dev.hpp"
 
 namespace lhvi {
 namespace gmkl {
-
-constexpr int CHUNK = 64;
-constexpr int GROUP = 21, GROUPS = 3;
-
-struct Comp { double la, mu, nhiv; };
-struct Shared {
-    double pr[MAX_PANELS], pe[MAX_PANELS];
-    double sa[MAX_DEPTH], sb[MAX_DEPTH], sr[MAX_DEPTH], se[MAX_DEPTH];
-    int sd[MAX_DEPTH];
-    Comp c[CHUNK];
-    double fv[WAVE];
-    double child[2][2];     // (result, estimate) of the two children of a bisection
-    Row in;                 // the row's pointers, bounds and tolerances, and where its outputs go: written by lane 0 and read
-    double *kl, *abserr;    // back by every lane, which keeps them in vector registers (they live as long as the kernel and
-    int32_t *status, *neval;// would crowd the scalar file)
-};
-static_assert(sizeof(Shared) <= 20 * 1024, "8 waves per CU: 160 KiB / 8");
-
-struct DevCtx {
-    Shared& sh;
-    int lane, g, j;         // the lane's interval of the step and its node
-    bool resident;
-
-    __device__ __forceinline__ DevCtx(Shared& s, int l) : sh(s), lane(l), g(l / GROUP < GROUPS ? l / GROUP : GROUPS - 1),
-                                                         j(l < GROUP * GROUPS ? l % GROUP : 0), resident(false) {}
-    __device__ __forceinline__ bool lane0() const { return lane == 0; }
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-    __device__ __forceinline__ static bool uniform(bool c) { return __builtin_amdgcn_readfirstlane((int)c) != 0; }
-    __device__ __forceinline__ static int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
-
-    __device__ __forceinline__ void scan(const Row& in, Scan& sc) const {
-        for (int k = lane; k < in.Kp; k += WAVE) scan_p(sc, in.wp[k], in.mup[k], in.varp[k]);
-        for (int k = lane; k < in.Kq; k += WAVE) scan_q(sc, in.wq[k], in.muq[k], in.varq[k]);
-        sc.lo = -dpp_wave_reduce(-sc.lo, MaxOp());
-        sc.hi = dpp_wave_reduce(sc.hi, MaxOp());
-        sc.sdmin = -dpp_wave_reduce(-sc.sdmin, MaxOp());
-        sc.bad = __any(sc.bad), sc.anyp = __any(sc.anyp), sc.anyq = __any(sc.anyq);
-        // (the reductions leave scalars; the range lives as long as the kernel: through LDS into vector registers, as the row)
-        if (lane == 0) sh.fv[0] = sc.lo, sh.fv[1] = sc.hi, sh.fv[2] = sc.sdmin;
-        sync();
-        sc.lo = sh.fv[0], sc.hi = sh.fv[1], sc.sdmin = sh.fv[2];
-    }
-    __device__ __forceinline__ void load(int slot, const double* w, const double* mu, const double* var, int k) const {
-        Comp c;
-        comp_consts(w[k], var[k], c.la, c.nhiv);
-        c.mu = mu[k];
-        sh.c[slot] = c;
-    }
-    __device__ __forceinline__ void prepare(const Row& in) {
-        resident = in.Kp + in.Kq <= CHUNK;
-        if (resident) {
-            if (lane < in.Kp) load(lane, in.wp, in.mup, in.varp, lane);
-            else if (lane < in.Kp + in.Kq) load(lane, in.wq, in.muq, in.varq, lane - in.Kp);
-            sync();
-        }
-    }
-    __device__ __forceinline__ void run(int first, int n, double x, double& m, double& s) const {
-#pragma unroll 1               // (unrolled, the loop holds more constants in scalar registers than the file has: spills)
-        for (int c = first; c < first + n; ++c) {
-            const Comp k = sh.c[c];             // (weight 0: la = -inf adds exp(-inf) = 0 and leaves the maximum, as skipping does,
-            lse_step(m, s, k.la, k.mu, k.nhiv, x);      //  without a branch per component in this loop)
-        }
-    }
-    __device__ __forceinline__ void side(int K, const double* w, const double* mu, const double* var, int first, double x,
-                                         double& m, double& s) const {
-        m = LSE_START, s = 0.0;
-        for (int k0 = 0; k0 < K; k0 += CHUNK) {             // (resident: K <= CHUNK, one round on what prepare() left)
-            const int n = K - k0 < CHUNK ? K - k0 : CHUNK;
-            if (!resident) {
-                sync();
-                if (lane < n) load(lane, w, mu, var, k0 + lane);
-                sync();
-            }
-            run(resident ? first : 0, n, x, m, s);
-        }
-    }
-    __device__ __forceinline__ double f(const Row& in, double x) const {
-        double mp, sp, mq, sq;
-        side(in.Kp, in.wp, in.mup, in.varp, 0, x, mp, sp);
-        side(in.Kq, in.wq, in.muq, in.varq, in.Kp, x, mq, sq);
-        return integrand(mp, sp, mq, sq);
-    }
-    // the rule on the lane's interval [a, b]: every lane of a group returns the group's result
-    __device__ __forceinline__ Gk21 rule(const Row& in, double a, double b) const {
-        const double centr = 0.5 * (a + b), hlgth = 0.5 * (b - a);
-        const double v = f(in, gk21_node(j, centr, hlgth));
-        sync();
-        sh.fv[lane] = v;
-        sync();
-        const double* fv = sh.fv + g * GROUP;
-        return gk21_from_values([&](int n) { return fv[n]; }, hlgth);
-    }
-    __device__ __forceinline__ void pass1(const Row& in, const Plan& pl) const {
-        for (int i0 = 0; i0 < pl.P; i0 += GROUPS) {
-            const int i = i0 + g, ic = i < pl.P ? i : pl.P - 1;        // a group past the last panel repeats it
-            const Gk21 r = rule(in, panel_edge(pl, ic), panel_edge(pl, ic + 1));
-            if (j == 0 && lane < GROUP * GROUPS && i < pl.P) sh.pr[i] = r.result, sh.pe[i] = r.abserr;
-        }
-        sync();
-    }
-    __device__ __forceinline__ double pres(int i) const { return sh.pr[i]; }
-    __device__ __forceinline__ double perr(int i) const { return sh.pe[i]; }
-    __device__ __forceinline__ void bisect(const Row& in, double a, double mid, double b, Gk21& l, Gk21& r) const {
-        const Gk21 t = rule(in, g == 0 ? a : mid, g == 0 ? mid : b);         // one call: every lane takes part in its barriers
-        if (lane == 0 || lane == GROUP) sh.child[g][0] = t.result, sh.child[g][1] = t.abserr;
-        sync();
-        l.result = sh.child[0][0], l.abserr = sh.child[0][1];
-        r.result = sh.child[1][0], r.abserr = sh.child[1][1];
-    }
-    __device__ __forceinline__ void push(int t, double a, double b, double res, double err, int depth) const {
-        if (lane == 0) sh.sa[t] = a, sh.sb[t] = b, sh.sr[t] = res, sh.se[t] = err, sh.sd[t] = depth;
-    }
-    __device__ __forceinline__ void pop(int t, double& a, double& b, double& res, double& err, int& depth) const {
-        a = sh.sa[t], b = sh.sb[t], res = sh.sr[t], err = sh.se[t], depth = sh.sd[t];
-    }
-};
 
 __global__ void __launch_bounds__(WAVE) gm_kl_kernel(int32_t Kp, const double* __restrict__ wp, const double* __restrict__ mup,
                                                      const double* __restrict__ varp, int32_t Kq, const double* __restrict__ wq,
@@ -155,16 +30,23 @@ __global__ void __launch_bounds__(WAVE) gm_kl_kernel(int32_t Kp, const double* _
     __syncthreads();
     Row in = sh.in;
     in.Kp = Kp, in.Kq = Kq;         // the loop bounds stay scalar
-    DevCtx ctx(sh, (int)threadIdx.x);
+    const MixtureQ q;
+    DevCtx<MixtureQ> ctx(sh, (int)threadIdx.x, q);
     kl_row(in, ctx, sh.kl, sh.abserr, sh.status, sh.neval);
+}
+
+static int kl_check_p(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp, const double* a,
+                      const double* b, double epsabs, double epsrel, const double* kl) {
+    if (R < 1 || Kp < 1 || !(epsabs >= 0.0) || !(epsrel >= 0.0)) return LHVI_E_ARG;
+    if (!wp || !mup || !varp || !a || !b || !kl) return LHVI_E_ARG;
+    return LHVI_OK;
 }
 
 static int kl_check(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp, int32_t Kq, const double* wq,
                     const double* muq, const double* varq, const double* a, const double* b, double epsabs, double epsrel,
                     const double* kl) {
-    if (R < 1 || Kp < 1 || Kq < 1 || !(epsabs >= 0.0) || !(epsrel >= 0.0)) return LHVI_E_ARG;
-    if (!wp || !mup || !varp || !wq || !muq || !varq || !a || !b || !kl) return LHVI_E_ARG;
-    return LHVI_OK;
+    if (Kq < 1 || !wq || !muq || !varq) return LHVI_E_ARG;
+    return kl_check_p(R, Kp, wp, mup, varp, a, b, epsabs, epsrel, kl);
 }
 
 }  // namespace gmkl
@@ -199,6 +81,21 @@ int lhvi_gm_kl_host(int32_t R, int32_t Kp, const double* wp, const double* mup, 
     HostCtx ctx;
     for (int64_t r = 0; r < R; ++r) {
         const Row in{Kp, Kq, wp + r * Kp, mup + r * Kp, varp + r * Kp, wq + r * Kq, muq + r * Kq, varq + r * Kq, a[r], b[r], epsabs, epsrel};
+        kl_row(in, ctx, kl + r, abserr ? abserr + r : nullptr, status ? status + r : nullptr, neval ? neval + r : nullptr);
+    }
+    return LHVI_OK;
+}
+
+int lhvi_gm_kl_fn_host(int32_t R, int32_t Kp, const double* wp, const double* mup, const double* varp,
+                       double (*logq)(double x, int64_t row, void* user), void* user, const double* a, const double* b,
+                       double epsabs, double epsrel, double* kl, double* abserr, int32_t* status, int32_t* neval) {
+    const int rc = kl_check_p(R, Kp, wp, mup, varp, a, b, epsabs, epsrel, kl);
+    if (rc || !logq) return LHVI_E_ARG;
+    HostCtxT<HostFnQ> ctx;
+    ctx.q.logq = logq, ctx.q.user = user;
+    for (int64_t r = 0; r < R; ++r) {
+        const Row in{Kp, 0, wp + r * Kp, mup + r * Kp, varp + r * Kp, nullptr, nullptr, nullptr, a[r], b[r], epsabs, epsrel};
+        ctx.q.row = r;
         kl_row(in, ctx, kl + r, abserr ? abserr + r : nullptr, status ? status + r : nullptr, neval ? neval + r : nullptr);
     }
     return LHVI_OK;

@@ -3,7 +3,9 @@
 // per quadrature node) and the host (lhvi_gm_kl_host: the nodes one after another).  docs/kernels_gmkl.md has the method.
 //
 // Shared here: the component constants, the running log-sum-exp of a node, the integrand, the range and panel plan, the
-// acceptance rule and the refinement loop (pass 2).  A Ctx supplies what depends on where the nodes are evaluated:
+// acceptance rule and the refinement loop (pass 2).  q need not be a mixture: the integrand takes log q(x) as (mq, sq) with
+// log q = mq + log(sq), and a context whose q side is another log density (a caller's function on the host, a particle
+// solver's belief in csrc/pbp.hip) passes (log q(x), 1).  A Ctx supplies what depends on where the nodes are evaluated:
 //   scan(in, sc)                   the validity of the row and the range of p (order-independent: min / max / or)
 //   prepare(in)                    once per row, before the first evaluation
 //   pass1(in, pl)                  the rule on every panel; afterwards pres(i), perr(i) are readable
@@ -111,7 +113,9 @@ LHVI_HD Plan make_plan(double a, double b, const Scan& sc) {
 }
 LHVI_HD double panel_edge(const Plan& pl, int i) { return i >= pl.P ? pl.U : pl.L + (double)i * pl.h; }
 
-LHVI_HD bool meets(double err, double bound, double width, double range) { return err <= bound * (width / range); }
+// (an estimate that is not finite meets nothing, not even an infinite bound: where pass 1 already sees an infinite integrand
+// area0 and the bound are infinite too, and the interval is accepted by the guard with status bit 0, as docs/kernels_gmkl.md says)
+LHVI_HD bool meets(double err, double bound, double width, double range) { return err <= bound * (width / range) && err <= DBL_MAX; }
 
 template <class Ctx>
 LHVI_HD void kl_row(const Row& in, Ctx& ctx, double* kl, double* abserr, int32_t* status, int32_t* neval) {
@@ -169,36 +173,55 @@ LHVI_HD void kl_row(const Row& in, Ctx& ctx, double* kl, double* abserr, int32_t
     write(sum, esum, st, ne);
 }
 
-// ---- the host: one node after another, the components straight from the arrays
-struct HostCtx {
+// ---- the host: one node after another, the components straight from the arrays.  The q side is a policy Q, as on the
+// device (csrc/gmkl_dev.hpp): scan(in, sc) marks the row's q side (anyq, bad), eval(in, x, m, s) leaves log q(x) = m + log(s)
+LHVI_HD void host_side(int K, const double* w, const double* mu, const double* var, double x, double& m, double& s) {
+    m = LSE_START, s = 0.0;
+    for (int k = 0; k < K; ++k) {
+        double la, nhiv;
+        comp_consts(w[k], var[k], la, nhiv);
+        if (la == NEG_INF) continue;
+        lse_step(m, s, la, mu[k], nhiv, x);
+    }
+}
+
+struct HostMixtureQ {           // q is the row's second mixture
+    void scan(const Row& in, Scan& sc) const {
+        for (int k = 0; k < in.Kq; ++k) scan_q(sc, in.wq[k], in.muq[k], in.varq[k]);
+    }
+    void eval(const Row& in, double x, double& m, double& s) const { host_side(in.Kq, in.wq, in.muq, in.varq, x, m, s); }
+};
+
+struct HostFnQ {                // q is any log density: the caller's function of the point and the row (lhvi_gm_kl_fn_host)
+    double (*logq)(double x, int64_t row, void* user);
+    void* user;
+    int64_t row;
+    void scan(const Row&, Scan& sc) const { sc.anyq = true; }
+    void eval(const Row&, double x, double& m, double& s) const { m = logq(x, row, user), s = 1.0; }
+};
+
+template <class Q>
+struct HostCtxT {
     double pr[MAX_PANELS], pe[MAX_PANELS];
     double sa[MAX_DEPTH], sb[MAX_DEPTH], sr[MAX_DEPTH], se[MAX_DEPTH];
     int sd[MAX_DEPTH];
+    Q q;
 
     bool lane0() const { return true; }
     static bool uniform(bool c) { return c; }
     static int uniform(int v) { return v; }
     void scan(const Row& in, Scan& sc) const {
         for (int k = 0; k < in.Kp; ++k) scan_p(sc, in.wp[k], in.mup[k], in.varp[k]);
-        for (int k = 0; k < in.Kq; ++k) scan_q(sc, in.wq[k], in.muq[k], in.varq[k]);
+        q.scan(in, sc);
     }
     void prepare(const Row&) {}
-    static void side(int K, const double* w, const double* mu, const double* var, double x, double& m, double& s) {
-        m = LSE_START, s = 0.0;
-        for (int k = 0; k < K; ++k) {
-            double la, nhiv;
-            comp_consts(w[k], var[k], la, nhiv);
-            if (la == NEG_INF) continue;
-            lse_step(m, s, la, mu[k], nhiv, x);
-        }
-    }
-    static double f(const Row& in, double x) {
+    double f(const Row& in, double x) const {
         double mp, sp, mq, sq;
-        side(in.Kp, in.wp, in.mup, in.varp, x, mp, sp);
-        side(in.Kq, in.wq, in.muq, in.varq, x, mq, sq);
+        host_side(in.Kp, in.wp, in.mup, in.varp, x, mp, sp);
+        q.eval(in, x, mq, sq);
         return integrand(mp, sp, mq, sq);
     }
-    static Gk21 rule(const Row& in, double a, double b) {
+    Gk21 rule(const Row& in, double a, double b) const {
         const double centr = 0.5 * (a + b), hlgth = 0.5 * (b - a);
         double fv[21];
         for (int j = 0; j < 21; ++j) fv[j] = f(in, gk21_node(j, centr, hlgth));
@@ -217,6 +240,7 @@ struct HostCtx {
     void pop(int t, double& a, double& b, double& res, double& err, int& depth) const { a = sa[t], b = sb[t], res = sr[t], err = se[t], depth = sd[t]; }
     void sync() const {}
 };
+using HostCtx = HostCtxT<HostMixtureQ>;
 
 }  // namespace gmkl
 }  // namespace lhvi

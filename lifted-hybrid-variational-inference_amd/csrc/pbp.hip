@@ -3167,6 +3167,62 @@ pbp_var_fused_kernel(lhvi_graph_t g, lhvi_pbp_t s, const double* __restrict__ f2
     if (on && j < n) uniq[(int64_t)v * n + j] = (uint8_t)u;
 }
 
+}  // namespace lhvi
+
+// ---------------------------------------------------------------------------------------------
+// KL(p || belief of a query row) for every row at once, p a scalar Gaussian mixture: the drivers' kl_err with an EPBP / HybridLBP
+// belief as log_q (osi/hybrid_mln_experiment.py:326-338, osi/utils.py:724-729).  The method is csrc/gmkl.hpp::kl_row and the lane
+// mapping csrc/gmkl_dev.hpp's DevCtx, both as for gm_kl_kernel (one wavefront per row, the lanes on the quadrature nodes, the
+// panel list and the stack in LDS); the q side is BeliefQ: every lane walks the row's edges at its own node with
+// query_log_belief -- the edge, partner-particle and message loads are wave-uniform, only x differs -- and log q(x) is that sum
+// less the row's log normaliser.  docs/kernels_pbkl.md.  (Included here, behind every other kernel of this file: gmkl.hpp
+// switches contraction off from its inclusion on.)
+#include "gmkl_dev.hpp"
+
+namespace lhvi {
+
+struct BeliefQ {
+    const lhvi_graph_t& g; const lhvi_pots_t& pots; const lhvi_pbp_t& s; const double* __restrict__ v2f; const QueryRows& rows;
+    int64_t i; int v; double logz; bool valid;
+
+    template <class C> __device__ __forceinline__ void scan(const C&, const gmkl::Row&, gmkl::Scan& sc) const {
+        sc.anyq = true;
+        sc.bad = sc.bad || !valid;
+    }
+    __device__ __forceinline__ static int slots(const gmkl::Row&) { return 0; }
+    template <class C> __device__ __forceinline__ void load_resident(const C&, const gmkl::Row&) const {}
+    template <class C> __device__ __forceinline__ void eval(const C&, const gmkl::Row&, double x, double& m, double& sum) const {
+        m = query_log_belief(g, pots, s, v2f, rows, i, v, x) - logz, sum = 1.0;
+    }
+};
+
+__global__ void __launch_bounds__(WAVE, 2) pbp_kl_kernel(lhvi_graph_t g, lhvi_pots_t pots, lhvi_pbp_t s, const double* __restrict__ v2f,
+                                                      QueryRows rows, const int32_t* __restrict__ row_var,
+                                                      const double* __restrict__ logz, int32_t Kp, const double* __restrict__ wp,
+                                                      const double* __restrict__ mup, const double* __restrict__ varp,
+                                                      const double* __restrict__ a, const double* __restrict__ b, double epsabs,
+                                                      double epsrel, double* __restrict__ kl, double* __restrict__ abserr,
+                                                      int32_t* __restrict__ status, int32_t* __restrict__ neval) {
+    __shared__ gmkl::Shared sh;
+    const int64_t r = blockIdx.x;
+    if (threadIdx.x == 0) {
+        sh.in = gmkl::Row{Kp, 0, wp + r * Kp, mup + r * Kp, varp + r * Kp, nullptr, nullptr, nullptr, a[r], b[r], epsabs, epsrel};
+        sh.kl = kl + r, sh.abserr = abserr ? abserr + r : nullptr;
+        sh.status = status ? status + r : nullptr, sh.neval = neval ? neval + r : nullptr;
+    }
+    __syncthreads();
+    gmkl::Row in = sh.in;
+    in.Kp = Kp, in.Kq = 0;          // the loop bounds stay scalar
+    // the row is valid when its variable is a continuous hidden one of g and its normaliser is finite; otherwise NaN, status bit 2
+    const int v = row_var[r];
+    const double lz = logz[r];
+    bool valid = v >= 0 && v < g.V && fabs(lz) <= DBL_MAX;
+    if (valid) valid = is_hidden(g.var_value[v]) && g.dom_cont[g.var_dom[v]] != 0;
+    const BeliefQ q{g, pots, s, v2f, rows, r, v, lz, valid};
+    gmkl::DevCtx<BeliefQ> ctx(sh, (int)threadIdx.x, q);
+    gmkl::kl_row(in, ctx, sh.kl, sh.abserr, sh.status, sh.neval);
+}
+
 static int validate_pbp(const lhvi_graph_t* g, const lhvi_pbp_t* s) {
     if (!g || !s) return LHVI_E_ARG;
     if (g->V < 0 || g->E < 0 || s->n <= 0 || s->T < 0) return LHVI_E_ARG;
@@ -3645,6 +3701,21 @@ int lhvi_pbp_quad(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp
     QueryRows rows{row_var, qptr, qedge, qmult};
     hipLaunchKernelGGL(pbp_quad_kernel, dim3(grid_for(nq)), dim3(BLOCK), 0, as_stream(stream), *g, *pots, *s, v2f, nq, rows, row_var,
                        lo, hi, epsabs, epsrel, z, abserr, status);
+    return check_launch();
+}
+
+int lhvi_pbp_kl(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_t* s, const double* v2f, int64_t nq,
+                const int32_t* row_var, const int64_t* qptr, const int32_t* qedge, const double* qmult, const double* logz,
+                int32_t Kp, const double* wp, const double* mup, const double* varp, const double* a, const double* b,
+                double epsabs, double epsrel, double* kl, double* abserr, int32_t* status, int32_t* neval, void* stream) {
+    if (int rc = validate_pbp(g, s)) return rc;
+    if (!pots || !v2f || nq < 1 || nq > 0x7fffffff || Kp < 1 || !(epsabs >= 0.0) || !(epsrel >= 0.0)) return LHVI_E_ARG;
+    if (!row_var || !logz || !wp || !mup || !varp || !a || !b || !kl) return LHVI_E_ARG;
+    if (g->V < 1 || !g->dom_lo || !g->dom_hi || !g->dom_val) return LHVI_E_ARG;
+    if (qptr && (!qedge || !qmult)) return LHVI_E_ARG;
+    QueryRows rows{row_var, qptr, qedge, qmult};
+    hipLaunchKernelGGL(pbp_kl_kernel, dim3((unsigned)nq), dim3(WAVE), 0, as_stream(stream), *g, *pots, *s, v2f, rows, row_var, logz,
+                       Kp, wp, mup, varp, a, b, epsabs, epsrel, kl, abserr, status, neval);
     return check_launch();
 }
 

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 25            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 26            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -143,6 +143,7 @@ MIX_MAX_K, MIX_TILE, MIX_ROWS = 128, 64, 4     # LHVI_MIX_MAX_K / LHVI_MIX_TILE 
 MIX_GAUSSIAN, MIX_VI = 0, 1                     # normaliser of lhvi_mix_prepare
 GMFIT_MAX_K = 16            # LHVI_GMFIT_MAX_K
 GMKL_MAX_PANELS = 1024      # LHVI_GMKL_MAX_PANELS
+GMKL_LOGQ = C.CFUNCTYPE(C.c_double, C.c_double, C.c_int64, C.c_void_p)     # logq(x, row, user) of lhvi_gm_kl_fn_host
 VI_GAUSSIAN_PDF = 2         # LHVI_VI_GAUSSIAN_PDF (lhvi_vi_t.quirks)
 NPVI_MAX_K, NPVI_MAX_SLOTS = 16, 24             # LHVI_NPVI_MAX_K / LHVI_NPVI_MAX_SLOTS
 
@@ -216,6 +217,8 @@ SIGNATURES = {
     'lhvi_pbp_var_fused': (C.c_int, [_G, _S, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _i32, _i32, _i32, _vp]),
     'lhvi_pbp_var_fused64': (C.c_int, [_G, _S, _vp, _vp, _vp, _vp, _vp, _u64, _u32, _vp, _vp, _vp, _i32, _i32, _vp]),
     'lhvi_pbp_quad': (C.c_int, [_G, _P, _S, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
+    'lhvi_pbp_kl': (C.c_int, [_G, _P, _S, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp,
+                              _vp]),
     'lhvi_vi_workspace_bytes': (_sz, [_G, _VI]),
     'lhvi_vi_grad': (C.c_int, [_G, _P, _VI, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     'lhvi_vi_adam_run': (C.c_int, [_G, _P, _VI, C.POINTER(ViOptStruct), _i32, _vp, _vp, _sz, _vp]),
@@ -272,6 +275,7 @@ SIGNATURES = {
     'lhvi_gm_kl_ws_doubles': (_sz, [_i32]),
     'lhvi_gm_kl': (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_kl_host': (C.c_int, [_i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
+    'lhvi_gm_kl_fn_host': (C.c_int, [_i32, _i32, _vp, _vp, _vp, GMKL_LOGQ, _vp, _vp, _vp, _f64, _f64, _vp, _vp, _vp, _vp]),
     'lhvi_hg_energy': (C.c_int, [C.POINTER(ExactStruct), _i64, _i64, _vp, _vp, _vp, _vp]),
     'lhvi_hg_energy_host': (C.c_int, [C.POINTER(ExactStruct), _i64, _i64, _vp, _vp, _vp]),
     'lhvi_argmax_first_ws_bytes': (_sz, [_i64]),

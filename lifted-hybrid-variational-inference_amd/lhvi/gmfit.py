@@ -57,9 +57,15 @@ class ScalarMixtures:
             raise ValueError('mu and var must have the same length')
         return cls(w, mu, var, host=host)
 
-    def kl(self, other, a=-np.inf, b=np.inf, **kw):
+    def kl(self, other, a=-np.inf, b=np.inf, rows=None, **kw):
         """``KL(self[r] || other[r])`` over ``[a, b]`` for every row (``lhvi.gmkl.kl_scalar_mixtures``; ``other``: a
-        ``ScalarMixtures`` or a ``(w, mu, var)`` tuple).  ``host`` defaults to this object's."""
+        ``ScalarMixtures`` or a ``(w, mu, var)`` tuple).  ``host`` defaults to this object's.  ``other`` may also be a particle
+        solver (``EPBP``, ``HybridLBP``): row r is then compared with the belief of the solver's variable ``rows[r]``
+        (``kl_from`` of ``lhvi/pbp.py``; on the device only, ``rows`` defaults to every continuous hidden variable)."""
+        if hasattr(other, 'kl_from'):
+            return other.kl_from(self, rows=rows, a=a, b=b, **kw)
+        if rows is not None:
+            raise ValueError('rows= goes with a particle solver as the second operand')
         from .gmkl import kl_scalar_mixtures
         kw.setdefault('host', self.host)
         return kl_scalar_mixtures(self, other, a, b, **kw)

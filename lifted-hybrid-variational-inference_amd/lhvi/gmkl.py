@@ -7,6 +7,10 @@ configuration, the Gibbs fits, the K-component beliefs of the variational solver
 no component can fall between the nodes of the first pass; each panel is then refined by bisection under QUADPACK's 21-point
 Gauss-Kronrod rule.
 
+``kl_mixture_logpdf`` is the same method with any Python log density as ``q`` (``lhvi_gm_kl_fn_host``, on the host only):
+the reference's ``kl_continuous_logpdf(log_p = a mixture, log_q = any callable)``.  A particle solver's belief as ``q`` on the
+device is ``EPBP.kl_from`` / ``HybridLBP.kl_from`` (``lhvi/pbp.py``, docs/kernels_pbkl.md).
+
 ``host=True`` runs the host twin (``lhvi_gm_kl_host``: the device's code, the nodes one after another) on NumPy arrays and
 needs no GPU; it is what the CPU tests use.  Nothing switches to it by itself: without a GPU the default raises ``LhviError``."""
 from __future__ import annotations
@@ -133,4 +137,45 @@ def kl_scalar_mixtures(p, q, a=-np.inf, b=np.inf, epsabs=1.49e-8, epsrel=1.49e-8
         _abi.check(l.lhvi_gm_kl(*head, _p(ws), *tail, _abi.stream_ptr()))
         if not tensors:
             kl, abserr, status, neval = (t.cpu().numpy() for t in (kl, abserr, status, neval))
+    return (kl, dict(abserr=abserr, status=status, neval=neval)) if info else kl
+
+
+def kl_mixture_logpdf(p, log_q, a=-np.inf, b=np.inf, epsabs=1.49e-8, epsrel=1.49e-8, info=False):
+    """``KL(p[r] || q[r])`` over ``[a[r], b[r]]`` with ``q`` given by its log density: ``log_q(x, row) -> float``.  ``p``, ``a``,
+    ``b``, the tolerances and ``info`` as for ``kl_scalar_mixtures``; the method is the same (the range and the panels come from
+    ``p`` alone), run on the host through a ``ctypes`` callback (``lhvi_gm_kl_fn_host``), so NumPy arrays in and out.  Where
+    ``log_q`` is ``-inf`` and ``p`` is not 0 the result is ``+inf`` with status bit 0.  An exception in ``log_q`` is raised
+    again after the call."""
+    if any(_is_tensor(t) for t in list(_parts(p, 'p')) + [a, b]):
+        raise ValueError('kl_mixture_logpdf runs on the host and takes NumPy arrays')
+    if not callable(log_q):
+        raise ValueError('log_q must be a callable log_q(x, row)')
+    if not (float(epsabs) >= 0 and float(epsrel) >= 0):
+        raise ValueError('epsabs and epsrel must not be negative')
+    kind = _Numpy
+    wp, mup, varp = _mixture(kind, p, 'p')
+    a, b = kind.array(a).reshape(-1), kind.array(b).reshape(-1)
+    sizes = {int(t.shape[0]) for t in (wp, mup, varp, a, b)} - {1}
+    if len(sizes) > 1:
+        raise ValueError('p, a and b disagree on the number of rows: %s' % sorted(sizes))
+    R = sizes.pop() if sizes else 1
+    Kp = int(mup.shape[1])
+    wp, mup, varp = (kind.rows(t, (R, Kp)) for t in (wp, mup, varp))
+    a, b = kind.rows(a, (R,)), kind.rows(b, (R,))
+    kl, abserr = kind.empty(R, np.float64), kind.empty(R, np.float64)
+    status, neval = kind.empty(R, np.int32), kind.empty(R, np.int32)
+    raised = []
+
+    def call(x, row, _user):
+        try:
+            return float(log_q(x, row))
+        except BaseException as exc:        # (an exception cannot cross the C frames: keep the first, finish the row on NaN)
+            if not raised:
+                raised.append(exc)
+            return float('nan')
+    cb = _abi.GMKL_LOGQ(call)
+    _abi.check(_abi.lib().lhvi_gm_kl_fn_host(R, Kp, _p(wp), _p(mup), _p(varp), cb, None, _p(a), _p(b), float(epsabs), float(epsrel),
+                                            _p(kl), _p(abserr), _p(status), _p(neval)))
+    if raised:
+        raise raised[0]
     return (kl, dict(abserr=abserr, status=status, neval=neval)) if info else kl

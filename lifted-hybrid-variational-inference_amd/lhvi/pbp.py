@@ -631,6 +631,81 @@ class _ParticleSweep:
             z[rows], st[rows] = zt.cpu().numpy(), stt.cpu().numpy()
         return z, st
 
+    def _kl_rows(self, rows):
+        """the query rows of ``kl_from`` as an int32 array; ``ValueError`` for a row that is no continuous hidden variable"""
+        flat = self.flat
+        cont = flat.var_hidden & flat.var_cont
+        if rows is None:
+            return np.flatnonzero(cont).astype(np.int32)
+        index = getattr(flat, 'var_index', None) or {}
+
+        def one(r):         # an index, a random variable of the graph, or (lifted) a ground variable through its cluster
+            if isinstance(r, (int, np.integer)):
+                return int(r)
+            key = r if r in index else getattr(r, 'cluster', None)
+            if key not in index:
+                raise ValueError('rows must name variables of the solver\'s graph')
+            return index[key]
+        rows = np.asarray([one(r) for r in (rows.tolist() if hasattr(rows, 'tolist') else list(rows))], dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= flat.V):
+            raise ValueError('rows must name variables of the solver\'s graph, 0 .. %d' % (flat.V - 1))
+        bad = rows[~cont[rows]]
+        if bad.size:
+            raise ValueError('kl_from compares continuous hidden variables; rows %s are observed or discrete' % bad[:8].tolist())
+        return rows.astype(np.int32)
+
+    def _kl_logz(self):
+        """``log`` of every row's belief normaliser as a host array [V] (NaN: not a continuous hidden row, or the normaliser
+        overflowed).  The base class normalises like ``HybridLBP.belief`` (HLBP:343-382): the 20-point ``log_area`` over the
+        domain, ``log(area) + shift``."""
+        z, shift = self._cached_area()
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.log(z) + shift
+
+    def kl_from(self, p, rows=None, a=-np.inf, b=np.inf, epsabs=1.49e-8, epsrel=1.49e-8, info=False):
+        """``KL(p[r] || belief of variable rows[r])`` for every row in ONE launch (``lhvi_pbp_kl``, docs/kernels_pbkl.md): the
+        drivers' ``kl_err = kl_continuous_logpdf(log_p, curry_epbp_belief(bp, rv, log_belief=True))`` with ``p`` the baseline's
+        mixture marginals.  ``p``: a ``ScalarMixtures`` or a ``(w, mu, var)`` tuple, broadcast as in ``kl_scalar_mixtures`` (a
+        one-row ``p`` serves every row); ``rows``: variable indices of the solver's graph (or its random variables), default
+        every continuous hidden variable in index order; ``a``, ``b``: scalars or [R].  The belief is normalised as the solver's
+        own ``belief`` does it: for ``EPBP`` by ``quad_all``'s ``z`` (EPBP:321-331), for ``HybridLBP`` by the 20-point
+        ``log_area`` over the domain (HLBP:343-382).  A row whose normaliser overflowed is NaN with status bit 2, the others are
+        unaffected.  Device tensors in give device tensors out, arrays in give arrays out; ``info=True`` returns
+        ``(kl, dict(abserr=, status=, neval=))``.  ``ValueError`` before any launch for an observed or discrete row, or when the
+        number of rows does not match ``p``."""
+        from . import gmkl
+        rows = self._kl_rows(rows)
+        R = int(rows.size)
+        parts = list(gmkl._parts(p, 'p')) + [a, b]
+        tensors = [t for t in parts if gmkl._is_tensor(t)]
+        if not (float(epsabs) >= 0 and float(epsrel) >= 0):
+            raise ValueError('epsabs and epsrel must not be negative')
+        shapes = [tuple(t.shape) if hasattr(t, 'shape') else np.shape(t) for t in parts]
+        sizes = {int(s[0]) for s in shapes[:3] if len(s) == 2} | {int(np.prod(s)) for s in shapes[3:]}
+        if R == 0:
+            raise ValueError('no rows to compare')
+        if sizes - {1, R}:
+            raise ValueError('p, a and b must have one row or as many as rows (%d): %s' % (R, sorted(sizes - {1, R})))
+        if self.flat.lifted and not getattr(self, '_stable_partition', False):
+            raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
+        torch = _abi.require_gpu()
+        kind = gmkl._Torch(torch, self.particles.device)
+        wp, mup, varp = gmkl._mixture(kind, p, 'p')
+        Kp = int(mup.shape[1])
+        wp, mup, varp = (kind.rows(t, (R, Kp)) for t in (wp, mup, varp))
+        a, b = kind.rows(kind.array(a).reshape(-1), (R,)), kind.rows(kind.array(b).reshape(-1), (R,))
+        logz = _abi.to_dev(np.ascontiguousarray(self._query_cache('kl_logz', self._kl_logz)[rows], dtype=np.float64))
+        rv_t = _abi.to_dev(rows)
+        kl, abserr = kind.empty(R, np.float64), kind.empty(R, np.float64)
+        status, neval = kind.empty(R, np.int32), kind.empty(R, np.int32)
+        _abi.check(_abi.lib().lhvi_pbp_kl(self.dg.g, self.dg.p, self._struct(), _abi.ptr(self.v2f), R, _abi.ptr(rv_t), None, None, None,
+                                          _abi.ptr(logz), Kp, _abi.ptr(wp), _abi.ptr(mup), _abi.ptr(varp), _abi.ptr(a), _abi.ptr(b),
+                                          float(epsabs), float(epsrel), _abi.ptr(kl), _abi.ptr(abserr), _abi.ptr(status),
+                                          _abi.ptr(neval), _abi.stream_ptr()))
+        if not tensors:
+            kl, abserr, status, neval = (t.cpu().numpy() for t in (kl, abserr, status, neval))
+        return (kl, dict(abserr=abserr, status=status, neval=neval)) if info else kl
+
     def _per_var(self, a):
         torch = _abi.require_gpu()
         t = torch.as_tensor(np.broadcast_to(np.asarray(a, dtype=np.float64), (self.flat.V,)).copy()) if not torch.is_tensor(a) else a
@@ -850,6 +925,13 @@ class EPBP(_ParticleSweep):
         b = dict(zip(vals, (e ** t for t in self._belief_rv_points(v, vals).tolist())))
         self.message_normalization(b)
         return log(b[x]) if log_belief else b[x]
+
+    def _kl_logz(self):
+        """``log`` of ``quad_all()``'s ``z`` (the cache ``belief`` fills too): the normaliser of ``EPBP.belief`` (EPBP:321-331);
+        NaN where ``e ** belief_rv`` overflowed (status 3), which ``kl_from`` reports as an invalid row"""
+        zs, _ = self._query_cache('quad', self.quad_all)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            return np.log(zs)
 
     def probability(self, a, b, rv):
         if rv.value is None and rv.domain.continuous:
