@@ -2247,7 +2247,9 @@ __global__ void __launch_bounds__(BLOCK) pbp_quad_kernel(lhvi_graph_t g, lhvi_po
     double area = r.result, errsum = r.abserr;
     bool overflow = r.overflow;
     double errbnd = fmax(epsabs, epsrel * fabs(area));
-    const bool done0 = (r.abserr <= errbnd && r.abserr != r.resabs) || r.abserr == 0.0;
+    // dqage.f's first-rule test `abserr.ne.resabs` is on the variable that receives dqk21's resasc, the integral of |f - mean|: an
+    // estimate equal to it was cut off at its ceiling (one node saw a narrow peak) and proves nothing, so the bisection starts
+    const bool done0 = (r.abserr <= errbnd && r.abserr != r.resasc) || r.abserr == 0.0;
     if (!done0 && !overflow) {
         st = 1;
         while (n < QUAD_LIMIT) {
