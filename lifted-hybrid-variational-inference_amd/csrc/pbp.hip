@@ -2586,8 +2586,14 @@ __device__ __forceinline__ double cos_turns(double t) {
 // 53-bit uniforms gives r cos(2 pi u2) and r sin(2 pi u2).  Particle j of a variable takes block (j & 31) | (j >> 6 << 5) and the
 // cosine (bit 5 of j clear) or the sine (set): particles j and j + 32 share a block, so that a wavefront can draw for two variables
 // at once -- 32 blocks each -- whichever two they are (pbp_resample_uniq_kernel).
-// log / sqrt / cos are the short routines above (absolute error < 1e-15 on z): a sampler needs reproducibility -- every
-// rank runs this same code, so replicas of a boundary variable still draw identical particles -- not the last ulp.
+// log / sqrt / cos are the short routines above: a sampler needs reproducibility -- every rank runs this same code, so replicas
+// of a boundary variable still draw identical particles -- not the last ulp.  What holds for z (tests/pbp_sampler_models.py,
+// z_bound): |dz| <= |c| dl / rad + rad E_cos + 3 ulp(z), dl the log's error (table: 5e-16 absolute next to u1 = 1, so the term
+// grows as 1 / rad -- 5e-13 at rad = 1e-3 -- ; series: 2 ulp), E_cos <= 5.4e-16: about 1e-15 at the median draw, no fixed
+// absolute figure.  Measured on the MI355X: at most 7.7e-16 over 1.3e5 draws, half the bound (tests/test_gpu_pbp_sampler.py).
+// Outside the domain of these routines: u1 = 1.0 (probability 2^-53) makes the radicand 0 or negative and the radius NaN, which
+// the clip turns into dom_lo; sqrt_pos(0) is NaN too, so a proposal variance of exactly 0 must not reach the fused draws (the
+// proposal kernels never produce one while var_threshold > 0).
 // `logtab` = LDS copy of the log table (load_log_table), or nullptr for the table-free series
 __device__ __forceinline__ void philox_normal_pair(uint64_t seed, uint64_t gid, uint32_t block, uint32_t iteration,
                                                    const LogRec* __restrict__ logtab, double& zc, double& zs) {
