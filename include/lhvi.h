@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 26  /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 27 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -49,7 +49,8 @@ extern "C" {
                               * 23: lhvi_gauss_chain_*, LHVI_GAUSS_CHAIN_MAX_BLOCK;
                               * 24: lhvi_gm_kl, lhvi_gm_kl_ws_doubles, lhvi_gm_kl_host, LHVI_GMKL_MAX_PANELS;
                               * 25: lhvi_hg_energy, lhvi_hg_energy_host, lhvi_argmax_first, lhvi_argmax_first_ws_bytes, lhvi_argmax_first_host;
-                              * 26: lhvi_pbp_kl, lhvi_gm_kl_fn_host */
+                              * 26: lhvi_pbp_kl, lhvi_gm_kl_fn_host;
+                              * 27: lhvi_exact_configs_at, lhvi_exact_config_at_host, lhvi_gibbs_rb_disc, lhvi_gibbs_rb_disc_host */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -790,6 +791,34 @@ int lhvi_gibbs_run(const lhvi_gibbs_t* m, int64_t chains, int32_t it_begin, int3
  * is ignored.  LHVI_E_NOT_PD when a J is not positive definite (x_d then holds the state). */
 int lhvi_gibbs_chain_host(const lhvi_gibbs_t* m, int32_t it_begin, int32_t it_end, int32_t* x_d, const double* z, const double* u,
                           int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2);
+
+/* ---- Rao-Blackwellised marginals of the block Gibbs sampler (csrc/gibbs_rb.hip, csrc/gibbs_rb.hpp) ---------------------------
+ * The conditional Gaussian of explicit discrete states: lhvi_exact_configs with row s of x_d [S][Nd] (int32 digits, each inside
+ * [0, dstates[n]): the caller checks) in the place of a configuration index.  logp [S] or NULL, means [S][Nc], vars [S][Nc]; rows
+ * indexed by s.  Neither m->M nor m->dstride is read, so a model whose configurations cannot be numbered (M = 0) is served.  The
+ * operations are those of lhvi_exact_configs after its digit decode, in the same order: a row of digits gives the bits that call
+ * gives for that configuration, whatever `lanes`.  Launch shape and LDS of lhvi_exact_configs (lhvi_exact_lds_bytes).
+ * bad [1]: the caller sets it to UINT64_MAX; a row whose J is not positive definite lowers it to s (atomic min).
+ * LHVI_E_UNSUPPORTED: Nc > LHVI_EXACT_MAX_NC or more than 64 KiB of LDS. */
+int lhvi_exact_configs_at(const lhvi_exact_t* m, int64_t S, const int32_t* x_d, int32_t lanes, double* logp, double* means,
+                          double* vars, uint64_t* bad, void* stream);
+/* one row of digits on the HOST through the device's code; every pointer is host memory, logp, mean, var may be NULL.
+ * LHVI_E_ARG for a digit outside its range, LHVI_E_NOT_PD when J is not positive definite. */
+int lhvi_exact_config_at_host(const lhvi_exact_t* m, const int32_t* x_d_row, double* logp, double* mean, double* var);
+/* prob_sum [chains][sum dstates] += sum over the kept samples s in [s_begin, s_end) of p(x_n = k | x_d,-n, x_c) at the sample
+ * (disc [chains][num_samples][Nd], cont [chains][num_samples][Nc], as lhvi_gibbs_run stored them): the reduced tables of the
+ * strictly hybrid factors at the sample's x_c, every variable's log probabilities over its table factors, then its hybrid
+ * factors, in factor order with the other digits at the sample's values, and the sampler's softmax exp(v - (max + log sum)),
+ * added in sample order by the lane that owns the state.  The caller zeroes prob_sum before the first call; a chain's sums
+ * depend neither on `lanes`, nor on `chains`, nor on the split of [0, num_samples) over calls.  Workspace, lanes and the place of
+ * the reduced tables (LDS, or m->table_scratch) are those of lhvi_gibbs_run (lhvi_gibbs_lds_bytes).  m->disc_block_its,
+ * num_burnin and seed are not read.  LHVI_E_UNSUPPORTED: Nc > LHVI_EXACT_MAX_NC or more than 64 KiB of LDS. */
+int lhvi_gibbs_rb_disc(const lhvi_gibbs_t* m, int64_t chains, int32_t s_begin, int32_t s_end, int32_t lanes, const int32_t* disc,
+                       const double* cont, double* prob_sum, void* stream);
+/* one chain on the HOST through the device's code: disc [num_samples][Nd], cont [num_samples][Nc], prob_sum [sum dstates];
+ * m->table_scratch is ignored.  LHVI_E_ARG for a digit outside its range. */
+int lhvi_gibbs_rb_disc_host(const lhvi_gibbs_t* m, int32_t s_begin, int32_t s_end, const int32_t* disc, const double* cont,
+                            double* prob_sum);
 
 /* ---- Exact Gaussian-MRF marginals: dense blocked fp64 Cholesky (osi/utils.py get_gaussian_mean_params_from_quadratic_params;
  * csrc/gauss_exact.hip, csrc/gauss_exact.hpp) ----------------------------------------------------------------------------------

@@ -112,15 +112,19 @@ LHVI_HD int cholesky(int Nc, double* mat, double* ldiag, double* dinv, const Ctx
     return bad;
 }
 
-// One configuration.  Outputs (each may be null): logp = log p~(x_d), mean [Nc], var [Nc] = diag(J^-1), cov [Nc][Nc] = J^-1.
-// Returns 1 when J is not positive definite (a pivot <= 0 or NaN), the same value in every lane.
+// the digits of a configuration's workspace W
+LHVI_HD int32_t* digits(int Nc, double* W) { return reinterpret_cast<int32_t*>(W + Nc * ld_of(Nc) + 5 * Nc); }
+
+// The conditional Gaussian of the discrete state whose digits the lanes have just written to digits(Nc, W) (digit d by lane
+// d % lanes; assemble's first barrier publishes them): config() below after its digit decode, and csrc/gibbs_rb.hip with a row of
+// explicit digits.  Reads neither m.M nor m.dstride.  Outputs (each may be null): logp = log p~(x_d), mean [Nc],
+// var [Nc] = diag(J^-1), cov [Nc][Nc] = J^-1.  Returns 1 when J is not positive definite (a pivot <= 0 or NaN), the same value
+// in every lane.
 template <class Ctx>
-LHVI_HD int config(const lhvi_exact_t& m, int64_t cfg, double* W, const Ctx& ctx, double* logp, double* mean, double* var,
-                   double* cov) {
-    const int Nc = m.Nc, Nd = m.Nd, ld = ld_of(Nc);
+LHVI_HD int config_at(const lhvi_exact_t& m, double* W, const Ctx& ctx, double* logp, double* mean, double* var, double* cov) {
+    const int Nc = m.Nc, ld = ld_of(Nc);
     double *mat = W, *b = W + Nc * ld, *y = b + Nc, *mu = y + Nc, *ldiag = mu + Nc, *dinv = ldiag + Nc;
     int32_t* dig = reinterpret_cast<int32_t*>(dinv + Nc);
-    for (int d = ctx.lane; d < Nd; d += ctx.lanes) dig[d] = (int32_t)((cfg / m.dstride[d]) % m.dstates[d]);
     double c, logdet;
     assemble(m, dig, mat, b, ctx, c);
     const double ts = table_sum(m, dig);
@@ -172,6 +176,19 @@ LHVI_HD int config(const lhvi_exact_t& m, int64_t cfg, double* W, const Ctx& ctx
     if (logp && ctx.lane == 0) *logp = ts + t;
     ctx.sync();                                      // the workspace may be reused by the caller's next configuration
     return bad;
+}
+
+// One configuration by its index: the digit decode, then config_at.
+template <class Ctx>
+LHVI_HD int config(const lhvi_exact_t& m, int64_t cfg, double* W, const Ctx& ctx, double* logp, double* mean, double* var,
+                   double* cov) {
+    const int Nc = m.Nc, Nd = m.Nd;
+    // digits(Nc, W), spelled as config_at's own chain of offsets: the compiler then shares the address with it, and
+    // exact_config_kernel keeps the registers it had before the split (scripts/kernel_resources.sh)
+    double* dinv = W + Nc * ld_of(Nc) + Nc + Nc + Nc + Nc;
+    int32_t* dig = reinterpret_cast<int32_t*>(dinv + Nc);
+    for (int d = ctx.lane; d < Nd; d += ctx.lanes) dig[d] = (int32_t)((cfg / m.dstride[d]) % m.dstates[d]);
+    return config_at(m, W, ctx, logp, mean, var, cov);
 }
 
 }  // namespace exact

@@ -102,6 +102,51 @@ LHVI_HD int64_t local_with(const int32_t* p, int nd, const int32_t* dig, int n, 
     return l;
 }
 
+// The two pieces of the discrete block that iteration() below shares with the Rao-Blackwellised marginals (csrc/gibbs_rb.hpp);
+// their floating-point operations are iteration()'s own.
+//
+// reduced_tables: the reduced log table of every strictly hybrid factor at xc (Potential.py get_table_params_given_x_c):
+// sum(A_k * x x^T) row-major, + b_k . x, + c_k, entry k by the lane that owns it.  The caller syncs after.
+template <class Ctx>
+LHVI_HD void reduced_tables(const lhvi_gibbs_t& g, const double* xc, double* tab, const Ctx& ctx) {
+    const lhvi_exact_t& m = g.ex;
+    for (int h = 0; h < g.n_hyb; ++h) {
+        const int32_t* rec = m.quad_desc + m.quad_ptr[g.hyb_quad[h]];
+        const int nd = rec[0], nc = rec[1], stride = nc * nc + nc + 1;
+        const int32_t* sc = rec + 3 + 2 * nd;
+        const int L = g.hyb_off[h + 1] - g.hyb_off[h];
+        for (int k = ctx.lane; k < L; k += ctx.lanes) {
+            const double* P = m.quad_par + rec[2] + (int64_t)k * stride;
+            double s = 0.0, t = 0.0;
+            for (int a = 0; a < nc; ++a)
+                for (int j = 0; j < nc; ++j) s += P[a * nc + j] * (xc[sc[a]] * xc[sc[j]]);
+            for (int a = 0; a < nc; ++a) t += P[nc * nc + a] * xc[sc[a]];
+            tab[g.hyb_off[h] + k] = (s + t) + P[nc * nc + nc];
+        }
+    }
+}
+
+// cond_lprobs: lprobs[j] = log p~(x_n = j | the other digits, x_c) up to a constant: variable n's table factors, then its hybrid
+// factors' reduced tables, in factor order, state j by the lane that owns it.  The caller syncs after.
+template <class Ctx>
+LHVI_HD void cond_lprobs(const lhvi_gibbs_t& g, int n, const int32_t* dig, const double* tab, double* lprobs, const Ctx& ctx) {
+    const lhvi_exact_t& m = g.ex;
+    const int d = m.dstates[n];
+    for (int j = ctx.lane; j < d; j += ctx.lanes) {
+        double v = 0.0;
+        for (int e = g.vt_ptr[n]; e < g.vt_ptr[n + 1]; ++e) {
+            const int32_t* rec = m.tab_desc + m.tab_ptr[g.vt_fac[e]];
+            v += m.tab_par[rec[1] + local_with(rec + 2, rec[0], dig, n, j)];
+        }
+        for (int e = g.vh_ptr[n]; e < g.vh_ptr[n + 1]; ++e) {
+            const int h = g.vh_fac[e];
+            const int32_t* rec = m.quad_desc + m.quad_ptr[g.hyb_quad[h]];
+            v += tab[g.hyb_off[h] + local_with(rec + 3, rec[0], dig, n, j)];
+        }
+        lprobs[j] = v;
+    }
+}
+
 // One outer iteration `it` of a chain whose x_d is in w.dig.  dead: the chain met a J that is not positive definite; it keeps
 // its x_d from then on and stores nothing.  Returns 1 when this iteration's J is not positive definite (and sets dead), the
 // same value in every lane.
@@ -138,40 +183,14 @@ LHVI_HD int iteration(const lhvi_gibbs_t& g, int it, const Draws& dr, const Work
                 if (r < i) w.xc[r] -= w.mat[i * ld + r] * w.xc[i];
         }
     }
-    // 2. the reduced log table of every strictly hybrid factor at x_c (Potential.py get_table_params_given_x_c), once per
-    // outer iteration: sum(A_k * x x^T) row-major, + b_k . x, + c_k
-    for (int h = 0; h < g.n_hyb; ++h) {
-        const int32_t* rec = m.quad_desc + m.quad_ptr[g.hyb_quad[h]];
-        const int nd = rec[0], nc = rec[1], stride = nc * nc + nc + 1;
-        const int32_t* sc = rec + 3 + 2 * nd;
-        const int L = g.hyb_off[h + 1] - g.hyb_off[h];
-        for (int k = ctx.lane; k < L; k += ctx.lanes) {
-            const double* P = m.quad_par + rec[2] + (int64_t)k * stride;
-            double s = 0.0, t = 0.0;
-            for (int a = 0; a < nc; ++a)
-                for (int j = 0; j < nc; ++j) s += P[a * nc + j] * (w.xc[sc[a]] * w.xc[sc[j]]);
-            for (int a = 0; a < nc; ++a) t += P[nc * nc + a] * w.xc[sc[a]];
-            w.tab[g.hyb_off[h] + k] = (s + t) + P[nc * nc + nc];
-        }
-    }
+    // 2. the reduced tables at x_c, once per outer iteration
+    reduced_tables(g, w.xc, w.tab, ctx);
     ctx.sync();
     // 3. x_d | x_c: disc_block_its sweeps over the variables in order (disc_mrf_sampler.pyx gibbs_sample_one)
     for (int sweep = 0; sweep < g.disc_block_its; ++sweep)
         for (int n = 0; n < Nd; ++n) {
             const int d = m.dstates[n];
-            for (int j = ctx.lane; j < d; j += ctx.lanes) {
-                double v = 0.0;
-                for (int e = g.vt_ptr[n]; e < g.vt_ptr[n + 1]; ++e) {
-                    const int32_t* rec = m.tab_desc + m.tab_ptr[g.vt_fac[e]];
-                    v += m.tab_par[rec[1] + local_with(rec + 2, rec[0], w.dig, n, j)];
-                }
-                for (int e = g.vh_ptr[n]; e < g.vh_ptr[n + 1]; ++e) {
-                    const int h = g.vh_fac[e];
-                    const int32_t* rec = m.quad_desc + m.quad_ptr[g.hyb_quad[h]];
-                    v += w.tab[g.hyb_off[h] + local_with(rec + 3, rec[0], w.dig, n, j)];
-                }
-                w.lprobs[j] = v;
-            }
+            cond_lprobs(g, n, w.dig, w.tab, w.lprobs, ctx);
             ctx.sync();
             // softmax (:43-58) and the first state with u <= cumulative sum (:62-70), by every lane with the same bits; the
             // last state catches rounding

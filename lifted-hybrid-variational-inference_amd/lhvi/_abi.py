@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 26            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 27            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -270,6 +270,10 @@ SIGNATURES = {
     'lhvi_mix_marginal_map_host': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     'lhvi_mix_log_belief_host': (C.c_int, [_MX, _i64, _vp, _i32, _vp, _i32, _vp, _vp]),
     'lhvi_gibbs_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_exact_configs_at': (C.c_int, [C.POINTER(ExactStruct), _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_exact_config_at_host': (C.c_int, [C.POINTER(ExactStruct), _vp, _vp, _vp, _vp]),
+    'lhvi_gibbs_rb_disc': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    'lhvi_gibbs_rb_disc_host': (C.c_int, [C.POINTER(GibbsStruct), _i32, _i32, _vp, _vp, _vp]),
     'lhvi_gm_fit': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit_host': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_kl_ws_doubles': (_sz, [_i32]),

@@ -6,6 +6,8 @@ enumeration half): ``p(x_d, x_c) = p(x_d) N(x_c; mu(x_d), Sig(x_d))``.
 ``belief_all``, no full covariances unless asked).  The host flattens the factors once (``flatten_factors``); every
 configuration is then one dense fp64 factorisation on the device (``csrc/exact.hip``).  There is no CPU path: without a GPU
 the calls raise ``LhviError`` (``config_host`` runs single configurations through the device's code for the tests).
+``configs_at`` / ``config_at_host`` are the same computation for explicit rows of discrete digits (``csrc/gibbs_rb.hip``): they
+read neither ``M`` nor ``dstride`` and serve the Rao-Blackwellised marginals of ``lhvi/gibbs.py``.
 
 Deliberate differences (docs/kernels_exact.md): the conditional Gaussian comes from a Cholesky factor of ``J = -(A + A^T)``
 instead of ``np.linalg.inv(-2A)`` (equal for the symmetric ``A`` every potential class yields); a ``J`` that is not positive
@@ -362,13 +364,7 @@ class _DeviceRun:
         torch = _abi._torch()
         M, Nc = self.model.M, self.model.Nc
         dev = self.logp.device
-        if M <= MAX_CANDIDATES:
-            cand = self.means.t().contiguous()
-        else:       # the components of largest peak density w_k / sqrt(var_kj)
-            score = (self.table[:, None] / torch.sqrt(self.vars)).t()
-            cand = self.means.t().gather(1, score.topk(MAX_CANDIDATES, dim=1).indices).contiguous()
-        lo_d, hi_d = _abi.to_dev(np.asarray(lo, dtype=np.float64)), _abi.to_dev(np.asarray(hi, dtype=np.float64))
-        cand = torch.minimum(torch.maximum(cand, lo_d[:, None]), hi_d[:, None])
+        cand, lo_d, hi_d = map_candidates(self.table, self.means, self.vars, lo, hi)
         dens = self.mixture(cand)[:, :, 0]
         S = int(min(cand.shape[1], max_starts))
         x = cand.gather(1, dens.topk(S, dim=1).indices).contiguous()
@@ -378,6 +374,87 @@ class _DeviceRun:
                                                     _abi.ptr(vmin), int(max_iter), _abi.ptr(logf), _abi.stream_ptr()))
         best = logf.argmax(dim=1, keepdim=True)
         return x.gather(1, best)[:, 0], logf.gather(1, best)[:, 0]
+
+
+def map_candidates(weights, means, vars, lo, hi):
+    """the starting candidates of the marginal MAP of every variable of a mixture (weights [M], means / vars [M, Nc], device
+    tensors; lo / hi [Nc] host arrays): every component mean up to MAX_CANDIDATES components, else the means of the components
+    of largest peak density w_k / sqrt(var_kj), clipped to the domain.  Returns (cand [Nc, n], lo, hi on the device); shared by
+    the exact baseline and the Rao-Blackwellised mixtures of the Gibbs baseline."""
+    torch = _abi._torch()
+    if means.shape[0] <= MAX_CANDIDATES:
+        cand = means.t().contiguous()
+    else:       # the components of largest peak density w_k / sqrt(var_kj)
+        score = (weights[:, None] / torch.sqrt(vars)).t()
+        cand = means.t().gather(1, score.topk(MAX_CANDIDATES, dim=1).indices).contiguous()
+    lo_d, hi_d = _abi.to_dev(np.asarray(lo, dtype=np.float64)), _abi.to_dev(np.asarray(hi, dtype=np.float64))
+    return torch.minimum(torch.maximum(cand, lo_d[:, None]), hi_d[:, None]), lo_d, hi_d
+
+
+def config_at_host(model, x_d):
+    """the conditional Gaussian of one row of digits on the CPU through the device's code (``lhvi_exact_config_at_host``):
+    (logp, mean, var).  Serves a model with ``M = 0``."""
+    row = np.ascontiguousarray(x_d, dtype=np.int32).reshape(model.Nd)
+    if model.Nd and (row.min() < 0 or (row >= model.dstates).any()):
+        raise ValueError('x_d holds a state outside its variable\'s range')
+    logp, mean, var = np.zeros(1), np.zeros(max(model.Nc, 1)), np.zeros(max(model.Nc, 1))
+    rc = _abi.lib().lhvi_exact_config_at_host(model.host_struct(), row.ctypes.data if row.size else None, logp.ctypes.data,
+                                              mean.ctypes.data, var.ctypes.data)
+    if rc == _abi.E_NOT_PD:
+        raise ValueError('the precision matrix J = -2A is not positive definite at the discrete state %r'
+                         % (tuple(int(k) for k in row),))
+    _abi.check(rc)
+    return float(logp[0]), mean[:model.Nc], var[:model.Nc]
+
+
+def configs_at(model, s, rows, lanes=None, chunk=CHUNK):
+    """the conditional Gaussians of explicit discrete states on the device (``lhvi_exact_configs_at``): rows [S, Nd] int32 device
+    tensor, s the model's device struct.  Returns (logp [S], means [S, Nc], vars [S, Nc]) as device tensors, launched in chunks
+    of ``chunk`` rows.  The digits are checked against ``model.dstates`` before the first launch; a row whose J is not positive
+    definite raises ``ValueError`` naming the state; ``MemoryError`` with the byte count when the outputs do not fit."""
+    torch = _abi.require_gpu()
+    S, Nd, Nc = int(rows.shape[0]), model.Nd, model.Nc
+    if rows.dim() != 2 or rows.shape[1] != Nd or rows.dtype != torch.int32:
+        raise ValueError('rows must be an int32 tensor [S, %d]' % Nd)
+    if Nc > MAX_NC:
+        raise ValueError('Nc = %d continuous variables exceed LHVI_EXACT_MAX_NC = %d' % (Nc, MAX_NC))
+    need = 8 * S * (1 + 2 * max(Nc, 1))
+    free = int(torch.cuda.mem_get_info()[0])
+    if need > free:
+        raise MemoryError('%d discrete states with Nc = %d need %d bytes of device memory for the outputs, %d are free'
+                          % (S, Nc, need, free))
+    rows = rows.contiguous()
+    if S and Nd:
+        top = _abi.to_dev(np.asarray(model.dstates, dtype=np.int32))
+        if bool(((rows < 0) | (rows >= top[None, :])).any().item()):
+            raise ValueError('rows hold a state outside its variable\'s range')
+    lanes = default_lanes(Nc) if lanes is None else int(lanes)
+    dev, f64 = rows.device, torch.float64
+    logp = torch.empty(S, dtype=f64, device=dev)
+    means_buf = torch.empty(S, max(Nc, 1), dtype=f64, device=dev)       # real pointers at Nc = 0, as in _DeviceRun
+    vars_buf = torch.empty(S, max(Nc, 1), dtype=f64, device=dev)
+    bad = torch.full((1,), -1, dtype=torch.int64, device=dev)           # UINT64_MAX
+    l, st = _abi.lib(), _abi.stream_ptr()
+    for b in range(0, S, int(chunk)):
+        n = min(int(chunk), S - b)
+        _abi.check(l.lhvi_exact_configs_at(s, n, _abi.ptr(rows[b:]) if Nd else None, lanes, _abi.ptr(logp[b:]),
+                                           _abi.ptr(means_buf[b:]), _abi.ptr(vars_buf[b:]), _abi.ptr(bad), st))
+        first = int(bad.item())
+        if first != -1:
+            raise ValueError('the precision matrix J = -2A is not positive definite at the discrete state %r'
+                             % (tuple(int(k) for k in rows[b + first].cpu().numpy()),))
+    return logp, means_buf[:, :Nc], vars_buf[:, :Nc]
+
+
+def mixture_run(weights, means, vars):
+    """a ``_DeviceRun`` around given mixture parameters on the device (weights [M], means / vars [M, Nc]): its ``mixture`` and
+    ``cont_map`` are the exact baseline's kernels on these components"""
+    run = _DeviceRun.__new__(_DeviceRun)
+    run.model = ExactModel([int(means.shape[0])], int(means.shape[1]))
+    run.table = run.logp = weights.contiguous()
+    run.means, run.vars = means.contiguous(), vars.contiguous()
+    run._mix = None
+    return run
 
 
 # ---- the reference's functions -----------------------------------------------------------------------------------------------

@@ -13,6 +13,11 @@ Deliberate differences (docs/kernels_gibbs.md): x_c is drawn as ``mu + L^-T z`` 
 ``drand48`` / NumPy's generator; ``HybridGaussianSampler.map`` of a discrete variable works.  ``GibbsHybridGaussian`` fits the
 mixtures of all continuous variables to the kept samples on the device (``fit_marginals``, ``lhvi/gmfit.py``);
 ``fit_scalar_gm_from_samples`` and ``HybridGaussianSampler.map`` keep calling scikit-learn like the reference.
+
+Beyond the reference (docs/kernels_gibbs_rb.md): ``GibbsHybridGaussian.rb_marginals()`` / ``rb_disc_marginals()`` /
+``rb_moments()`` and ``rao_blackwell=True`` of ``map`` / ``map_all`` / ``belief`` average the exact conditionals
+``p(x_c | x_d)`` and ``p(x_n | x_d,-n, x_c)`` over the kept samples (``csrc/gibbs_rb.hip``); ``rb_disc_host`` runs one chain of
+the latter through the device's code on the CPU.
 """
 from __future__ import annotations
 
@@ -23,6 +28,7 @@ import types
 import numpy as np
 
 from . import _abi, hg_energy
+from . import exact as _exact
 from .exact import MAX_NC, ExactHybridGaussian, ExactModel, _Factor, flatten_factors, joint_map_dict
 from .potentials import LogTable
 
@@ -123,6 +129,26 @@ def chain_host(gm, x_d, z, u, disc_block_its, num_burnin, num_samples, it_begin=
         raise ValueError(_not_pd_message(r.x_d))
     _abi.check(rc)
     return r
+
+
+def rb_disc_host(gm, disc, cont, s_begin=0, s_end=None, prob_sum=None):
+    """one chain's Rao-Blackwellised probability sums on the CPU through the device's code (``lhvi_gibbs_rb_disc_host``):
+    disc [num_samples, Nd], cont [num_samples, Nc] -> prob_sum [sum dstates], the sum over the samples [s_begin, s_end) of
+    p(x_n = k | x_d,-n, x_c), added to ``prob_sum`` when one is given (a run split over calls)"""
+    ex = gm.ex
+    Nd, Nc = ex.Nd, ex.Nc
+    num_samples = len(disc)
+    disc = np.ascontiguousarray(disc, dtype=np.int32).reshape(num_samples, Nd)
+    cont = np.ascontiguousarray(cont, dtype=np.float64).reshape(num_samples, Nc)
+    s_end = num_samples if s_end is None else int(s_end)
+    if Nd and disc.size and (disc.min() < 0 or (disc >= ex.dstates[None, :]).any()):
+        raise ValueError('disc holds a state outside its variable\'s range')
+    arrs = {n: np.ascontiguousarray(a) for n, a in gm.arrays().items()}
+    s = gm.struct(lambda n: C.c_void_p(arrs[n].ctypes.data if arrs[n].size else 0), 1, 0, num_samples, 0)
+    out = np.zeros(gm.n_states) if prob_sum is None else np.ascontiguousarray(prob_sum, dtype=np.float64).reshape(gm.n_states)
+    p = lambda a: a.ctypes.data if a.size else None                                     # noqa: E731
+    _abi.check(_abi.lib().lhvi_gibbs_rb_disc_host(s, int(s_begin), s_end, p(disc), p(cont), p(out)))
+    return out
 
 
 # ---- device ------------------------------------------------------------------------------------------------------------------
@@ -228,6 +254,23 @@ class _Chains:
             self.advance(min(iters, self.done + step))
         self.check()
         return self
+
+    def rb_disc(self, s_begin=0, s_end=None, prob_sum=None, lanes=None):
+        """prob_sum [chains, sum dstates] (device tensor, zeros when not given) += the conditional probabilities
+        p(x_n = k | x_d,-n, x_c) of the kept samples [s_begin, s_end) of every chain (``lhvi_gibbs_rb_disc``), one launch.
+        lanes: lanes per chain (default: the run's); the reduced tables live where the run's do.  Needs keep_samples."""
+        if self.disc is None:
+            raise RuntimeError('rb_disc needs the kept samples')
+        torch = _abi._torch()
+        if prob_sum is None:
+            prob_sum = torch.zeros(self.chains, max(self.gm.n_states, 1), dtype=torch.float64, device=self.x_d.device)
+        if prob_sum.shape != (self.chains, max(self.gm.n_states, 1)) or prob_sum.dtype != torch.float64 or not prob_sum.is_contiguous():
+            raise ValueError('prob_sum must be a contiguous float64 tensor [chains, sum dstates]')
+        p = lambda a: _abi.ptr(a) if a is not None and a.numel() else None              # noqa: E731
+        _abi.check(_abi.lib().lhvi_gibbs_rb_disc(self.s, self.chains, int(s_begin), self.num_samples if s_end is None else int(s_end),
+                                                 self.lanes if lanes is None else int(lanes), p(self.disc), p(self.cont),
+                                                 _abi.ptr(prob_sum), _abi.stream_ptr()))
+        return prob_sum
 
     def check(self):
         first = int(self.bad.item())
@@ -360,8 +403,11 @@ class GibbsHybridGaussian:
     ``GibbsHybridGaussian(factors=, Vd=, Vc=)``; variables with ``rv.value`` set are evidence, potentials are converted as in
     ``ExactHybridGaussian``.  After ``run()``: ``disc_marginals()``, ``moments()``, ``rhat()``, ``map`` / ``map_all`` /
     ``belief``, and with ``keep_samples`` ``disc_samples`` [chains, num_samples, Nd] / ``cont_samples`` and
-    ``fit_marginals(K)``: the mixtures of the continuous variables fitted to the kept samples on the device, and
-    ``sample_energies()`` / ``joint_map()``: the joint log potential of every kept sample and the best of them."""
+    ``fit_marginals(K)``: the mixtures of the continuous variables fitted to the kept samples on the device,
+    ``sample_energies()`` / ``joint_map()``: the joint log potential of every kept sample and the best of them, and the
+    Rao-Blackwellised estimates ``rb_marginals()`` / ``rb_disc_marginals()`` / ``rb_moments()`` and ``map`` / ``map_all`` /
+    ``belief`` with ``rao_blackwell=True``: the exact conditionals p(x_c | x_d) and p(x_n | x_d,-n, x_c) averaged over the kept
+    samples (docs/kernels_gibbs_rb.md)."""
 
     def __init__(self, g=None, factors=None, Vd=None, Vc=None):
         if g is None and (factors is None or Vd is None or Vc is None):
@@ -372,6 +418,7 @@ class GibbsHybridGaussian:
         self.model = GibbsModel(ex.model)
         self._run = None
         self.marginals, self._fits = None, {}
+        self.rb, self._rb_prob, self._rb_run, self._rb_maps = None, None, None, None
 
     def run(self, chains=1024, num_burnin=100, num_samples=100, disc_block_its=100, seed=0, keep_samples=False, lanes=None,
             its_per_launch=None, init_x_d=None):
@@ -382,6 +429,7 @@ class GibbsHybridGaussian:
         self.chains, self.num_samples = r.chains, r.num_samples
         self.marginals, self._fits = None, {}           # fits of an earlier run's samples
         self._energies = None
+        self.rb, self._rb_prob, self._rb_run, self._rb_maps = None, None, None, None
         self.counts = r.counts.cpu().numpy()
         self.sum1, self.sum2 = r.sum1.cpu().numpy(), r.sum2.cpu().numpy()
         self.disc_samples = r.disc.cpu().numpy() if keep_samples else None
@@ -464,6 +512,93 @@ class GibbsHybridGaussian:
             self._fits[int(K)] = self.marginals
         return self.marginals
 
+    # ---- Rao-Blackwellised estimates (docs/kernels_gibbs_rb.md) ---------------------------------------------------------------
+    def _need_samples(self, what):
+        r = self._need_run()
+        if r.disc is None:
+            raise RuntimeError('%s needs the kept samples: call run(keep_samples=True)' % what)
+        return r
+
+    def rb_marginals(self, chunk=None):
+        """The Rao-Blackwellised marginals of the continuous variables: ``p(x_i) ~ (1 / S) sum_s N(x_i; mu_i(x_d^s),
+        Sig_ii(x_d^s))`` over the kept discrete samples, with no K and no EM.  The distinct rows of the kept ``disc`` samples
+        (``torch.unique`` on the device tensor, lexicographic order) go through ``lhvi_exact_configs_at``; a component per distinct
+        row, its weight the row's share of the samples.  Returns the ``gmfit.ScalarMixtures`` [Nc, U] in ``Vc`` order, the shape
+        of ``ExactHybridGaussian.marginals()``, and keeps ``self.rb``: a namespace of rows [U, Nd], counts [U], inverse
+        [chains, num_samples], means / vars [U, Nc] (device tensors) and mixtures.  ``self.marginals`` (the fitted mixtures) is
+        left alone.  Needs ``run(keep_samples=True)``."""
+        from .gmfit import ScalarMixtures
+        r = self._need_samples('rb_marginals')
+        Nd, Nc = len(self.Vd), len(self.Vc)
+        if Nc == 0:
+            raise ValueError('the model has no continuous variable')
+        torch = _abi._torch()
+        total = r.chains * r.num_samples
+        if Nd:
+            rows, inverse, counts = torch.unique(r.disc.reshape(total, Nd), dim=0, return_inverse=True, return_counts=True)
+        else:
+            dev = r.disc.device
+            rows = torch.zeros(1, 0, dtype=torch.int32, device=dev)
+            inverse = torch.zeros(total, dtype=torch.int64, device=dev)
+            counts = torch.full((1,), total, dtype=torch.int64, device=dev)
+        rows = rows.to(torch.int32).contiguous()
+        _, means, vars_ = _exact.configs_at(self.model.ex, r.s.ex, rows, chunk=_exact.CHUNK if chunk is None else chunk)
+        U = int(rows.shape[0])
+        weights = counts.to(torch.float64) / float(total)
+        mixtures = ScalarMixtures(weights[None, :].expand(Nc, U), means.t(), vars_.t())
+        self.rb = types.SimpleNamespace(rows=rows, counts=counts, inverse=inverse.reshape(r.chains, r.num_samples), means=means,
+                                        vars=vars_, weights=weights, mixtures=mixtures)
+        self._rb_run = self._rb_maps = None
+        return mixtures
+
+    def _rb_probs(self):
+        """[chains, sum dstates] host array: per chain the mean over its kept samples of p(x_n = k | x_d,-n, x_c)
+        (``lhvi_gibbs_rb_disc``, one launch over all chains; computed once per run)"""
+        r = self._need_samples('rb_disc_marginals')
+        if self._rb_prob is None:
+            self._rb_prob = r.rb_disc().cpu().numpy()[:, :self.model.n_states] / float(r.num_samples)
+        return self._rb_prob
+
+    def rb_disc_marginals(self):
+        """``disc_marginals()`` with the state counts replaced by the conditional probabilities
+        ``p(x_n = k | x_d,-n, x_c)`` averaged over the kept samples: per discrete variable (marginal [states], standard error over
+        chains [states]).  Needs ``run(keep_samples=True)``."""
+        prob = self._rb_probs()
+        mean, se = prob.mean(axis=0), self._stderr(prob)
+        off = self.model.dstate_off
+        return [(mean[off[i]:off[i + 1]], se[off[i]:off[i + 1]]) for i in range(len(self.Vd))]
+
+    def rb_moments(self):
+        """namespace: mean [Nc] = E[x_c] and second_diag [Nc] = E[x_i^2] from the conditional means and variances of the kept
+        discrete samples (the per-chain means of ``rb.means[inverse]`` and of ``(rb.vars + rb.means^2)[inverse]``), and their
+        standard errors over chains mean_se, second_diag_se.  Cross moments stay with ``moments()``.  Needs
+        ``run(keep_samples=True)``; calls ``rb_marginals()`` when it has not run."""
+        self._need_samples('rb_moments')
+        if self.rb is None:
+            self.rb_marginals()
+        rb = self.rb
+        m1 = rb.means[rb.inverse].mean(dim=1).cpu().numpy()
+        m2 = (rb.vars + rb.means * rb.means)[rb.inverse].mean(dim=1).cpu().numpy()
+        return types.SimpleNamespace(mean=m1.mean(axis=0), second_diag=m2.mean(axis=0), mean_se=self._stderr(m1),
+                                     second_diag_se=self._stderr(m2))
+
+    def _rb_mixture_run(self):
+        """the Rao-Blackwellised mixtures behind the exact baseline's mixture kernels (lhvi_exact_mix_prepare / _mixture /
+        _map_polish)"""
+        self._need_samples('the Rao-Blackwellised mixture')
+        if self.rb is None:
+            self.rb_marginals()
+        if self._rb_run is None:
+            self._rb_run = _exact.mixture_run(self.rb.weights, self.rb.means, self.rb.vars)
+        return self._rb_run
+
+    def _rb_cont_maps(self):
+        if self._rb_maps is None:
+            bds = self._bds()
+            x, lf = self._rb_mixture_run().cont_map(bds[0], bds[1])
+            self._rb_maps = (x.cpu().numpy(), lf.cpu().numpy())
+        return self._rb_maps
+
     def sample_energies(self):
         """[chains, num_samples] device tensor: the joint log potential of every kept sample with the evidence in place
         (``log_const`` included, like ``ExactHybridGaussian.config_energies``), one launch over all of them.  Needs
@@ -498,14 +633,20 @@ class GibbsHybridGaussian:
     def _bds(self):
         return np.array([[rv.domain.values[0] for rv in self.Vc], [rv.domain.values[1] for rv in self.Vc]], dtype=np.float64)
 
-    def map(self, rv, num_gm_components_for_crv=1):
+    def map(self, rv, num_gm_components_for_crv=1, rao_blackwell=False):
         """observed: its value; discrete: the state of largest sampled marginal; continuous: the sample mean clipped to the
         domain (the one-component fit of ``HybridGaussianSampler.map``) or, with ``num_gm_components_for_crv`` = K > 1, the
         mode inside the domain of the K-component mixture fitted to the kept samples on the device (``fit_marginals(K)``
-        with its defaults, fitted once for all variables)"""
+        with its defaults, fitted once for all variables).  ``rao_blackwell``: the state of largest ``rb_disc_marginals()``; the
+        mode inside the domain of the variable's Rao-Blackwellised mixture, by the exact baseline's candidate selection and
+        Newton polish (K is not read)."""
         if rv.value is not None:
             return rv.value
         self._need_run()
+        if rao_blackwell:
+            if rv in self.Vd_idx:
+                return rv.domain.values[int(np.argmax(self.rb_disc_marginals()[self.Vd_idx[rv]][0]))]
+            return float(self._rb_cont_maps()[0][self.Vc_idx[rv]])
         if rv in self.Vd_idx:
             return rv.domain.values[int(np.argmax(self.disc_marginals()[self.Vd_idx[rv]][0]))]
         K = int(num_gm_components_for_crv)
@@ -515,16 +656,28 @@ class GibbsHybridGaussian:
         mean = float(self.moments().mean[self.Vc_idx[rv]])
         return float(min(max(mean, rv.domain.values[0]), rv.domain.values[1]))
 
-    def map_all(self, num_gm_components_for_crv=1):
+    def map_all(self, num_gm_components_for_crv=1, rao_blackwell=False):
         """``map`` of every variable of ``self.rvs`` as an array"""
-        return np.array([float(self.map(rv, num_gm_components_for_crv)) for rv in self.rvs])
+        return np.array([float(self.map(rv, num_gm_components_for_crv, rao_blackwell)) for rv in self.rvs])
 
-    def belief(self, x, rv):
+    def belief(self, x, rv, rao_blackwell=False):
         """sampled marginal probability of the state x of a discrete variable; for a continuous variable the density at x
-        (a number or an array) of its mixture of the last ``fit_marginals`` call"""
+        (a number or an array) of its mixture of the last ``fit_marginals`` call.  ``rao_blackwell``: the probability from
+        ``rb_disc_marginals()``; the density of the variable's Rao-Blackwellised mixture (``lhvi_exact_mixture``)."""
         if rv.value is not None:
             return 1 if x == rv.value else 0
         self._need_run()
+        if rao_blackwell:
+            if rv in self.Vd_idx:
+                vals = list(rv.domain.values)
+                return float(self.rb_disc_marginals()[self.Vd_idx[rv]][0][vals.index(x)]) if x in vals else 0.0
+            torch = _abi._torch()
+            run = self._rb_mixture_run()
+            xs = np.asarray(x, dtype=np.float64)
+            pts = torch.zeros(len(self.Vc), xs.size, dtype=torch.float64, device=run.table.device)
+            pts[self.Vc_idx[rv]] = _abi.to_dev(np.ascontiguousarray(xs.reshape(-1)))
+            out = np.exp(run.mixture(pts)[self.Vc_idx[rv], :, 0].cpu().numpy()).reshape(xs.shape)
+            return float(out) if xs.ndim == 0 else out
         if rv not in self.Vd_idx:
             if self.marginals is None:
                 raise NotImplementedError('belief of a continuous variable is the density of its fitted mixture: call '
