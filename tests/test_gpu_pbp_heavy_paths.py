@@ -6,7 +6,10 @@ the graph holds, so every access stays inside the graph's arrays.  The same list
 ``pbp_f2v_fast_kernel`` (which reads the same descriptor format), through the heavy kernel's direct form
 (LHVI_PBP_NO_GRID) and through the heavy kernel without work tickets.
 
-Tolerances (those of the heavy tests in test_gpu_pbp.py): 1e-11 against the fast kernel (another order of the sums when a
+Every list's messages are also held to the longdouble twin of tests/pbp_f2v_models.py, called with the overrides that match the
+edit, within that module's derived bound (``_hold_to_twin``).
+
+Tolerances between the device variants (those of the heavy tests in test_gpu_pbp.py): 1e-11 against the fast kernel (another order of the sums when a
 short round is split across lane groups, another unroll), 1e-12 for the grid recurrence against the direct form, and
 bit for bit for ticket against static striding (the same code per edge either way).
 
@@ -15,6 +18,8 @@ the short lists below exercise the cursor's static form and its clamp; the ticke
 counter, ``min(next, limit - 1)``) runs in ``test_ticketed_list_matches_static_striding`` on a list long enough."""
 import numpy as np
 import pytest
+
+import pbp_f2v_models as fm
 
 pytestmark = pytest.mark.gpu
 
@@ -84,6 +89,44 @@ def _run(api, bp, rows, family, extra=0, ticket=True, take=None):
     return out.cpu().numpy()[rows[:take, 0]], tick.cpu().numpy()
 
 
+class _HostState:
+    """the solver's particles, old particles, v -> f messages and counts on the host: what ``pbp_f2v_models.f2v_twin`` reads"""
+
+    def __init__(self, bp):
+        self.particles, self.old_particles = bp.particles.cpu().numpy(), bp.old_particles.cpu().numpy()
+        self.v2f, self.counts = bp.v2f.cpu().numpy(), bp.np_host
+
+
+def _hold_to_twin(bp, rows, heavy):
+    """the heavy kernel's messages of the edited rows against the longdouble twin called with the overrides that match the edit
+    (partner count, target count, grid size, partner observed at the descriptor's value): regular points within
+    ``pbp_f2v_models.f2v_bound`` -- the recurrence's for the grid points of an edge that may take it, the direct one elsewhere --
+    and dead points at the floor.  (On the domain [-40, 40] some points lie between the two classes: those are counted, not held.)"""
+    if getattr(bp, '_host_state', None) is None:
+        bp._host_state = _HostState(bp)
+    st, fl = bp._host_state, bp.flat
+    pval = rows[:, W_PVAL:W_PVAL + 2].copy().view(np.float64)[:, 0]
+    worst, between, held = 0.0, 0, 0
+    for row, value, out in zip(rows, pval, heavy):
+        e, nj, npart, T, grid = (int(row[w]) for w in (0, W_NJ, W_NP, W_T, W_GRID))
+        tw = fm.f2v_twin(fl, st, e, nj=nj, np_=npart, T=T, partner_value=None if np.isnan(value) else value)
+        L = tw.L.astype(np.float64)
+        regular = (L >= fm.REGULAR_MIN_L) & (tw.top <= fm.REGULAR_MAX_EXPONENT)
+        dead = tw.top <= fm.DEAD_MAX_EXPONENT
+        bound = fm.f2v_bound(tw.M, tw.n_terms, tw.L, 'direct')
+        if grid == 1 and nj >= GRID_MIN_NJ and 1 <= T <= 128:
+            g = fm.grid_deviation(fl, fl.var_dom[fl.edge_var[e]])
+            bound[npart:] = fm.f2v_bound(tw.M[npart:].max(), tw.n_terms, tw.L[npart:], 'recurrence', t=np.arange(T), grid_dev=g)
+        got = np.concatenate([out[:npart], out[N:N + T]])
+        ratio = np.abs(got - L)[regular] / bound[regular]
+        worst = max(worst, float(ratio.max()) if ratio.size else 0.0)
+        assert (ratio <= 1.0).all(), (e, float(ratio.max()))
+        assert (got[dead] == fm.FLOOR).all(), (e, got[dead])
+        between, held = between + int((~regular & ~dead).sum()), held + int(regular.sum() + dead.sum())
+    print('heavy vs longdouble twin: worst |d| / bound = %.3f on %d points (%d between the classes)' % (worst, held, between))
+    assert held > between
+
+
 def _check(api, bp, rows, expect_fallback=None):
     nj, npart, T, grid = (rows[:, w] for w in (W_NJ, W_NP, W_T, W_GRID))
     S = bp.f2v.shape[1]
@@ -91,6 +134,7 @@ def _check(api, bp, rows, expect_fallback=None):
     written = (col < npart[:, None]) | ((col >= N) & (col < N + T[:, None]))
     heavy, tick = _run(api, bp, rows, api.PBP_F2V_HEAVY)
     assert np.isfinite(heavy).all() and (heavy[~written] == 0).all()          # nothing outside the edge's own points
+    _hold_to_twin(bp, rows, heavy)                                            # ... and a host value for every one of them
     # ticket words 8 / 9: edges through the recurrence / edges the range guard sent to the direct form
     eligible = (grid == 1) & (nj >= GRID_MIN_NJ) & (T <= 128)
     assert int(tick[COUNTERS]) + int(tick[COUNTERS + 1]) == int(eligible.sum())
