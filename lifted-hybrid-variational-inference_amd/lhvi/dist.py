@@ -58,7 +58,7 @@ class SingleRunner:
 
     def heavy_stats(self):
         """(edges, joint terms) of the continuous x continuous kernel's work list"""
-        return int(getattr(self.bp, 'n_heavy_class', 0) or self.bp.n_heavy), self.bp.heavy_terms
+        return int(self.bp.n_heavy_class or self.bp.n_heavy), self.bp.heavy_terms
 
     def heavy_grid_terms(self):
         """joint terms at the integral points of the edges the heavy kernel serves by the grid recurrence"""
@@ -442,32 +442,7 @@ class ShardedRunner:
 
     def _edge_part(self, s, part):
         """restrict the f2v work lists of `s` to the interior prefix (part 0) or the boundary suffix (part 1)"""
-        bp, pc = self.bp, self.bp.part_counts
-
-        def cut(total, first):
-            return (0, first) if part == 0 else (first, total - first)
-        D = _abi.PBP_DESC_BYTES
-        off, cnt = cut(bp.n_heavy, pc['heavy'])
-        s.heavy_desc, s.n_heavy = (bp.heavy_desc.data_ptr() + off * D if cnt else None), cnt
-        for name in ('small16', 'small32'):              # (heavy-class edges with few particles: four / two per wavefront)
-            off, cnt = cut(int(getattr(bp, 'n_' + name, 0)), pc.get(name, 0))
-            setattr(s, name + '_desc', (getattr(bp, name + '_desc').data_ptr() + off * D) if cnt else None)
-            setattr(s, 'n_' + name, cnt)
-        off, cnt = cut(bp.n_light, pc['light'])
-        s.light_desc, s.n_light = (bp.light_desc.data_ptr() + off * D if cnt else None), cnt
-        off, cnt = cut(int(getattr(bp, 'n_pair', 0)), pc.get('pair', 0))
-        s.pair_desc, s.n_pair = (bp.pair_desc.data_ptr() + off * D if cnt else None), cnt
-        off, cnt = cut(int(getattr(bp, 'n_cq', 0)), pc.get('cq', 0))
-        s.cq_desc, s.n_cq = (bp.cq_desc.data_ptr() + off * 2 * D if cnt else None), cnt
-        off, cnt = cut(int(bp.fast_edges.numel()), pc['fast'])
-        if cnt:
-            s.fast_edges, s.fast_desc = bp.fast_edges.data_ptr() + 4 * off, bp.fast_desc.data_ptr() + off * D
-        s.n_fast = cnt                       # 0 with a non-null list pointer = nothing to do
-        off, cnt = cut(int(bp.generic_edges.numel()), pc['generic'])
-        if cnt:
-            s.generic_edges = bp.generic_edges.data_ptr() + 4 * off
-        s.n_generic = cnt
-        return s
+        return self.bp.f2v_lists.install_part(s, part)
 
     def init(self):
         bp = self.bp
@@ -1010,10 +985,7 @@ class OwnerRunner:
         # the first one hides a good part of the exchange.  With many ranks nearly every factor of an expander is cut: the first
         # launch then hides next to nothing and costs a second ramp-up and tail of the persistent kernels (0.35 of 1.75 ms at 8
         # ranks) -- below `min_interior` of the f -> v work ONE launch after the exchange serves both lists.
-        pc = bp.part_counts
-        total = bp.n_heavy + bp.n_pair + int(bp.generic_edges.numel()) + int(bp.fast_edges.numel()) + bp.n_small16 + bp.n_small32 + bp.n_cq
-        inner = pc['heavy'] + pc['pair'] + pc['generic'] + pc['fast'] + pc['small16'] + pc['small32'] + pc['cq']
-        self.interior_fraction = inner / float(max(total, 1))
+        self.interior_fraction = bp.f2v_lists.n_interior / float(max(bp.f2v_lists.n_items, 1))
         self.split_f2v = self.interior_fraction >= self.min_interior
 
     min_interior = 0.25         # least share of the f -> v work lists that must need no ghost for the two-launch schedule

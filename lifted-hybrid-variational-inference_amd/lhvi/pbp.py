@@ -103,142 +103,34 @@ class _ParticleSweep:
         self._views, self._batched = {}, {}
         self._draws = 0
         self._static_rows = False           # the rows no listed draw writes are filled once, by the first draw (_generate_sample)
-        self.cq_desc, self.n_cq = None, 0
-        self.fast_edges = self.generic_edges = self._fast_list = self._generic_list = torch.zeros(1, dtype=torch.int32, device=dg.device)
         dev_lists = _abi.upload(plan.host)                      # the per-variable lists go to the device in one copy
         for name in ('np_dev', 'resample_vars', '_static_idx', 'prop_desc'):
             setattr(self, name, dev_lists[name])
         self.n_prop_desc, self.n_prop_hub, self.prop_hub = plan.n_prop_desc, plan.n_prop_hub, dev_lists.get('prop_hub')
         self.v2f_lists = plan.v2f.on(dev_lists, 'v2f_') if plan.v2f is not None else None
         self._fused = plan.fused.on(dev_lists) if plan.fused is not None else None
-        # static work lists of the f -> v half sweep (which kernel serves which edge)
-        pad = torch.zeros(1, dtype=torch.int32, device=dg.device)       # keeps the pointers non-null when a list is empty
-        self.cq_edges = pad[:0]
-        self.part_counts = {'heavy': 0, 'light': 0, 'fast': 0, 'generic': 0, 'cq': 0, 'pair': 0, 'small16': 0, 'small32': 0}
-        self.generic_pts_log2 = 6
-        self.fast_desc = self.heavy_desc = self.light_desc = self.pair_desc = self.small16_desc = self.small32_desc = None
-        self.n_heavy = self.n_light = self.n_pair = self.n_small16 = self.n_small32 = self.n_heavy_class = 0
-        self.cq_terms = self.heavy_terms = self.heavy_grid_terms = 0
+        # static work lists of the f -> v half sweep: which kernel serves which edge (lhvi/pbp_plan.py); none until they are built
         self._has_f_side = 'f' in sides
-        if not self._has_f_side:
-            self.fast_edges = self.generic_edges = pad[:0]
-            self._fast_list = self._generic_list = pad
-            return
-        cls = torch.zeros(max(flat.E, 1), dtype=torch.uint8, device=dg.device)
-        _abi.check(_abi.lib().lhvi_pbp_classify(dg.g, dg.p, self._struct(), _abi.ptr(cls), _abi.stream_ptr()))
-        cls = cls[:flat.E]
-        if edge_skip is not None:
-            cls = torch.where(_abi.to_dev(np.ascontiguousarray(edge_skip, dtype=bool)), torch.zeros_like(cls), cls)
-        self.fast_edges = torch.nonzero((cls == 1) | (cls == 2)).flatten().to(torch.int32)
-        self.generic_edges = torch.nonzero(cls == 3).flatten().to(torch.int32)
-        self.cq_edges = torch.nonzero(cls == 4).flatten().to(torch.int32)
-        key_dev = None
-        if edge_key is not None:
-            key_dev = _abi.to_dev(np.ascontiguousarray(edge_key, dtype=np.int32))
-            self.fast_edges = self.fast_edges[torch.sort(key_dev[self.fast_edges.long()], stable=True).indices].contiguous()
-            self.generic_edges = self.generic_edges[torch.sort(key_dev[self.generic_edges.long()], stable=True).indices].contiguous()
-            self.cq_edges = self.cq_edges[torch.sort(key_dev[self.cq_edges.long()], stable=True).indices].contiguous()
+        self.f2v_lists = pbp_plan.F2vLists.empty(torch.zeros(1, dtype=torch.int32, device=dg.device))
+        if self._has_f_side:
+            cls = torch.zeros(max(flat.E, 1), dtype=torch.uint8, device=dg.device)
+            _abi.check(_abi.lib().lhvi_pbp_classify(dg.g, dg.p, self._struct(), _abi.ptr(cls), _abi.stream_ptr()))
+            self.f2v_lists = pbp_plan.f_side_plan(
+                cls[:flat.E], flat, self.np_host, describe=self._describe,
+                describe_cq=lambda edges: self._describe(edges, 'lhvi_pbp_describe_cq', 2 * _abi.PBP_DESC_BYTES),
+                skip=None if edge_skip is None else _abi.to_dev(np.ascontiguousarray(edge_skip, dtype=bool)),
+                key=None if edge_key is None else _abi.to_dev(np.ascontiguousarray(edge_key, dtype=np.int32)),
+                paired_light=self.paired_light, small_f2v=self.small_f2v, long_grid_min_edges=self.long_grid_min_edges)
+        for name, value in self.f2v_lists.named().items():      # (fast_edges, heavy_desc, n_heavy, part_counts, ...)
+            setattr(self, name, value)
 
-        def first_part(edges):      # entries of an (ordered) edge list with key 0
-            return int((key_dev[edges.long()] == 0).sum().item()) if key_dev is not None and edges.numel() else 0
-        self.part_counts = {'heavy': 0, 'light': 0, 'fast': 0, 'generic': first_part(self.generic_edges),
-                            'cq': first_part(self.cq_edges), 'pair': 0, 'small16': 0, 'small32': 0}
-        self._fast_list = self.fast_edges if self.fast_edges.numel() else pad
-        self._generic_list = self.generic_edges if self.generic_edges.numel() else pad
-        # lanes per generic edge: smallest power of two covering its output points (particles + integral points)
-        ge = self.generic_edges.cpu().numpy()
-        tv = flat.edge_var[ge]
-        pts = self.np_host[tv] + np.where(flat.var_cont[tv], flat.var_nstates[tv], 0) if ge.size else np.zeros(0, dtype=int)
-        self.generic_pts_log2 = int(min(6, max(0, int(np.ceil(np.log2(max(int(pts.max()), 1)))) if ge.size else 6)))
-        ncq = int(self.cq_edges.numel())
-        if ncq:
-            # two-partner edges of conditionally quadratic factors (include/lhvi.h, lhvi_pbp_describe_cq)
-            cqd = torch.empty(ncq * 2 * _abi.PBP_DESC_BYTES, dtype=torch.uint8, device=dg.device)
-            _abi.check(_abi.lib().lhvi_pbp_describe_cq(dg.g, dg.p, self._struct(), _abi.ptr(self.cq_edges), ncq,
-                                                       _abi.ptr(cqd), _abi.stream_ptr()))
-            self.cq_desc, self.n_cq = cqd, ncq
-            cw = cqd.view(torch.int32).view(ncq, 2 * _abi.PBP_DESC_BYTES // 4).to(torch.int64)
-            # (output point, partner particle, state) terms: type 1: (np + T) * ny * S;  type 2: S * nx * ny
-            self.cq_terms = int(torch.where(cw[:, 2] == 1, (cw[:, 4] + cw[:, 5]) * cw[:, 9] * cw[:, 3],
-                                            cw[:, 3] * cw[:, 12] * cw[:, 9]).sum().item())
-        nf = int(self.fast_edges.numel())
-        if nf:
-            desc = torch.empty(nf * _abi.PBP_DESC_BYTES, dtype=torch.uint8, device=dg.device)
-            _abi.check(_abi.lib().lhvi_pbp_describe(dg.g, dg.p, self._struct(), _abi.ptr(self.fast_edges), nf,
-                                                    _abi.ptr(desc), _abi.stream_ptr()))
-            # split off the edges the specialised kernels serve (lhvi/pbp_plan.py, f2v_split)
-            heavy, small16, small32, light, rest, self.heavy_terms, self.heavy_grid_terms = pbp_plan.f2v_split(
-                desc.view(torch.int32).view(nf, _abi.PBP_DESC_BYTES // 4), self.small_f2v, self.long_grid_min_edges)
-            small = small16 | small32
-            rows = desc.view(nf, _abi.PBP_DESC_BYTES)
-            self.small16_desc, self.small32_desc = rows[small16].contiguous(), rows[small32].contiguous()
-            self.n_small16, self.n_small32 = int(self.small16_desc.shape[0]), int(self.small32_desc.shape[0])
-            self.n_heavy_class = int(heavy.sum().item())
-            self.heavy_desc = rows[heavy & ~small].contiguous()
-            self.n_heavy = int(self.heavy_desc.shape[0])
-            self.light_desc = rows[light].contiguous()
-            self.n_light = int(self.light_desc.shape[0])
-            self.fast_desc = rows[rest].contiguous()
-            all_fast = self.fast_edges
-            self.fast_edges = all_fast[rest].contiguous()
-            self._fast_list = self.fast_edges if self.fast_edges.numel() else pad
-            # (sharded runs: every list is ordered interior part first -- all_fast is -- and split at these counts)
-            self.part_counts.update(heavy=first_part(all_fast[heavy & ~small]), light=first_part(all_fast[light]),
-                                    fast=first_part(self.fast_edges), small16=first_part(all_fast[small16]),
-                                    small32=first_part(all_fast[small32]))
-            self._build_pairs(key_dev)
-
-    def _build_pairs(self, key_dev):
-        """``lhvi_pbp_t.pair_desc``: one record per HybridQuadratic(1 discrete, 1 continuous) factor from the per-edge light
-        descriptors (words 0 e, 1 target, 2 partner, 3 partner's canonical edge, 7 nj, 8 np, 9 T, 10 grid base, 12-13 partner
-        value, 14 type, 16-27 coefficients), on the device.  A type-1 entry (continuous target) is joined with the type-2 entry
-        (discrete target) of the same factor when there is one; what is left of either type becomes a one-sided record."""
+    def _describe(self, edges, entry='lhvi_pbp_describe', nbytes=_abi.PBP_DESC_BYTES):
+        """the descriptors of `edges` (int32 device tensor), `nbytes` each (include/lhvi.h, lhvi_pbp_describe / lhvi_pbp_describe_cq)"""
         torch = _abi.require_gpu()
-        if not self.paired_light or self.light_desc is None or self.n_light == 0:
-            return
-        dev = self.light_desc.device
-        w = self.light_desc.view(torch.int32).view(-1, 32).long()
-        dd = self.light_desc.view(torch.float64).view(-1, 16)
-        i1, i2 = torch.nonzero(w[:, 14] == 1).flatten(), torch.nonzero(w[:, 14] == 2).flatten()
-        w1, w2, d1, d2 = w[i1], w[i2], dd[i1], dd[i2]
-        lookup = torch.full((max(self.flat.E, 1),), -1, dtype=torch.int64, device=dev)
-        lookup[w2[:, 0]] = torch.arange(i2.numel(), device=dev)
-        j = torch.where(torch.isnan(d1[:, 6]), lookup[w1[:, 3]], torch.full_like(w1[:, 3], -1))      # partner hidden: its own entry
-        taken = torch.zeros(i2.numel(), dtype=torch.bool, device=dev)
-        taken[j[j >= 0]] = True
-        rest = torch.nonzero(~taken).flatten()
-        n1, n2 = int(i1.numel()), int(rest.numel())
-        out = torch.zeros(n1 + n2, 128, dtype=torch.uint8, device=dev)
-        ow, od = out.view(torch.int32).view(-1, 32), out.view(torch.float64).view(-1, 16)
-        nan = float('nan')
-        if n1:
-            jj = j.clamp_min(0)
-            has = j >= 0
-            ow[:n1, 0] = w1[:, 0].int()
-            ow[:n1, 1] = torch.where(has, w2[jj, 0], torch.full_like(jj, -1)).int() if i2.numel() else -1
-            ow[:n1, 2], ow[:n1, 3] = w1[:, 1].int(), w1[:, 2].int()
-            ow[:n1, 4], ow[:n1, 5], ow[:n1, 6], ow[:n1, 7] = w1[:, 8].int(), w1[:, 9].int(), w1[:, 10].int(), w1[:, 7].int()
-            od[:n1, 4], od[:n1, 5] = nan, d1[:, 6]
-            od[:n1, 6:12] = d1[:, 8:14]
-            ow[:n1, 24] = w1[:, 3].int()
-            ow[:n1, 25] = (torch.where(has, w2[jj, 3], torch.zeros_like(jj)).int() if i2.numel() else 0)
-        if n2:
-            r2, rd = w2[rest], d2[rest]
-            ow[n1:, 0], ow[n1:, 1] = -1, r2[:, 0].int()
-            ow[n1:, 2], ow[n1:, 3] = r2[:, 2].int(), r2[:, 1].int()
-            ow[n1:, 4], ow[n1:, 7] = r2[:, 7].int(), r2[:, 8].int()
-            od[n1:, 4], od[n1:, 5] = rd[:, 6], nan
-            od[n1:, 6:12] = rd[:, 8:14]
-            ow[n1:, 25] = r2[:, 3].int()
-        first = 0
-        if key_dev is not None and n1 + n2:      # sharded runs: records of factors that touch no boundary variable first
-            # (a record's key: that of its edges -- both belong to one factor, and a factor's edges share their key)
-            edge = torch.where(ow[:, 0] >= 0, ow[:, 0], ow[:, 1]).long()
-            order = torch.sort(key_dev[edge], stable=True).indices
-            out = out[order].contiguous()
-            first = int((key_dev[edge] == 0).sum().item())
-        self.pair_desc, self.n_pair = out, n1 + n2
-        self.part_counts['pair'] = first
+        k = int(edges.numel())
+        desc = torch.empty(k * nbytes, dtype=torch.uint8, device=edges.device)
+        _abi.check(getattr(_abi.lib(), entry)(self.dg.g, self.dg.p, self._struct(), _abi.ptr(edges), k, _abi.ptr(desc), _abi.stream_ptr()))
+        return desc
 
     def _plan_options(self):
         """what the variable-side plan depends on besides the graph: the class attributes and the tuning variables, each read here"""
@@ -257,19 +149,7 @@ class _ParticleSweep:
         s.var_threshold, s.max_log_value = float(self.var_threshold), float(self.max_log_value)
         s.particles, s.old_particles = _abi.ptr(self.particles), _abi.ptr(self.old_particles)
         s.np, s.uniq, s.q = _abi.ptr(self.np_dev), _abi.ptr(self.uniq), _abi.ptr(self.q_dev)
-        s.fast_edges, s.n_fast = _abi.ptr(self._fast_list), int(self.fast_edges.numel())
-        s.generic_edges, s.n_generic = _abi.ptr(self._generic_list), int(self.generic_edges.numel())
-        s.generic_pts_log2 = int(getattr(self, 'generic_pts_log2', 6))
-        s.fast_desc = _abi.ptr(getattr(self, 'fast_desc', None))
-        s.heavy_desc, s.n_heavy = _abi.ptr(getattr(self, 'heavy_desc', None)), int(getattr(self, 'n_heavy', 0))
-        s.light_desc, s.n_light = _abi.ptr(getattr(self, 'light_desc', None)), int(getattr(self, 'n_light', 0))
-        if getattr(self, 'n_small16', 0):
-            s.small16_desc, s.n_small16 = _abi.ptr(self.small16_desc), int(self.n_small16)
-        if getattr(self, 'n_small32', 0):
-            s.small32_desc, s.n_small32 = _abi.ptr(self.small32_desc), int(self.n_small32)
-        if self.paired_light and getattr(self, 'pair_desc', None) is not None:
-            s.pair_desc, s.n_pair = _abi.ptr(self.pair_desc), int(self.n_pair)
-        s.cq_desc, s.n_cq = _abi.ptr(getattr(self, 'cq_desc', None)), int(getattr(self, 'n_cq', 0))
+        self.f2v_lists.install(s)
         if getattr(self, 'v2f_lists', None) is not None:
             self.v2f_lists.install(s)
         s.f2v_ticket = _abi.ptr(self.f2v_ticket) if self.dynamic_f2v else None
@@ -400,7 +280,7 @@ class _ParticleSweep:
         """the f -> v half sweep (`lhvi_pbp_f2v`) by the schedule of _f2v_schedule.  `f2v_events`: (start, end) events recorded
         on this stream around the long kernels (heavy and small lists); the other families then run in a call of their own."""
         l, g, p, st = _abi.lib(), self.dg.g, self.dg.p, _abi.stream_ptr()
-        if not getattr(self, '_has_f_side', True):
+        if not self._has_f_side:
             raise _abi.LhviError('this state was set up for the v -> f half only (sides="v")')
         args = (_abi.ptr(self.v2f), _abi.ptr(self.f2v))
         calls = F2V_SCHEDULES[self._f2v_schedule(bool(f2v_events))]

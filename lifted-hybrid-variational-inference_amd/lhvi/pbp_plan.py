@@ -1,6 +1,9 @@
-"""Which variable (and which described edge) of a particle sweep goes to which kernel, and the records those kernels read:
-pure host functions of the graph arrays -- no device, no environment, same arguments give the same bytes.  The record layouts are
-those of ``include/lhvi.h`` (``lhvi_pbp_t``); ``lhvi/pbp.py::_setup`` uploads what ``var_side_plan`` returns in one copy."""
+"""Which variable and which edge of a particle sweep goes to which kernel, and the records those kernels read: pure functions of
+their arguments -- no environment, same arguments give the same bytes.  The record layouts are those of ``include/lhvi.h``
+(``lhvi_pbp_t``).  The variable side (``var_side_plan``) works on the graph's host arrays; ``lhvi/pbp.py::_setup`` uploads what it
+returns in one copy.  The factor side (``f_side_plan``, ``f2v_split``, ``pair_records``) works on tensors, on the device they
+live on -- the device in a sweep, the CPU in a test -- and takes the two device calls that describe edges as callables; its lists
+travel as one record (``F2vLists``), as the variable side's do (``V2fLists``, ``FusedLists``)."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -229,3 +232,182 @@ def f2v_split(words, small_f2v, long_grid_min_edges):
     heavy_grid_terms = int((hw[:, 9] * hw[:, 7])[on_grid].sum().item())
     light = ~heavy & (words[:, 14] != 0)          # word 14: set by lhvi_pbp_describe for the light kernel's edges
     return F2vSplit(heavy, small16, small32, light, ~heavy & ~light, heavy_terms, heavy_grid_terms)
+
+
+def pair_records(light_words, E, key=None):
+    """``lhvi_pbp_t.pair_desc``: one record per HybridQuadratic(1 discrete, 1 continuous) factor from the per-edge light
+    descriptors (`light_words`: [k, 128] uint8, or its int32 / float64 view; words 0 e, 1 target, 2 partner, 3 partner's canonical
+    edge, 7 nj, 8 np, 9 T, 10 grid base, 12-13 partner value, 14 type, 16-27 coefficients), on the descriptors' device.  A type-1
+    entry (continuous target) is joined with the type-2 entry (discrete target) of the same factor when there is one; what is left
+    of either type becomes a one-sided record.  `E`: the graph's edges; `key`: 0 / 1 per edge, or None.  Returns the records
+    ([n1 + n2, 128] uint8: type-1 rows, then the leftover type-2 rows; stable-sorted by `key`) and the number of those with key 0."""
+    import torch
+    light = light_words.view(torch.uint8).view(-1, 128)
+    dev = light.device
+    w = light.view(torch.int32).view(-1, 32).long()
+    dd = light.view(torch.float64).view(-1, 16)
+    i1, i2 = torch.nonzero(w[:, 14] == 1).flatten(), torch.nonzero(w[:, 14] == 2).flatten()
+    w1, w2, d1, d2 = w[i1], w[i2], dd[i1], dd[i2]
+    lookup = torch.full((max(E, 1),), -1, dtype=torch.int64, device=dev)
+    lookup[w2[:, 0]] = torch.arange(i2.numel(), device=dev)
+    j = torch.where(torch.isnan(d1[:, 6]), lookup[w1[:, 3]], torch.full_like(w1[:, 3], -1))      # partner hidden: its own entry
+    taken = torch.zeros(i2.numel(), dtype=torch.bool, device=dev)
+    taken[j[j >= 0]] = True
+    rest = torch.nonzero(~taken).flatten()
+    n1, n2 = int(i1.numel()), int(rest.numel())
+    out = torch.zeros(n1 + n2, 128, dtype=torch.uint8, device=dev)
+    ow, od = out.view(torch.int32).view(-1, 32), out.view(torch.float64).view(-1, 16)
+    nan = float('nan')
+    if n1:
+        jj = j.clamp_min(0)
+        has = j >= 0
+        ow[:n1, 0] = w1[:, 0].int()
+        ow[:n1, 1] = torch.where(has, w2[jj, 0], torch.full_like(jj, -1)).int() if i2.numel() else -1
+        ow[:n1, 2], ow[:n1, 3] = w1[:, 1].int(), w1[:, 2].int()
+        ow[:n1, 4], ow[:n1, 5], ow[:n1, 6], ow[:n1, 7] = w1[:, 8].int(), w1[:, 9].int(), w1[:, 10].int(), w1[:, 7].int()
+        od[:n1, 4], od[:n1, 5] = nan, d1[:, 6]
+        od[:n1, 6:12] = d1[:, 8:14]
+        ow[:n1, 24] = w1[:, 3].int()
+        ow[:n1, 25] = (torch.where(has, w2[jj, 3], torch.zeros_like(jj)).int() if i2.numel() else 0)
+    if n2:
+        r2, rd = w2[rest], d2[rest]
+        ow[n1:, 0], ow[n1:, 1] = -1, r2[:, 0].int()
+        ow[n1:, 2], ow[n1:, 3] = r2[:, 2].int(), r2[:, 1].int()
+        ow[n1:, 4], ow[n1:, 7] = r2[:, 7].int(), r2[:, 8].int()
+        od[n1:, 4], od[n1:, 5] = rd[:, 6], nan
+        od[n1:, 6:12] = rd[:, 8:14]
+        ow[n1:, 25] = r2[:, 3].int()
+    first = 0
+    if key is not None and n1 + n2:      # sharded runs: records of factors that touch no boundary variable first
+        # (a record's key: that of its edges -- both belong to one factor, and a factor's edges share their key)
+        edge = torch.where(ow[:, 0] >= 0, ow[:, 0], ow[:, 1]).long()
+        order = torch.sort(key[edge], stable=True).indices
+        out = out[order].contiguous()
+        first = int((key[edge] == 0).sum().item())
+    return out, first
+
+
+F2V_LISTS = ('heavy', 'small16', 'small32', 'light', 'pair', 'fast', 'generic', 'cq')
+_F2V_DESC_BYTES = {'heavy': 128, 'small16': 128, 'small32': 128, 'light': 128, 'pair': 128, 'cq': 256}      # per record (include/lhvi.h)
+
+
+class F2vLists(namedtuple('F2vLists', 'fast_edges fast_desc generic_edges cq_edges cq_desc n_cq heavy_desc n_heavy small16_desc n_small16 '
+                                      'small32_desc n_small32 light_desc n_light pair_desc n_pair part_counts generic_pts_log2 '
+                                      'n_heavy_class heavy_terms heavy_grid_terms cq_terms pad')):
+    """the f -> v half's eight lists (F2V_LISTS): descriptors with their counts (``lhvi_pbp_t.heavy_desc / small16_desc /
+    small32_desc / light_desc / pair_desc / cq_desc``; None without any, `pair_desc` also when the light edges are served one by one),
+    the edge lists ``fast_edges`` (with ``fast_desc``) and ``generic_edges``, and `cq_edges`, the edges `cq_desc` describes.
+    `part_counts`: per list the length of its interior prefix (key 0).  `pad`: one word for the pointer of an empty edge list -- to
+    ``lhvi_pbp_f2v`` a null edge list is every edge of the graph."""
+
+    @classmethod
+    def empty(cls, pad):
+        """no list at all (what a state of the v -> f half alone holds); `pad`: one int32 zero on the state's device"""
+        fields = dict.fromkeys(cls._fields, 0)
+        fields.update({name: None for name in cls._fields if name.endswith('_desc')})
+        fields.update(fast_edges=pad[:0], generic_edges=pad[:0], cq_edges=pad[:0], pad=pad, part_counts=dict.fromkeys(F2V_LISTS, 0),
+                      generic_pts_log2=6)
+        return cls(**fields)
+
+    n_fast = property(lambda self: int(self.fast_edges.numel()))
+    n_generic = property(lambda self: int(self.generic_edges.numel()))
+    # entries of the lists, and of their interior prefixes, without the light list's (OwnerRunner.interior_fraction)
+    n_items = property(lambda self: sum(getattr(self, 'n_' + name) for name in F2V_LISTS if name != 'light'))
+    n_interior = property(lambda self: sum(first for name, first in self.part_counts.items() if name != 'light'))
+
+    def named(self):
+        """the lists under the names a sweep object holds them by"""
+        named = dict(self._asdict(), _fast_list=self.fast_edges if self.n_fast else self.pad,
+                     _generic_list=self.generic_edges if self.n_generic else self.pad)
+        del named['pad']
+        return named
+
+    def install(self, s):
+        s.fast_edges, s.n_fast = _abi.ptr(self.fast_edges if self.n_fast else self.pad), self.n_fast
+        s.generic_edges, s.n_generic = _abi.ptr(self.generic_edges if self.n_generic else self.pad), self.n_generic
+        s.generic_pts_log2 = int(self.generic_pts_log2)
+        s.fast_desc = _abi.ptr(self.fast_desc)
+        s.heavy_desc, s.n_heavy = _abi.ptr(self.heavy_desc), int(self.n_heavy)
+        s.light_desc, s.n_light = _abi.ptr(self.light_desc), int(self.n_light)
+        if self.n_small16:
+            s.small16_desc, s.n_small16 = _abi.ptr(self.small16_desc), int(self.n_small16)
+        if self.n_small32:
+            s.small32_desc, s.n_small32 = _abi.ptr(self.small32_desc), int(self.n_small32)
+        if self.pair_desc is not None:
+            s.pair_desc, s.n_pair = _abi.ptr(self.pair_desc), int(self.n_pair)
+        s.cq_desc, s.n_cq = _abi.ptr(self.cq_desc), int(self.n_cq)
+
+    def install_part(self, s, part):
+        """restrict the lists of `s` (installed) to their interior prefix (part 0) or their boundary suffix (part 1)"""
+        def cut(name):
+            first = self.part_counts[name]
+            return (0, first) if part == 0 else (first, getattr(self, 'n_' + name) - first)
+        for name, stride in _F2V_DESC_BYTES.items():
+            off, cnt = cut(name)
+            setattr(s, name + '_desc', getattr(self, name + '_desc').data_ptr() + off * stride if cnt else None)
+            setattr(s, 'n_' + name, cnt)
+        off, cnt = cut('fast')
+        if cnt:
+            s.fast_edges, s.fast_desc = self.fast_edges.data_ptr() + 4 * off, self.fast_desc.data_ptr() + off * _abi.PBP_DESC_BYTES
+        s.n_fast = cnt                       # 0 with a non-null list pointer = nothing to do
+        off, cnt = cut('generic')
+        if cnt:
+            s.generic_edges = self.generic_edges.data_ptr() + 4 * off
+        s.n_generic = cnt
+        return s
+
+
+def f_side_plan(cls, flat, np_host, *, describe, describe_cq, key=None, skip=None, paired_light=True, small_f2v=True,
+                long_grid_min_edges=1 << 16):
+    """The static work lists of the f -> v half sweep: which kernel serves which edge.
+    `cls`: ``lhvi_pbp_classify``'s class per edge ([E] uint8 tensor; the lists live on its device).  `describe`, `describe_cq`:
+    edges (int32 tensor) -> their descriptors (uint8 tensor; ``lhvi_pbp_describe``: 128 bytes per edge, ``lhvi_pbp_describe_cq``: 256).
+    `key` (sharded runs): 0 / 1 per edge (tensor); every list is ordered key-0 edges first and `part_counts` gives the length of that
+    first part.  `skip` (owner-computes shards): boolean per edge (tensor); a marked edge enters no list."""
+    import torch
+    if skip is not None:
+        cls = torch.where(skip, torch.zeros_like(cls), cls)
+    L = F2vLists.empty(torch.zeros(1, dtype=torch.int32, device=cls.device))._asdict()
+    fast = torch.nonzero((cls == 1) | (cls == 2)).flatten().to(torch.int32)
+    generic = torch.nonzero(cls == 3).flatten().to(torch.int32)
+    cq = torch.nonzero(cls == 4).flatten().to(torch.int32)
+    if key is not None:
+        fast, generic, cq = (e[torch.sort(key[e.long()], stable=True).indices].contiguous() for e in (fast, generic, cq))
+
+    def first_part(edges):      # entries of an (ordered) edge list with key 0
+        return int((key[edges.long()] == 0).sum().item()) if key is not None and edges.numel() else 0
+    first = L['part_counts']
+    first.update(generic=first_part(generic), cq=first_part(cq))
+    L.update(fast_edges=fast, generic_edges=generic, cq_edges=cq)
+    # lanes per generic edge: smallest power of two covering its output points (particles + integral points)
+    ge = generic.cpu().numpy()
+    tv = flat.edge_var[ge]
+    pts = np_host[tv] + np.where(flat.var_cont[tv], flat.var_nstates[tv], 0) if ge.size else np.zeros(0, dtype=int)
+    L['generic_pts_log2'] = int(min(6, max(0, int(np.ceil(np.log2(max(int(pts.max()), 1)))) if ge.size else 6)))
+    ncq = int(cq.numel())
+    if ncq:
+        # two-partner edges of conditionally quadratic factors (include/lhvi.h, lhvi_pbp_describe_cq)
+        L['cq_desc'], L['n_cq'] = describe_cq(cq), ncq
+        cw = L['cq_desc'].view(torch.int32).view(ncq, 2 * _abi.PBP_DESC_BYTES // 4).to(torch.int64)
+        # (output point, partner particle, state) terms: type 1: (np + T) * ny * S;  type 2: S * nx * ny
+        L['cq_terms'] = int(torch.where(cw[:, 2] == 1, (cw[:, 4] + cw[:, 5]) * cw[:, 9] * cw[:, 3],
+                                        cw[:, 3] * cw[:, 12] * cw[:, 9]).sum().item())
+    nf = int(fast.numel())
+    if nf:
+        # split off the edges the specialised kernels serve (f2v_split)
+        rows = describe(fast).view(nf, _abi.PBP_DESC_BYTES)
+        sp = f2v_split(rows.view(torch.int32), small_f2v, long_grid_min_edges)
+        small = sp.small16 | sp.small32
+        L.update(heavy_terms=sp.heavy_terms, heavy_grid_terms=sp.heavy_grid_terms, n_heavy_class=int(sp.heavy.sum().item()))
+        # (sharded runs: every list is ordered interior part first -- `fast` is -- and split at these counts)
+        for name, mask in (('small16', sp.small16), ('small32', sp.small32), ('heavy', sp.heavy & ~small), ('light', sp.light)):
+            L[name + '_desc'] = rows[mask].contiguous()
+            L['n_' + name], first[name] = int(L[name + '_desc'].shape[0]), first_part(fast[mask])
+        L['fast_desc'], L['fast_edges'] = rows[sp.rest].contiguous(), fast[sp.rest].contiguous()
+        first['fast'] = first_part(L['fast_edges'])
+        if paired_light and L['n_light']:
+            L['pair_desc'], first['pair'] = pair_records(L['light_desc'], flat.E, key)
+            L['n_pair'] = int(L['pair_desc'].shape[0])
+    return F2vLists(**L)
+
+

@@ -385,3 +385,293 @@ def test_f2v_split_without_the_small_lists():
     assert sp.heavy.tolist()[:2] == [True, False] and sp.rest.tolist()[:2] == [False, True]
     assert (sp.heavy.int() + sp.light.int() + sp.rest.int()).tolist() == [1] * len(ROWS)
     assert sp.heavy_grid_terms == 64 * 64 + 2 * 128 * 64                            # the 10-particle edge's grid: not by the recurrence
+
+
+# ---- the pair records: one per HybridQuadratic(1 discrete, 1 continuous) factor, from the light descriptors ---------------------
+NAN = float('nan')
+
+
+def light_rows(*rows):
+    """[k, 128] uint8 light descriptors of hand-built edges (include/lhvi.h, lhvi_pbp_describe): (edge, target, partner, partner's
+    canonical edge, nj, np, T, grid base, partner value, type); the six coefficients are 100 * edge + 0 .. 5"""
+    out = torch.zeros(len(rows), 128, dtype=torch.uint8)
+    w, d = out.view(torch.int32).view(-1, 32), out.view(torch.float64).view(-1, 16)
+    for i, (e, target, partner, canon, nj, np_, T, base, value, kind) in enumerate(rows):
+        w[i, 0], w[i, 1], w[i, 2], w[i, 3], w[i, 7], w[i, 8], w[i, 9], w[i, 10], w[i, 14] = e, target, partner, canon, nj, np_, T, base, kind
+        w[i, 4] = 2 if kind == 2 else 1
+        d[i, 6] = value
+        d[i, 8:14] = 100.0 * e + torch.arange(6, dtype=torch.float64)
+    return out
+
+
+def record_views(rec):
+    assert rec.dtype == torch.uint8 and rec.dim() == 2 and rec.shape[1] == 128 and rec.is_contiguous()
+    return rec.view(torch.int32).view(-1, 32).numpy(), rec.view(torch.float64).view(-1, 16).numpy()
+
+
+def coefficients(e):
+    return [100.0 * e + k for k in range(6)]
+
+
+def test_pair_records_join_the_two_edges_of_a_factor():
+    """``lhvi_pbp_t.pair_desc`` (include/lhvi.h): 0 e_c  1 e_d  2 v_c  3 v_d  4 np_c  5 T  6 grid base  7 live states of v_d
+    8-9 val_c  10-11 val_d  12-23 coefficients  24 / 25 rows of v2f with the discrete / continuous variable's message"""
+    light = light_rows(
+        (5, 11, 10, 4, 64, 2, 0, 0, NAN, 2),           # factor A, discrete target 11: its partner 10 is hidden, that one's v -> f row is 4
+        (7, 20, 21, 8, 1, 16, 24, 300, 1.0, 1),        # factor B, continuous target 20: its partner 21 is observed at 1.0
+        (9, 31, 30, 19, 1, 3, 0, 0, 0.25, 2),          # factor C, discrete target 31 (three live states): partner 30 observed at 0.25
+        (4, 10, 11, 5, 2, 64, 32, 200, NAN, 1),        # factor A, continuous target 10: partner 11 hidden, its row 5 is the entry above
+    )
+    rec, first = pbp_plan.pair_records(light, 40)
+    assert first == 0                                                               # no key: no interior part
+    w, d = record_views(rec)
+    assert w.shape[0] == 3                                                          # B, A (type-1 rows in their order), then what is left: C
+    # B: one-sided, the discrete side observed
+    assert w[0, :8].tolist() == [7, -1, 20, 21, 16, 24, 300, 1]
+    assert np.isnan(d[0, 4]) and d[0, 5] == 1.0 and d[0, 6:12].tolist() == coefficients(7)
+    assert w[0, 24] == 8 and w[0, 25] == 0
+    # A: both edges, both canonical rows; the coefficients are the continuous target's entry's
+    assert w[1, :8].tolist() == [4, 5, 10, 11, 64, 32, 200, 2]
+    assert np.isnan(d[1, 4]) and np.isnan(d[1, 5]) and d[1, 6:12].tolist() == coefficients(4)
+    assert w[1, 24] == 5 and w[1, 25] == 4
+    # C: one-sided, the continuous side observed (one partner "particle": its value)
+    assert w[2, :8].tolist() == [-1, 9, 30, 31, 1, 0, 0, 3]
+    assert d[2, 4] == 0.25 and np.isnan(d[2, 5]) and d[2, 6:12].tolist() == coefficients(9)
+    assert w[2, 24] == 0 and w[2, 25] == 19
+    assert not w[:, 26:].any()
+    # every input row is consumed exactly once
+    used = np.concatenate([w[:, 0][w[:, 0] >= 0], w[:, 1][w[:, 1] >= 0]])
+    assert sorted(used.tolist()) == [4, 5, 7, 9]
+    for view in (light.view(torch.int32).view(-1, 32), light.view(torch.float64).view(-1, 16)):      # the descriptors' typed views do as well
+        assert torch.equal(pbp_plan.pair_records(view, 40)[0], rec)
+
+
+def test_pair_records_with_an_observed_partner_leave_the_other_entry_alone():
+    """a type-1 entry whose partner is observed takes no type-2 entry, whatever its partner's canonical edge names"""
+    light = light_rows((4, 10, 11, 5, 1, 64, 32, 200, 2.0, 1), (5, 11, 10, 4, 64, 2, 0, 0, NAN, 2))
+    w, d = record_views(pbp_plan.pair_records(light, 8)[0])
+    assert w[:, 0].tolist() == [4, -1] and w[:, 1].tolist() == [-1, 5] and d[0, 5] == 2.0 and w[1, 25] == 4
+
+
+def test_pair_records_put_the_interior_factors_first():
+    factors = [(2 * f, 2 * f + 1) for f in range(9)]
+    rows, key = [], torch.zeros(18, dtype=torch.int32)
+    for f, (ec, ed) in enumerate(factors):
+        key[ec] = key[ed] = (1, 0, 1, 1, 0, 0, 1, 0, 1)[f]
+        if f % 3 != 2:
+            rows.append((ec, 100 + f, 200 + f, ed, 2, 16, 8, 0, NAN if f % 3 == 0 else 1.0, 1))
+        if f % 3 != 1:
+            rows.append((ed, 200 + f, 100 + f, ec, 16, 2, 0, 0, NAN if f % 3 == 0 else 0.5, 2))
+    light = light_rows(*rows)
+    plain, zero = pbp_plan.pair_records(light, 18)
+    rec, first = pbp_plan.pair_records(light, 18, key)
+    assert zero == 0 and plain.shape == rec.shape == (9, 128)
+    w = record_views(plain)[0]
+    rec_key = key[torch.from_numpy(np.where(w[:, 0] >= 0, w[:, 0], w[:, 1])).long()]
+    assert first == int((rec_key == 0).sum()) == 4
+    order = [i for i in range(9) if rec_key[i] == 0] + [i for i in range(9) if rec_key[i] == 1]      # stable within a key
+    assert torch.equal(rec, plain[order])
+
+
+def test_pair_records_of_no_light_edge():
+    for key in (None, torch.zeros(5, dtype=torch.int32)):
+        rec, first = pbp_plan.pair_records(torch.zeros(0, 128, dtype=torch.uint8), 5, key)
+        assert rec.shape == (0, 128) and rec.dtype == torch.uint8 and first == 0
+
+
+# ---- the factor side's lists as one record ---------------------------------------------------------------------------------------
+STRIDE = {'heavy': 128, 'small16': 128, 'small32': 128, 'light': 128, 'pair': 128, 'cq': 256}
+F2V_PARTS = dict(heavy=(5, 2), small16=(3, 0), small32=(4, 4), light=(6, 1), pair=(2, 1), cq=(3, 2), fast=(4, 3), generic=(5, 0))
+
+
+def small_lists(counts=F2V_PARTS):
+    """an F2vLists of CPU tensors with `counts`: list -> (entries, interior entries)"""
+    pad = torch.zeros(1, dtype=torch.int32)
+    L = pbp_plan.F2vLists.empty(pad)._asdict()
+    for name, nbytes in STRIDE.items():
+        k = counts[name][0]
+        L[name + '_desc'], L['n_' + name] = (torch.zeros(k * nbytes, dtype=torch.uint8) if name == 'cq' else torch.zeros(k, nbytes, dtype=torch.uint8)), k
+    L['fast_edges'], L['generic_edges'] = (torch.arange(counts[name][0], dtype=torch.int32) for name in ('fast', 'generic'))
+    L['fast_desc'] = torch.zeros(counts['fast'][0], 128, dtype=torch.uint8)
+    L['part_counts'] = {name: first for name, (_, first) in counts.items()}
+    L['generic_pts_log2'] = 4
+    return pbp_plan.F2vLists(**L)
+
+
+def test_f2v_lists_install_what_the_sweep_holds():
+    L = small_lists()
+    assert set(L.part_counts) == set(pbp_plan.F2V_LISTS) == set(F2V_PARTS)
+    s = _abi.PbpStruct()
+    L.install(s)
+    for name in STRIDE:
+        assert getattr(s, name + '_desc') == getattr(L, name + '_desc').data_ptr() and getattr(s, 'n_' + name) == F2V_PARTS[name][0]
+    assert s.fast_edges == L.fast_edges.data_ptr() and s.n_fast == 4 and s.fast_desc == L.fast_desc.data_ptr()
+    assert s.generic_edges == L.generic_edges.data_ptr() and s.n_generic == 5 and s.generic_pts_log2 == 4
+    assert L.n_fast == 4 and L.n_generic == 5
+    # the light list is the pair list's edges again: not counted
+    assert L.n_items == 5 + 3 + 4 + 2 + 3 + 4 + 5 and L.n_interior == 2 + 0 + 4 + 1 + 2 + 3 + 0
+    # under the names of the sweep object's attributes, the same tensors
+    named = L.named()
+    assert named['heavy_desc'] is L.heavy_desc and named['_fast_list'] is L.fast_edges and named['_generic_list'] is L.generic_edges
+    assert named['part_counts'] is L.part_counts and named['n_heavy'] == 5 and 'pad' not in named
+
+
+@pytest.mark.parametrize('part', [0, 1])
+def test_f2v_lists_install_a_prefix_or_a_suffix(part):
+    L = small_lists()
+    s = _abi.PbpStruct()
+    L.install(s)
+    assert L.install_part(s, part) is s
+    for name, (total, first) in F2V_PARTS.items():
+        off, cnt = (0, first) if part == 0 else (first, total - first)
+        assert getattr(s, 'n_' + name) == cnt, name
+        if name in STRIDE:
+            assert getattr(s, name + '_desc') == (getattr(L, name + '_desc').data_ptr() + STRIDE[name] * off if cnt else None), name
+        elif cnt:
+            assert getattr(s, name + '_edges') == getattr(L, name + '_edges').data_ptr() + 4 * off
+        else:           # nothing to do, and not "every edge of the graph": the pointer stays
+            assert getattr(s, name + '_edges') == getattr(L, name + '_edges').data_ptr()
+    assert s.fast_desc == L.fast_desc.data_ptr() + 128 * (0 if part == 0 else 3)
+
+
+def test_f2v_lists_without_any_list():
+    """what a state of the v -> f half alone installs: null descriptors, no entries, edge lists of no entry behind a non-null pointer"""
+    pad = torch.zeros(1, dtype=torch.int32)
+    L = pbp_plan.F2vLists.empty(pad)
+    s = _abi.PbpStruct()
+    for part in (None, 0, 1):
+        L.install(s)
+        if part is not None:
+            L.install_part(s, part)
+        for name in STRIDE:
+            assert getattr(s, name + '_desc') is None and getattr(s, 'n_' + name) == 0
+        assert s.fast_edges == pad.data_ptr() and s.generic_edges == pad.data_ptr() and s.n_fast == 0 and s.n_generic == 0
+        assert s.fast_desc is None and s.generic_pts_log2 == 6
+    assert L.part_counts == dict.fromkeys(pbp_plan.F2V_LISTS, 0) and L.n_items == 0 and L.n_interior == 0
+    assert (L.n_heavy_class, L.heavy_terms, L.heavy_grid_terms, L.cq_terms) == (0, 0, 0, 0)
+    named = L.named()
+    assert named['fast_edges'].numel() == 0 and named['cq_edges'].numel() == 0 and named['_fast_list'] is pad and named['_generic_list'] is pad
+    # an empty small or pair list leaves its fields as they are; without pair records there is no pair list
+    some = small_lists(dict(F2V_PARTS, small16=(0, 0)))._replace(pair_desc=None, n_pair=0)
+    s = _abi.PbpStruct()
+    some.install(s)
+    assert s.small16_desc is None and s.n_small16 == 0 and s.pair_desc is None and s.n_pair == 0 and s.n_small32 == 4
+
+
+# f_side_plan over a hand-built graph: edge e belongs to variable e; the described edges are those of ROWS, two more light rows (one
+# factor, both sides hidden) and, apart from them, two generic edges, one cq edge and one edge of no list (class 0)
+PLAN_ROWS = ROWS + ((1, 4, 2, 10, 32, 1, 0), (2, 1, 10, 2, 0, 2, 0))
+N_DESC = len(PLAN_ROWS)
+E_GENERIC, E_CQ, E_NONE, E_ALL = (N_DESC, N_DESC + 1), N_DESC + 2, N_DESC + 3, N_DESC + 4
+
+
+def plan_inputs():
+    import types
+    cls = torch.tensor([r[0] for r in PLAN_ROWS] + [3, 3, 4, 0], dtype=torch.uint8)
+    table = torch.zeros(E_ALL, 128, dtype=torch.uint8)
+    w, d = table.view(torch.int32).view(-1, 32), table.view(torch.float64).view(-1, 16)
+    w[:N_DESC] = words(*PLAN_ROWS)
+    w[:, 0] = torch.arange(E_ALL)
+    w[N_DESC - 2, 3], w[N_DESC - 1, 3] = N_DESC - 1, N_DESC - 2           # the last two rows: one factor, each the other's partner
+    d[N_DESC - 2:N_DESC, 6] = NAN
+    cq = torch.zeros(E_ALL, 64, dtype=torch.int32)                          # lhvi_pbp_describe_cq: 2 type, 3 S, 4 np, 5 T, 9 ny
+    cq[E_CQ, 0], cq[E_CQ, 2], cq[E_CQ, 3], cq[E_CQ, 4], cq[E_CQ, 5], cq[E_CQ, 9] = E_CQ, 1, 2, 10, 32, 7
+    var_cont = np.ones(E_ALL, dtype=bool)
+    var_cont[E_GENERIC[1]] = False
+    flat = types.SimpleNamespace(E=E_ALL, edge_var=np.arange(E_ALL), var_cont=var_cont, var_nstates=np.full(E_ALL, 3))
+    np_host = np.full(E_ALL, 10, dtype=np.int32)
+    calls = []
+
+    def describe(edges):
+        calls.append(edges.tolist())
+        return table[edges.long()].reshape(-1)
+
+    def describe_cq(edges):
+        return cq[edges.long()].contiguous().view(torch.uint8).reshape(-1)
+    return cls, flat, np_host, dict(describe=describe, describe_cq=describe_cq, long_grid_min_edges=2), calls
+
+
+def list_edges(L):
+    """list -> its edges, in list order"""
+    out = {name: getattr(L, name + '_desc').view(torch.int32).view(-1, 32)[:, 0].tolist() if getattr(L, name + '_desc') is not None else []
+           for name in ('heavy', 'small16', 'small32', 'light')}
+    out['cq'] = L.cq_desc.view(torch.int32).view(-1, 64)[:, 0].tolist() if L.cq_desc is not None else []
+    out['fast'], out['generic'] = L.fast_edges.tolist(), L.generic_edges.tolist()
+    return out
+
+
+def test_f_side_plan_puts_every_edge_on_one_list():
+    cls, flat, np_host, kw, calls = plan_inputs()
+    L = pbp_plan.f_side_plan(cls, flat, np_host, **kw)
+    assert calls == [list(range(N_DESC))]                                           # one describe call, for the edges of class 1 and 2
+    got = list_edges(L)
+    assert got == {'small16': [0], 'small32': [1], 'heavy': [2, 3, 4, 5], 'fast': [6, 7, 10], 'light': [8, 9, 11, 12],
+                   'generic': list(E_GENERIC), 'cq': [E_CQ]}
+    assert sorted(sum(got.values(), [])) == [e for e in range(E_ALL) if e != E_NONE]
+    for name in ('heavy', 'small16', 'small32', 'light', 'cq'):
+        assert getattr(L, 'n_' + name) == len(got[name])
+    assert L.cq_edges.tolist() == [E_CQ] and L.cq_edges.dtype == L.fast_edges.dtype == L.generic_edges.dtype == torch.int32
+    assert L.fast_desc.view(torch.int32).view(-1, 32)[:, 0].tolist() == got['fast']      # descriptor i is edge i's
+    assert L.n_heavy_class == 6                                                     # the heavy class: the heavy list and the two small lists
+    sp = pbp_plan.f2v_split(words(*PLAN_ROWS), True, 2)
+    assert (L.heavy_terms, L.heavy_grid_terms) == (sp.heavy_terms, sp.heavy_grid_terms)
+    assert L.cq_terms == (10 + 32) * 7 * 2                                          # type 1: (np + T) * ny * S
+    # generic edges: 10 particles + 3 integral points on the continuous variable, 10 points on the discrete one: 16 lanes
+    assert L.generic_pts_log2 == 4
+    # the pair list: the light edges again, the two of a factor in one record
+    w = record_views(L.pair_desc)[0]
+    assert L.n_pair == 3 and w[:, 0].tolist() == [8, 11, -1] and w[:, 1].tolist() == [-1, 12, 9]
+    assert L.part_counts == dict.fromkeys(pbp_plan.F2V_LISTS, 0)                    # no key: no interior part
+    off = pbp_plan.f_side_plan(cls, flat, np_host, paired_light=False, small_f2v=False, **kw)
+    assert off.pair_desc is None and off.n_pair == 0 and off.n_light == 4 and off.small16_desc.shape == (0, 128) and off.n_small16 == 0
+    assert list_edges(off)['heavy'] == [0, 2, 3, 4, 5] and list_edges(off)['fast'] == [1, 6, 7, 10]
+
+
+def test_f_side_plan_without_edges_of_a_kind():
+    cls, flat, np_host, kw, calls = plan_inputs()
+    L = pbp_plan.f_side_plan(torch.where(cls >= 3, torch.zeros_like(cls), cls), flat, np_host, **kw)
+    assert L.cq_desc is None and L.n_cq == 0 and L.cq_terms == 0 and L.generic_edges.numel() == 0 and L.generic_pts_log2 == 6
+    L = pbp_plan.f_side_plan(torch.where(cls < 3, torch.zeros_like(cls), cls), flat, np_host, **kw)
+    assert len(calls) == 1 and L.fast_edges.numel() == 0 and L.fast_desc is None and L.heavy_desc is None and L.light_desc is None
+    assert L.pair_desc is None and L.n_heavy_class == 0 and L.n_cq == 1
+    s = _abi.PbpStruct()
+    L.install(s)
+    assert s.fast_edges == L.pad.data_ptr() and s.n_fast == 0 and s.generic_edges == L.generic_edges.data_ptr() and s.n_generic == 2
+
+
+def test_f_side_plan_skips_edges_and_puts_interior_entries_first():
+    cls, flat, np_host, kw, _ = plan_inputs()
+    whole = list_edges(pbp_plan.f_side_plan(cls, flat, np_host, **kw))
+    skip = torch.zeros(E_ALL, dtype=torch.bool)
+    skip[3] = skip[10] = skip[E_GENERIC[0]] = True
+    got = list_edges(pbp_plan.f_side_plan(cls, flat, np_host, skip=skip, **kw))
+    assert got == {name: [e for e in es if not skip[e]] for name, es in whole.items()}
+    # a key: 1 on every third edge, the two light edges of the one factor alike
+    key = (torch.arange(E_ALL) % 3 == 0).to(torch.int32)
+    key[N_DESC - 2] = key[N_DESC - 1] = 1
+    L = pbp_plan.f_side_plan(cls, flat, np_host, key=key, **kw)
+    got = list_edges(L)
+    for name, es in got.items():
+        assert es == [e for e in whole[name] if key[e] == 0] + [e for e in whole[name] if key[e] == 1], name       # stable
+        assert L.part_counts[name] == sum(1 for e in es if key[e] == 0), name
+    w = record_views(L.pair_desc)[0]
+    rec_key = [int(key[a if a >= 0 else b]) for a, b in zip(w[:, 0].tolist(), w[:, 1].tolist())]
+    assert rec_key == sorted(rec_key) and L.part_counts['pair'] == rec_key.count(0) == 1 and L.n_pair == 3
+    assert L.fast_desc.view(torch.int32).view(-1, 32)[:, 0].tolist() == got['fast']
+    assert L.n_items == sum(len(es) for name, es in got.items() if name != 'light') + L.n_pair
+    assert L.n_interior == sum(first for name, first in L.part_counts.items() if name != 'light')
+    both = pbp_plan.f_side_plan(cls, flat, np_host, key=key, skip=skip, **kw)
+    assert list_edges(both) == {name: [e for e in es if not skip[e]] for name, es in got.items()}
+
+
+def test_f_side_plan_is_a_function_of_its_arguments():
+    cls, flat, np_host, kw, _ = plan_inputs()
+    key = (torch.arange(E_ALL) % 2).to(torch.int32)
+    key[N_DESC - 2] = key[N_DESC - 1] = 0
+    a, b = (pbp_plan.f_side_plan(cls, flat, np_host, key=key, **kw) for _ in range(2))
+    assert a._fields == b._fields
+    for name, x, y in zip(a._fields, a, b):
+        if torch.is_tensor(x):
+            assert x.dtype == y.dtype and x.shape == y.shape and x.numpy().tobytes() == y.numpy().tobytes(), name
+        else:
+            assert x == y, name
