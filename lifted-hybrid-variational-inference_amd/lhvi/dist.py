@@ -12,7 +12,6 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
-from .pbp_plan import V2fLists
 
 
 def joint_terms(flat, np_host, edge_mask=None):
@@ -31,23 +30,49 @@ def joint_terms(flat, np_host, edge_mask=None):
     return int(terms.sum() if edge_mask is None else terms[edge_mask].sum())
 
 
-class SingleRunner:
-    """whole graph on one GPU"""
+class _Runner:
+    """What the runners share: `bp`, the sweep state of the graph this process holds (the whole graph, or a rank's shard), the start
+    of a run, the work counts the benchmark reports and the timing of a sweep's phases."""
+
+    phases = ()                 # names of the intervals between the marks a sweep sets (two-part schedules)
 
     def __init__(self, bp):
         self.bp = bp
+        self.f2v_extra = []                 # event pairs around the second heavy-kernel launch of a sweep (bench)
+        self.record_phases = False          # sweep() records HIP events at its phase boundaries (bench.py --gpus N)
+        self._phase_events = []
+
+    def _struct(self):
+        return self.bp._struct()
 
     def init(self):
-        bp = self.bp
-        _abi.check(_abi.lib().lhvi_pbp_init(bp.dg.g, bp._struct(), _abi.ptr(bp.eta), _abi.ptr(bp.q_dev),
-                                            _abi.ptr(bp.f2v), _abi.ptr(bp.v2f), _abi.stream_ptr()))
-        bp._generate_sample()
+        self.bp._launch_init(self._struct())
+        self.bp._generate_sample()
 
-    def sweep(self, f2v_events=None):
-        self.bp.sweep(last=False, f2v_events=f2v_events)
+    def _edge_part(self, s, part):
+        """restrict the f2v work lists of `s` to the interior prefix (part 0) or the boundary suffix (part 1)"""
+        return self.bp.f2v_lists.install_part(s, part)
 
-    def local_edges(self):
-        return self.bp.flat.E
+    def _mark(self, marks):
+        if self.record_phases:
+            import torch
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            marks.append(ev)
+
+    def phase_ms(self):
+        """mean HIP-event time of each of `phases` on this rank's compute stream (call after a synchronisation), with the
+        runner's `_phase_info`; None when no sweep recorded its phases"""
+        if not self._phase_events:
+            return None
+        acc = {k: 0.0 for k in self.phases}
+        for m in self._phase_events:
+            for k, a, b in zip(self.phases, m[:-1], m[1:]):
+                acc[k] += a.elapsed_time(b)
+        n = len(self._phase_events)
+        out = {k: v / n for k, v in acc.items()}
+        out.update(sweeps=n, **self._phase_info())
+        return out
 
     def work_fraction(self):
         flat = self.bp.flat
@@ -58,11 +83,24 @@ class SingleRunner:
 
     def heavy_stats(self):
         """(edges, joint terms) of the continuous x continuous kernel's work list"""
-        return int(self.bp.n_heavy_class or self.bp.n_heavy), self.bp.heavy_terms
+        return self.bp.n_heavy, self.bp.heavy_terms
 
     def heavy_grid_terms(self):
         """joint terms at the integral points of the edges the heavy kernel serves by the grid recurrence"""
         return self.bp.heavy_grid_terms
+
+
+class SingleRunner(_Runner):
+    """whole graph on one GPU"""
+
+    def sweep(self, f2v_events=None):
+        self.bp.sweep(last=False, f2v_events=f2v_events)
+
+    def local_edges(self):
+        return self.bp.flat.E
+
+    def heavy_stats(self):
+        return int(self.bp.n_heavy_class or self.bp.n_heavy), self.bp.heavy_terms
 
 
 # =================================================================================================
@@ -354,7 +392,7 @@ class LoopbackGroup:
         return torch.cat(out) if out else self.sends[rank][0][:0]
 
 
-class ShardedRunner:
+class ShardedRunner(_Runner):
     """One rank's part of the edge-sharded particle sweep (EPBP semantics).
 
     Per sweep: local sites + information-form partials of the BOUNDARY variables -> their rows packed straight into the
@@ -374,7 +412,7 @@ class ShardedRunner:
         self.rank, self.world, self.group = rank, world, group
         bp = EPBP(None, n=n, proposal_approximation=proposal_approximation, sampler='device', seed=seed)
         bp._setup(None, flat=plan.flat, edge_key=plan.edge_boundary)
-        self.bp = bp
+        super().__init__(bp)
         dev = bp.dg.device
         bp.var_gid = _abi.to_dev(plan.var_gid)
         self.var_degree = _abi.to_dev(plan.var_degree)
@@ -385,9 +423,6 @@ class ShardedRunner:
         self.n_int = int(plan.n_interior)
         # two-part schedule: needs both parts non-empty and the fused resample kernel (n <= 64), which takes a range
         self.overlap = bool(overlap) and world > 1 and nb > 0 and self.n_int > 0 and n <= 64
-        self.f2v_extra = []                 # event pairs around the second heavy-kernel launch of a sweep (bench)
-        self.record_phases = False          # sweep() records HIP events at its phase boundaries (bench.py --gpus N)
-        self._phase_events = []
         self.ph = torch.zeros(plan.flat.V, 2, dtype=torch.float64, device=dev)
         # exchange rows, packed back to back in peer-major order: n + 2 doubles for a continuous boundary variable, its
         # np states for a discrete one (nothing else of a discrete variable is exchanged)
@@ -424,38 +459,23 @@ class ShardedRunner:
 
     def _struct(self, part=None, leave_room=True):
         """`part`: None = everything, 0 = interior variables, 1 = boundary variables (variable range only)"""
-        s = self.bp._struct()
-        if self.overlap and leave_room:
-            s.flags |= _abi.PBP_LEAVE_ROOM         # the exchange is in flight beside the persistent f2v kernels
+        var_range = (0, 0) if part is None else (0, self.n_int) if part == 0 else (self.n_int, self.plan.flat.V)
+        # (the sharded v -> f half and proposal address the variables by range; the exchange is in flight beside the persistent f2v kernels)
+        s = self.bp._struct(var_range, leave_room=self.overlap and leave_room)
         s.bslot, s.var_degree = _abi.ptr(self.bslot), _abi.ptr(self.var_degree)
         s.brow_ptr, s.brow_off, s.brow_peer = _abi.ptr(self.brow_ptr), _abi.ptr(self.brow_off), _abi.ptr(self.brow_peer)
         s.recv, s.rank = _abi.ptr(self.recv), int(self.rank)
         if self.owner_reduce:                                # one row per boundary variable: the total, in buffer B
             s.flags |= _abi.PBP_BOUNDARY_TOTALS
             s.brow_ptr, s.brow_off, s.recv = _abi.ptr(self.one_ptr), _abi.ptr(self.total_off), _abi.ptr(self.bufB)
-        s.prop_desc, s.n_prop_desc = None, 0                 # the sharded proposal addresses variables by range
-        s.prop_hub, s.n_prop_hub, s.prop_partial = None, 0, None
-        V2fLists().install(s)                                # ... and so does the sharded v -> f half
-        if part is not None:
-            s.var_lo, s.var_hi = (0, self.n_int) if part == 0 else (self.n_int, self.plan.flat.V)
         return s
-
-    def _edge_part(self, s, part):
-        """restrict the f2v work lists of `s` to the interior prefix (part 0) or the boundary suffix (part 1)"""
-        return self.bp.f2v_lists.install_part(s, part)
-
-    def init(self):
-        bp = self.bp
-        _abi.check(_abi.lib().lhvi_pbp_init(bp.dg.g, self._struct(), _abi.ptr(bp.eta), _abi.ptr(bp.q_dev),
-                                            _abi.ptr(bp.f2v), _abi.ptr(bp.v2f), _abi.stream_ptr()))
-        bp._generate_sample()
 
     # -- phase 1: everything that must precede the exchange -----------------------------------------
     def pre(self, part=None):
         """site updates + information-form partials (of one part), boundary rows packed into the send buffer"""
         bp, l, st = self.bp, _abi.lib(), _abi.stream_ptr()
         s = self._struct(part)
-        _abi.check(l.lhvi_pbp_proposal_partial(bp.dg.g, s, _abi.ptr(bp.f2v), _abi.ptr(bp.eta), _abi.ptr(self.ph), st))
+        bp._launch_proposal_partial(s, self.ph, st)
         if part != 0 and self.owner_reduce:
             s.brow_off = _abi.ptr(self.pack_off)             # one row per boundary variable: to its owner, or kept when owned here
             _abi.check(l.lhvi_pbp_boundary_pack(bp.dg.g, s, _abi.ptr(bp.f2v), _abi.ptr(self.ph), self.nb, _abi.ptr(self.bvars),
@@ -553,32 +573,28 @@ class ShardedRunner:
 
     def post(self, recv, f2v_events=None):
         """plain schedule: everything after the exchange, over all variables and edges"""
-        bp, l, st = self.bp, _abi.lib(), _abi.stream_ptr()
+        bp, st = self.bp, _abi.stream_ptr()
         # the kernels read the received rows in place (v2f: particle-part sums; proposal_finish: information-form sums in
         # rank order, so every replica of a boundary variable forms bit-identical q and draws bit-identical particles)
         self._install(recv)
         s = self._struct()
-        _abi.check(l.lhvi_pbp_v2f(bp.dg.g, s, _abi.ptr(bp.f2v), _abi.ptr(bp.v2f), st))
-        _abi.check(l.lhvi_pbp_proposal_finish(bp.dg.g, s, _abi.ptr(self.ph), _abi.ptr(bp.q_dev), st))
+        bp._launch_v2f(s, st)
+        bp._launch_proposal_finish(s, self.ph, st)
         bp._generate_sample()
         self._f2v(self._struct(), f2v_events)
 
     def _var_part(self, part, swapped):
         """v2f, proposal and new particles of one variable range.  `swapped`: the particle buffers were already exchanged
         for this sweep (by the other part), so the sample v2f weighs is in `old_particles`"""
-        bp, l, st = self.bp, _abi.lib(), _abi.stream_ptr()
+        bp, st = self.bp, _abi.stream_ptr()
         s = self._struct(part)
         if swapped:
             s.particles = _abi.ptr(bp.old_particles)
-        _abi.check(l.lhvi_pbp_v2f(bp.dg.g, s, _abi.ptr(bp.f2v), _abi.ptr(bp.v2f), st))
-        _abi.check(l.lhvi_pbp_proposal_finish(bp.dg.g, s, _abi.ptr(self.ph), _abi.ptr(bp.q_dev), st))
+        bp._launch_v2f(s, st)
+        bp._launch_proposal_finish(s, self.ph, st)
         if not swapped:
-            bp.old_particles, bp.particles = bp.particles, bp.old_particles
-            bp._draws += 1
-            bp._views = {}
-        s = self._struct(part)
-        _abi.check(l.lhvi_pbp_resample_uniq(bp.dg.g, s, _abi.ptr(bp.var_gid), int(bp.seed), int(bp._draws - 1),
-                                            _abi.ptr(bp.particles), _abi.ptr(bp.uniq), st))
+            bp._new_sample()
+        bp._launch_draw(self._struct(part), st)
 
     def interior(self, f2v_events=None):
         """the part of the sweep that needs nothing from the peers"""
@@ -601,63 +617,35 @@ class ShardedRunner:
             return
         import torch
         marks = []
-
-        def mark():
-            if self.record_phases:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                marks.append(ev)
-        mark()
+        self._mark(marks)
         send = self.pre(part=1)                             # boundary rows first: the exchange starts as early as it can
-        mark()
+        self._mark(marks)
         recv, work = self.exchange(send, async_op=True)
         extra = None
         if f2v_events:
             extra = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             self.f2v_extra.append(extra)
         self.interior(extra)
-        mark()
+        self._mark(marks)
         if work is not None:
             work.wait()                                     # the compute stream waits for the collective
-        mark()
+        self._mark(marks)
         self.boundary(recv, f2v_events)
-        mark()
+        self._mark(marks)
         if marks:
             self._phase_events.append(marks)
 
-    def phase_ms(self):
-        """mean HIP-event time of each phase of the two-part schedule on this rank's compute stream (call after a
-        synchronisation): boundary partials + pack, the interior part, the wait for the collective that is NOT hidden behind
-        it, the boundary part"""
-        if not self._phase_events:
-            return None
-        names = ('pack', 'interior', 'exchange_wait', 'boundary')
-        acc = {k: 0.0 for k in names}
-        for m in self._phase_events:
-            for k, a, b in zip(names, m[:-1], m[1:]):
-                acc[k] += a.elapsed_time(b)
-        n = len(self._phase_events)
-        out = {k: v / n for k, v in acc.items()}
-        out.update(sweeps=n, boundary_variables=int(self.nb), interior_variables=int(self.n_int),
-                   exchange='reduce to owner + totals back' if self.owner_reduce else 'all-to-all of the ranks\' rows',
-                   exchanged_MB_per_sweep=8e-6 * ((self.a_send_elems + self.b_send_elems) if self.owner_reduce else self.n_elems))
-        return out
+    # the two-part schedule: boundary partials + pack, the interior part, the wait for the collective that is NOT hidden behind it,
+    # the boundary part
+    phases = ('pack', 'interior', 'exchange_wait', 'boundary')
+
+    def _phase_info(self):
+        return dict(boundary_variables=int(self.nb), interior_variables=int(self.n_int),
+                    exchange='reduce to owner + totals back' if self.owner_reduce else 'all-to-all of the ranks\' rows',
+                    exchanged_MB_per_sweep=8e-6 * ((self.a_send_elems + self.b_send_elems) if self.owner_reduce else self.n_elems))
 
     def local_edges(self):
         return self.plan.flat.E
-
-    def work_fraction(self):
-        flat = self.plan.flat
-        return float(flat.var_hidden[flat.edge_var].mean())
-
-    def f2v_joint_terms(self):
-        return joint_terms(self.plan.flat, self.bp.np_host)
-
-    def heavy_stats(self):
-        return self.bp.n_heavy, self.bp.heavy_terms
-
-    def heavy_grid_terms(self):
-        return self.bp.heavy_grid_terms
 
 
 # =================================================================================================
@@ -913,7 +901,7 @@ class OwnerPlan:
         return canon, -(-lay['size'] // n)
 
 
-class OwnerRunner:
+class OwnerRunner(_Runner):
     """One rank's part of the owner-computes particle sweep (EPBP semantics), ``bench.py --exchange ownercompute``.
 
     Per sweep: v -> f and the proposal update of the OWNED variables (every one of them is swept once, over all its factors, in
@@ -938,7 +926,7 @@ class OwnerRunner:
         # (the v -> f half and the proposal update address the OWNED variables through the same per-variable lists as a single-GPU
         # run -- sixteen binary variables per wavefront, one record per continuous one -- not through a range of all local rows)
         bp._setup(None, flat=plan.flat, edge_key=plan.edge_key, edge_skip=plan.edge_skip, owned=plan.n_owned)
-        self.bp = bp
+        super().__init__(bp)
         bp.var_gid = _abi.to_dev(plan.var_gid)
         self.n = n
         self.n_owned, self.n_ghost = plan.n_owned, plan.n_ghost
@@ -978,9 +966,6 @@ class OwnerRunner:
             self.res_lists = (int(own.sum()), int((~own).sum()))
         self.idx = _abi.upload(up)
         self.counts = list(lay['send']['counts'])              # what a loopback group cuts this rank's send buffer by
-        self.record_phases = False
-        self._phase_events = []
-        self.f2v_extra = []
         # Two f -> v launches per sweep (factors without a ghost while the rows are in flight, the cut factors after them) pay when
         # the first one hides a good part of the exchange.  With many ranks nearly every factor of an expander is cut: the first
         # launch then hides next to nothing and costs a second ramp-up and tail of the persistent kernels (0.35 of 1.75 ms at 8
@@ -1000,22 +985,8 @@ class OwnerRunner:
 
     # ---- structs ------------------------------------------------------------------------------------------------------------
     def _struct(self, lo=0, hi=0, leave_room=False):
-        s = self.bp._struct()
-        if self.overlap and leave_room:                      # only the launches that run beside the collective leave it room
-            s.flags |= _abi.PBP_LEAVE_ROOM
-        s.prop_desc, s.n_prop_desc = None, 0                 # variables are addressed by range: owned [0, n_owned), ghosts after them
-        s.prop_hub, s.n_prop_hub, s.prop_partial = None, 0, None
-        V2fLists().install(s)
-        s.var_lo, s.var_hi = int(lo), int(hi)
-        return s
-
-    _edge_part = ShardedRunner._edge_part
-
-    def init(self):
-        bp = self.bp
-        _abi.check(_abi.lib().lhvi_pbp_init(bp.dg.g, self._struct(), _abi.ptr(bp.eta), _abi.ptr(bp.q_dev), _abi.ptr(bp.f2v),
-                                            _abi.ptr(bp.v2f), _abi.stream_ptr()))
-        bp._generate_sample()
+        """variables by range: owned [0, n_owned), ghosts after them; only the launches that run beside the collective leave it room"""
+        return self.bp._struct((lo, hi), leave_room=self.overlap and leave_room)
 
     # ---- the phases of a sweep ----------------------------------------------------------------------------------------------
     def owned_half(self):
@@ -1027,10 +998,10 @@ class OwnerRunner:
             if bp.v2f_lists is None:
                 s.var_lo, s.var_hi = 0, int(self.n_owned)
             s.halo_off, s.halo_buf = _abi.ptr(self.idx['halo_off']), _abi.ptr(self.send)
-            _abi.check(l.lhvi_pbp_v2f(bp.dg.g, s, _abi.ptr(bp.f2v), _abi.ptr(bp.v2f), st))
+            bp._launch_v2f(s, st)
             s.halo_off = s.halo_buf = None
             s.var_lo, s.var_hi = (0, 0) if s.prop_desc else (0, int(self.n_owned))
-            _abi.check(l.lhvi_pbp_proposal(bp.dg.g, s, _abi.ptr(bp.f2v), _abi.ptr(bp.eta), _abi.ptr(bp.q_dev), st))
+            bp._launch_proposal(s, st)
         L, ix = self.lay['send'], self.idx
         _abi.check(l.lhvi_pbp_halo_pack(_abi.ptr(bp.v2f), self.n, self.n_send_more, _abi.ptr(ix['send_more_edge']),
                                         _abi.ptr(ix['send_more_off']), _abi.ptr(ix['send_more_width']), _abi.ptr(bp.q_dev),
@@ -1050,18 +1021,14 @@ class OwnerRunner:
             s.resample_vars, s.n_resample_vars = _abi.ptr(self.idx['res_owned' if which == 0 else 'res_ghost']), self.res_lists[which]
             if which == 1:
                 s.flags |= _abi.PBP_NO_UNIQ                    # a ghost's first-occurrence mask is read by nobody here (no v -> f of its own)
-        _abi.check(_abi.lib().lhvi_pbp_resample_uniq(bp.dg.g, s, _abi.ptr(bp.var_gid), int(bp.seed), int(bp._draws - 1),
-                                                     _abi.ptr(bp.particles), _abi.ptr(bp.uniq), _abi.stream_ptr()))
+        bp._launch_draw(s)
 
     def interior(self, f2v_events=None):
         """what needs nothing from the peers: the owned variables' new particles, f -> v of the factors without a ghost"""
-        bp = self.bp
-        bp.old_particles, bp.particles = bp.particles, bp.old_particles
-        bp._draws += 1
-        bp._views = {}
+        self.bp._new_sample()
         self._resample(0, self.n_owned)
         if self.split_f2v:
-            bp._launch_f2v(self._edge_part(self._struct(leave_room=True), 0), f2v_events)
+            self.bp._launch_f2v(self._edge_part(self._struct(leave_room=True), 0), f2v_events)
 
     def boundary(self, recv, f2v_events=None):
         """the rest, once the peers' rows have arrived (after `interior`)"""
@@ -1095,15 +1062,9 @@ class OwnerRunner:
     def sweep(self, f2v_events=None):
         import torch
         marks = []
-
-        def mark():
-            if self.record_phases:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                marks.append(ev)
-        mark()
+        self._mark(marks)
         send = self.owned_half()
-        mark()
+        self._mark(marks)
         if self.world > 1:
             recv, work = self.exchange(send, async_op=self.overlap)
         else:
@@ -1113,30 +1074,22 @@ class OwnerRunner:
             extra = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             self.f2v_extra.append(extra)
         self.interior(extra)
-        mark()
+        self._mark(marks)
         if work is not None:
             work.wait()
-        mark()
+        self._mark(marks)
         self.boundary(recv, f2v_events)
-        mark()
+        self._mark(marks)
         if marks:
             self._phase_events.append(marks)
 
-    def phase_ms(self):
-        if not self._phase_events:
-            return None
-        names = ('owned_v2f_proposal_pack', 'interior', 'exchange_wait', 'boundary')
-        acc = {k: 0.0 for k in names}
-        for m in self._phase_events:
-            for k, a, b in zip(names, m[:-1], m[1:]):
-                acc[k] += a.elapsed_time(b)
-        n = len(self._phase_events)
-        out = {k: v / n for k, v in acc.items()}
-        out.update(sweeps=n, owned_variables=int(self.n_owned), ghost_variables=int(self.n_ghost),
-                   interior_fraction_of_f2v_lists=round(self.interior_fraction, 4), f2v_launches_per_sweep=2 if self.split_f2v else 1,
-                   cut_edge_rows_sent=int(self.lay['send']['row_edge'].size + self.lay['send']['cont_edge'].size), exchange='owner computes: v->f rows of cut edges + ghost proposals',
-                   exchanged_MB_per_sweep=8e-6 * self.lay['send']['size'])
-        return out
+    phases = ('owned_v2f_proposal_pack', 'interior', 'exchange_wait', 'boundary')
+
+    def _phase_info(self):
+        return dict(owned_variables=int(self.n_owned), ghost_variables=int(self.n_ghost),
+                    interior_fraction_of_f2v_lists=round(self.interior_fraction, 4), f2v_launches_per_sweep=2 if self.split_f2v else 1,
+                    cut_edge_rows_sent=int(self.lay['send']['row_edge'].size + self.lay['send']['cont_edge'].size), exchange='owner computes: v->f rows of cut edges + ghost proposals',
+                    exchanged_MB_per_sweep=8e-6 * self.lay['send']['size'])
 
     def local_edges(self):
         return int((~self.plan.edge_skip).sum())
@@ -1147,8 +1100,3 @@ class OwnerRunner:
     def f2v_joint_terms(self):
         return joint_terms(self.plan.flat, self.bp.np_host, ~self.plan.edge_skip)
 
-    def heavy_stats(self):
-        return self.bp.n_heavy, self.bp.heavy_terms
-
-    def heavy_grid_terms(self):
-        return self.bp.heavy_grid_terms

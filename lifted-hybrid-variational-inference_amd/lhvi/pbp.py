@@ -36,6 +36,11 @@ F2V_SCHEDULES = {
 }
 
 
+def _stream(st):
+    """the current stream's pointer unless the caller has it at hand (a null pointer is a stream too: the default one)"""
+    return _abi.stream_ptr() if st is None else st
+
+
 class _ParticleSweep:
     var_threshold = 3
     max_log_value = 700
@@ -65,6 +70,12 @@ class _ParticleSweep:
                                     # variables, made at the first call after run() (True: one fminbound / log_area / quad per call)
     map_mode = 'fminbound'          # what the batched map() runs per variable: the reference's fminbound iteration (lhvi_pbp_map_brent)
                                     # or 'global': scan + bracket refinement (map_all)
+    # state that is set later than _setup, if at all (class level: on_flat and the coarse-to-fine engine's states skip __init__)
+    var_gid = None                  # int64 device tensor: the variables' global ids, which key the device sampler on a shard (lhvi/dist.py)
+    _side = None                    # the second stream of the 'overlap' schedule, made by its first launch
+    _query_f2v = None               # belief_rv_all's table of messages at the query points
+    _stable_partition = False       # (lifted) the sweeps ran on the stable partition: a row is a cluster of equal ground variables
+    _ground = None                  # (lifted, on arrays) the ground graph and its colours, for the queries of ground variables
 
     # ---- set-up ------------------------------------------------------------------------------
     def _setup(self, graph_like, flat=None, edge_key=None, sides='vf', edge_skip=None, owned=None):
@@ -94,7 +105,6 @@ class _ParticleSweep:
         self.old_particles = dg.zeros(flat.V, n)
         self.uniq = torch.zeros(flat.V, n, dtype=torch.uint8, device=dg.device)
         self.f2v_ticket = torch.zeros(16, dtype=torch.int32, device=dg.device)    # work counters + statistics of the heavy f2v kernel (LHVI_PBP_TICKET_WORDS)
-        self.prop_partial = dg.zeros(plan.n_prop_partial, 2) if plan.n_prop_partial else None
         self.flags = (_abi.PBP_EP if self.proposal_approximation == 'EP' else 0) | \
                      (_abi.PBP_EPBP_DISCRETE if self._epbp_discrete else 0) | \
                      (_abi.PBP_CQ if self.cq_routing and bool((flat.pot_kind == 8).any()) else 0) | \
@@ -103,12 +113,10 @@ class _ParticleSweep:
         self._views, self._batched = {}, {}
         self._draws = 0
         self._static_rows = False           # the rows no listed draw writes are filled once, by the first draw (_generate_sample)
-        dev_lists = _abi.upload(plan.host)                      # the per-variable lists go to the device in one copy
-        for name in ('np_dev', 'resample_vars', '_static_idx', 'prop_desc'):
-            setattr(self, name, dev_lists[name])
-        self.n_prop_desc, self.n_prop_hub, self.prop_hub = plan.n_prop_desc, plan.n_prop_hub, dev_lists.get('prop_hub')
-        self.v2f_lists = plan.v2f.on(dev_lists, 'v2f_') if plan.v2f is not None else None
-        self._fused = plan.fused.on(dev_lists) if plan.fused is not None else None
+        # the per-variable lists go to the device in one copy
+        self.var_lists = plan.on(_abi.upload(plan.host), dg.zeros(plan.n_prop_partial, 2) if plan.n_prop_partial else None)
+        for name, value in self.var_lists.named().items():      # (np_dev, resample_vars, v2f_lists, _fused, ...)
+            setattr(self, name, value)
         # static work lists of the f -> v half sweep: which kernel serves which edge (lhvi/pbp_plan.py); none until they are built
         self._has_f_side = 'f' in sides
         self.f2v_lists = pbp_plan.F2vLists.empty(torch.zeros(1, dtype=torch.int32, device=dg.device))
@@ -143,21 +151,61 @@ class _ParticleSweep:
             fused_max_particles=int(env('LHVI_PBP_FUSED_MAX', self.fused_max_particles)),      # (tuning aid: scripts/diag/fused_batch.sh)
             fused_records16=env('LHVI_PBP_FUSED_REC16', '1') != '0')
 
-    def _struct(self):
+    def _struct(self, var_range=None, leave_room=False):
+        """`var_range`: (lo, hi) = this launch addresses the variables by range (0, 0: all of them), not through their lists;
+        `leave_room`: a collective is in flight beside the persistent f -> v kernels (LHVI_PBP_LEAVE_ROOM)"""
         s = _abi.PbpStruct()
-        s.n, s.T, s.flags = self.n, self.T, self.flags
+        s.n, s.T, s.flags = self.n, self.T, self.flags | (_abi.PBP_LEAVE_ROOM if leave_room else 0)
         s.var_threshold, s.max_log_value = float(self.var_threshold), float(self.max_log_value)
         s.particles, s.old_particles = _abi.ptr(self.particles), _abi.ptr(self.old_particles)
-        s.np, s.uniq, s.q = _abi.ptr(self.np_dev), _abi.ptr(self.uniq), _abi.ptr(self.q_dev)
+        s.uniq, s.q = _abi.ptr(self.uniq), _abi.ptr(self.q_dev)
         self.f2v_lists.install(s)
-        if getattr(self, 'v2f_lists', None) is not None:
-            self.v2f_lists.install(s)
+        if var_range is None:
+            self.var_lists.install(s, self.listed_proposal)
+        else:
+            self.var_lists.install_range(s, *var_range)
         s.f2v_ticket = _abi.ptr(self.f2v_ticket) if self.dynamic_f2v else None
-        if self.listed_proposal and getattr(self, 'prop_desc', None) is not None:
-            s.prop_desc, s.n_prop_desc = _abi.ptr(self.prop_desc), self.n_prop_desc
-            if getattr(self, 'prop_hub', None) is not None:
-                s.prop_hub, s.n_prop_hub, s.prop_partial = _abi.ptr(self.prop_hub), self.n_prop_hub, _abi.ptr(self.prop_partial)
         return s
+
+    # ---- the launches of a sweep: each entry point's argument list, once.  `st`: the current stream's pointer, when the caller
+    # has looked it up already (on a small graph a sweep is host time, and a look-up is not free: one serves a whole phase)
+    def _launch_init(self, s, st=None):
+        _abi.check(_abi.lib().lhvi_pbp_init(self.dg.g, s, _abi.ptr(self.eta), _abi.ptr(self.q_dev), _abi.ptr(self.f2v), _abi.ptr(self.v2f),
+                                            _stream(st)))
+
+    def _launch_v2f(self, s, st=None):
+        _abi.check(_abi.lib().lhvi_pbp_v2f(self.dg.g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _stream(st)))
+
+    def _launch_proposal(self, s, st=None):
+        _abi.check(_abi.lib().lhvi_pbp_proposal(self.dg.g, s, _abi.ptr(self.f2v), _abi.ptr(self.eta), _abi.ptr(self.q_dev), _stream(st)))
+
+    def _launch_proposal_partial(self, s, ph, st=None):
+        """the sites and information-form partial sums of a rank's local edges, into `ph` ([V, 2])"""
+        _abi.check(_abi.lib().lhvi_pbp_proposal_partial(self.dg.g, s, _abi.ptr(self.f2v), _abi.ptr(self.eta), _abi.ptr(ph), _stream(st)))
+
+    def _launch_proposal_finish(self, s, ph, st=None):
+        _abi.check(_abi.lib().lhvi_pbp_proposal_finish(self.dg.g, s, _abi.ptr(ph), _abi.ptr(self.q_dev), _stream(st)))
+
+    def _launch_draw(self, s, st=None):
+        """the device draw of the sample `_new_sample` has started, for the variables `s` lists or ranges over"""
+        _abi.check(_abi.lib().lhvi_pbp_resample_uniq(self.dg.g, s, _abi.ptr(self.var_gid), int(self.seed), int(self._draws - 1),
+                                                     _abi.ptr(self.particles), _abi.ptr(self.uniq), _stream(st)))
+
+    def _launch_fused(self, s, st=None):
+        """v -> f, proposal update and the NEXT sample of the fused pass's variables, drawn into the buffer `_new_sample` makes current"""
+        l, F, st = _abi.lib(), self.var_lists.fused, _stream(st)
+        args = (self.dg.g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev), _abi.ptr(self.var_gid),
+                int(self.seed), int(self._draws), _abi.ptr(self.old_particles), _abi.ptr(self.uniq))
+        if sum(F.counts):
+            _abi.check(l.lhvi_pbp_var_fused(*args, _abi.ptr(F.desc), *F.counts, st))
+        if F.desc64 is not None:
+            _abi.check(l.lhvi_pbp_var_fused64(*args, _abi.ptr(F.desc64), *F.counts64, st))
+
+    def _new_sample(self):
+        """start a new sample: the current particles become the old ones, and whatever was read off the old state is dropped"""
+        self.old_particles, self.particles = self.particles, self.old_particles
+        self._draws += 1
+        self._views, self._batched = {}, {}
 
     # ---- sampling ----------------------------------------------------------------------------
     def _host_draw(self):
@@ -189,48 +237,42 @@ class _ParticleSweep:
         self.particles.copy_(_abi.to_dev(p))
 
     def _generate_sample(self, rest_only=False):
-        """`rest_only`: the fused kernel has already drawn for its variables into the other buffer (``_fused_sweep_head``): swap,
-        then draw for the remaining listed variables only"""
-        l, st = _abi.lib(), _abi.stream_ptr()
-        k = self._draws
-        self._draws += 1
+        """`rest_only`: the fused kernel has already drawn for its variables into the other buffer (``_launch_fused``): start the
+        sample, then draw for the remaining listed variables only"""
+        L = self.var_lists
         if self.sampler == 'device':
-            self.old_particles, self.particles = self.particles, self.old_particles
+            self._new_sample()
             s = self._struct()
-            listed = self.listed_resample and self.n <= 64 and getattr(self, 'resample_vars', None) is not None
-            lst = None
+            listed = self.listed_resample and self.n <= 64 and L.resample_vars is not None
+            by_list = rest_only or (listed and self._static_rows)
             if rest_only:
-                lst = (self._fused.resample_rest, self._fused.n_resample_rest)
-            elif listed and self._static_rows:
-                lst = (self.resample_vars, int(self.resample_vars.shape[0]))
+                L.install_rest(s, 'sampler')
+            elif by_list:
+                L.install_sampler(s)
             # else the full (unlisted) draw.  As the first device draw of a listed state it goes into the CURRENT buffer only -- the
             # other one may hold the particles the v -> f messages were evaluated at (a coarse-to-fine state, or one a host sampler
             # filled) and must keep them; it only receives the rows no later listed draw writes: the states of the discrete
             # variables and the rows of the observed ones
-            if lst is not None:
-                s.resample_vars, s.n_resample_vars = _abi.ptr(lst[0]), lst[1]
-            if lst is None or lst[1]:
-                _abi.check(l.lhvi_pbp_resample_uniq(self.dg.g, s, _abi.ptr(getattr(self, 'var_gid', None)), int(self.seed), int(k),
-                                                    _abi.ptr(self.particles), _abi.ptr(self.uniq), st))
+            if not by_list or s.n_resample_vars:
+                self._launch_draw(s)
             if listed and not self._static_rows:
-                if self._static_idx is not None:
-                    self.old_particles.index_copy_(0, self._static_idx, self.particles.index_select(0, self._static_idx))
+                if L.static_idx is not None:
+                    self.old_particles.index_copy_(0, L.static_idx, self.particles.index_select(0, L.static_idx))
                 self._static_rows = True
-            self._views, self._batched = {}, {}
             return
-        elif callable(self.sampler):
+        k = self._draws
+        self._draws += 1
+        if callable(self.sampler):
             self._install(self.sampler(k, self.flat, self.q_dev.cpu().numpy()))
         else:
             self._install(self._host_draw())
-        _abi.check(l.lhvi_pbp_uniq(self.dg.g, self.n, _abi.ptr(self.particles), _abi.ptr(self.np_dev),
-                                   _abi.ptr(self.uniq), st))
+        _abi.check(_abi.lib().lhvi_pbp_uniq(self.dg.g, self.n, _abi.ptr(self.particles), _abi.ptr(L.np_dev), _abi.ptr(self.uniq),
+                                            _abi.stream_ptr()))
         self._views, self._batched = {}, {}
 
     # ---- the sweep (EPBP.run EPBP:225-289; HybridLBP.run with c2f=-1 HLBP:430-536) -------------
     def _run_sweeps(self, iteration):
-        l, st, g, p = _abi.lib(), _abi.stream_ptr(), self.dg.g, self.dg.p
-        _abi.check(l.lhvi_pbp_init(g, self._struct(), _abi.ptr(self.eta), _abi.ptr(self.q_dev), _abi.ptr(self.f2v),
-                                   _abi.ptr(self.v2f), st))
+        self._launch_init(self._struct())
         self._generate_sample()
         for i in range(iteration):
             self.sweep(last=(i == iteration - 1))
@@ -239,31 +281,25 @@ class _ParticleSweep:
     def sweep(self, last=False, f2v_events=None):
         """one flooding sweep: v2f, and unless `last`: proposal update, new sample, f2v.
         `f2v_events`: optional (start, end) torch.cuda.Event pair recorded around the f2v launch on its stream"""
-        l, st, g, p = _abi.lib(), _abi.stream_ptr(), self.dg.g, self.dg.p
-        if not last and getattr(self, '_fused', None) is not None and self._static_rows and self.sampler == 'device':
+        L, st = self.var_lists, _abi.stream_ptr()
+        if not last and L.fused is not None and self._static_rows and self.sampler == 'device':
             # few particles: one pass per continuous variable does its v -> f messages, its proposal update and its new sample
-            # (lhvi_pbp_var_fused, into the buffer the swap below makes current); the three kernels serve the other variables
-            F = self._fused
+            # (lhvi_pbp_var_fused, into the buffer the new sample makes current); the three kernels serve the other variables, each
+            # from its rest list
             s = self._struct()
-            args = (g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), _abi.ptr(self.eta), _abi.ptr(self.q_dev), _abi.ptr(getattr(self, 'var_gid', None)),
-                    int(self.seed), int(self._draws), _abi.ptr(self.old_particles), _abi.ptr(self.uniq))
-            if sum(F.counts):
-                _abi.check(l.lhvi_pbp_var_fused(*args, _abi.ptr(F.desc), *F.counts, st))
-            if F.desc64 is not None:
-                _abi.check(l.lhvi_pbp_var_fused64(*args, _abi.ptr(F.desc64), *F.counts64, st))
-            F.v2f_rest.install(s)
-            _abi.check(l.lhvi_pbp_v2f(g, s, _abi.ptr(self.f2v), _abi.ptr(self.v2f), st))
-            s.prop_desc, s.n_prop_desc = _abi.ptr(F.prop_desc_rest), F.n_prop_rest
-            _abi.check(l.lhvi_pbp_proposal(g, s, _abi.ptr(self.f2v), _abi.ptr(self.eta), _abi.ptr(self.q_dev), st))
+            self._launch_fused(s, st)
+            L.install_rest(s, 'v2f')
+            self._launch_v2f(s, st)
+            L.install_rest(s, 'proposal')
+            self._launch_proposal(s, st)
             self._generate_sample(rest_only=True)
-            self._launch_f2v(self._struct(), f2v_events)
+            self._launch_f2v(self._struct(), f2v_events, st)
             return
-        _abi.check(l.lhvi_pbp_v2f(g, self._struct(), _abi.ptr(self.f2v), _abi.ptr(self.v2f), st))
+        self._launch_v2f(self._struct(), st)
         if not last:
-            _abi.check(l.lhvi_pbp_proposal(g, self._struct(), _abi.ptr(self.f2v), _abi.ptr(self.eta),
-                                           _abi.ptr(self.q_dev), st))
+            self._launch_proposal(self._struct(), st)
             self._generate_sample()
-            self._launch_f2v(self._struct(), f2v_events)
+            self._launch_f2v(self._struct(), f2v_events, st)
 
     def _f2v_schedule(self, timed=False):
         """the F2V_SCHEDULES key of this state's f -> v half sweep; `timed`: f2v_events are given"""
@@ -276,19 +312,24 @@ class _ParticleSweep:
             return 'overlap'
         return 'timed' if timed else 'one'
 
-    def _launch_f2v(self, s, f2v_events=None):
+    def _call_f2v(self, s, out=None, st=None):
+        """ONE ``lhvi_pbp_f2v`` call on the current stream: the kernel families `s.flags` names (none named: all), into `out` (the
+        f -> v table unless given).  What bypasses the schedules calls this."""
+        _abi.check(_abi.lib().lhvi_pbp_f2v(self.dg.g, self.dg.p, s, _abi.ptr(self.v2f), _abi.ptr(self.f2v if out is None else out),
+                                           _stream(st)))
+
+    def _launch_f2v(self, s, f2v_events=None, st=None):
         """the f -> v half sweep (`lhvi_pbp_f2v`) by the schedule of _f2v_schedule.  `f2v_events`: (start, end) events recorded
         on this stream around the long kernels (heavy and small lists); the other families then run in a call of their own."""
-        l, g, p, st = _abi.lib(), self.dg.g, self.dg.p, _abi.stream_ptr()
         if not self._has_f_side:
             raise _abi.LhviError('this state was set up for the v -> f half only (sides="v")')
-        args = (_abi.ptr(self.v2f), _abi.ptr(self.f2v))
+        st = _stream(st)
         calls = F2V_SCHEDULES[self._f2v_schedule(bool(f2v_events))]
         side = any(stream == 'side' for stream, _, _, _ in calls)
         if side:
             torch = _abi.require_gpu()
             main = torch.cuda.current_stream()
-            if getattr(self, '_side', None) is None:
+            if self._side is None:
                 self._side = torch.cuda.Stream(device=self.dg.device)
                 self._fork, self._join = torch.cuda.Event(), torch.cuda.Event()
             self._fork.record(main)
@@ -298,12 +339,12 @@ class _ParticleSweep:
             s.flags = base | families | extra
             if stream == 'side':
                 with torch.cuda.stream(self._side):
-                    _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, _abi.stream_ptr()))
+                    self._call_f2v(s)
                 self._join.record(self._side)
                 continue
             if timed and f2v_events:
                 f2v_events[0].record()
-            _abi.check(l.lhvi_pbp_f2v(g, p, s, *args, st))
+            self._call_f2v(s, st=st)
             if timed and f2v_events:
                 f2v_events[1].record()
         s.flags = base
@@ -396,18 +437,18 @@ class _ParticleSweep:
         tabulates all messages, one pass adds them up per variable (count-weighted on a lifted graph with a stable
         partition: rows are clusters then).  Returns a (V, n) device tensor; rows of observed variables are 0."""
         torch = _abi.require_gpu()
-        if self.flat.lifted and not getattr(self, '_stable_partition', False):
+        if self.flat.lifted and not self._stable_partition:
             # a lifted query walks the GROUND variable's factors (HLBP:313-317); that equals the count-weighted sum over
             # the cluster's edges only when the partition is stable (run with c2f = -1)
             raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
         l, st = _abi.lib(), _abi.stream_ptr()
         xq = x if torch.is_tensor(x) else _abi.to_dev(np.ascontiguousarray(x, dtype=np.float64))
         assert tuple(xq.shape) == (self.flat.V, self.n) and xq.is_contiguous()
-        if getattr(self, '_query_f2v', None) is None or self._query_f2v.shape != self.f2v.shape:
+        if self._query_f2v is None or self._query_f2v.shape != self.f2v.shape:
             self._query_f2v = torch.empty_like(self.f2v)
         s = self._struct()
         s.particles, s.old_particles = _abi.ptr(xq), _abi.ptr(self.particles)      # partners: the current sample
-        _abi.check(l.lhvi_pbp_f2v(self.dg.g, self.dg.p, s, _abi.ptr(self.v2f), _abi.ptr(self._query_f2v), st))
+        self._call_f2v(s, out=self._query_f2v)
         out = torch.empty_like(xq)
         _abi.check(l.lhvi_pbp_var_sum(self.dg.g, s, _abi.ptr(self._query_f2v), _abi.ptr(out), st))
         return out
@@ -476,7 +517,7 @@ class _ParticleSweep:
         them in ONE launch, a thread each (``lhvi_pbp_map_brent``) -- and every discrete one takes its first state with the
         largest belief.  Returns (map [V], log-belief [V], evaluations [V]) as host arrays; observed rows hold their value."""
         flat = self.flat
-        if flat.lifted and not getattr(self, '_stable_partition', False):
+        if flat.lifted and not self._stable_partition:
             raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
         hid = np.flatnonzero(flat.var_hidden).astype(np.int32)
         out = np.nan_to_num(np.array(flat.var_value, dtype=np.float64), nan=0.0)
@@ -494,7 +535,7 @@ class _ParticleSweep:
         rows that are not continuous hidden variables."""
         torch = _abi.require_gpu()
         flat = self.flat
-        if flat.lifted and not getattr(self, '_stable_partition', False):
+        if flat.lifted and not self._stable_partition:
             raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
         rows = np.flatnonzero(flat.var_hidden & flat.var_cont).astype(np.int32)
         z, st = np.full(flat.V, np.nan), np.zeros(flat.V, dtype=np.int32)
@@ -566,7 +607,7 @@ class _ParticleSweep:
             raise ValueError('no rows to compare')
         if sizes - {1, R}:
             raise ValueError('p, a and b must have one row or as many as rows (%d): %s' % (R, sorted(sizes - {1, R})))
-        if self.flat.lifted and not getattr(self, '_stable_partition', False):
+        if self.flat.lifted and not self._stable_partition:
             raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
         torch = _abi.require_gpu()
         kind = gmkl._Torch(torch, self.particles.device)
@@ -859,6 +900,8 @@ class HybridLBP(_ParticleSweep):
         self.query_cache = dict()
 
     c2f_on_objects = False          # run(c2f >= 0) through Python objects per cluster (lhvi.c2f.run_c2f) instead of arrays
+    c2f_observer = None             # called by a coarse-to-fine run before every draw but the first (lhvi.c2f.run_c2f)
+    c2f_keep_history = False        # run_flat(c2f >= 0) keeps the partition of every sweep in c2f_history
 
     @classmethod
     def on_flat(cls, flat, n=50, k_mean_k=2, k_mean_iteration=10, proposal_approximation='EP', sampler='device', seed=0):
@@ -897,7 +940,7 @@ class HybridLBP(_ParticleSweep):
             self._run_sweeps(iteration)
             self._stable_partition = True
             return
-        self._run_c2f_arrays(flat, dg, iteration, c2f, timing, keep_history=getattr(self, 'c2f_keep_history', False))
+        self._run_c2f_arrays(flat, dg, iteration, c2f, timing, keep_history=self.c2f_keep_history)
 
     def _c2f_draw(self):
         def draw(k, flat, q_host):
@@ -921,10 +964,9 @@ class HybridLBP(_ParticleSweep):
         from . import c2f as _c2f
         from .lifting import initial_colors_device
         rvc0, fc0, sym = initial_colors_device(gflat, dg, False)                     # HLBP:432
-        observer = getattr(self, 'c2f_observer', None)
         st, G2, rvc, fc, history = _c2f.run_c2f_flat(
             gflat, dg, _DeviceEngine(self), _c2f.FlatRefiner(gflat, dg, sym), iteration, c2f, self.k_mean_k, self.k_mean_iteration,
-            self._c2f_draw(), rvc0, fc0, observer=observer, keep_history=keep_history, timing=timing)
+            self._c2f_draw(), rvc0, fc0, observer=self.c2f_observer, keep_history=keep_history, timing=timing)
         self.c2f_history = history
         self._stable_partition = False
         self.__dict__.update({k: v for k, v in st.__dict__.items()})
@@ -971,7 +1013,7 @@ class HybridLBP(_ParticleSweep):
         refiner = _c2f.DeviceRefiner(ground)
         st, flat, cg, rvc, fc, history = _c2f.run_c2f(ground, engine, refiner, iteration, c2f, self.k_mean_k,
                                                       self.k_mean_iteration, self._c2f_draw(),
-                                                      observer=getattr(self, 'c2f_observer', None))
+                                                      observer=self.c2f_observer)
         self.c2f_history = history
         self.g = cg
         # adopt the final factor-side state for the queries
@@ -1141,9 +1183,9 @@ class HybridLBP(_ParticleSweep):
         through the ground arrays of the arrays path)"""
         if self.exact_queries:
             return None
-        if getattr(self, '_stable_partition', False) and getattr(ground_rv, 'cluster', None) in self.flat.var_index:
+        if self._stable_partition and getattr(ground_rv, 'cluster', None) in self.flat.var_index:
             return 'cluster'
-        G = getattr(self, '_ground', None)
+        G = self._ground
         if G is not None and ground_rv in G['flat'].var_index:
             return 'ground'
         return None
@@ -1259,18 +1301,16 @@ class _DeviceEngine:
         setattr(st, self._names.get(name, name), value)
 
     def init(self, st):
-        _abi.check(_abi.lib().lhvi_pbp_init(st.dg.g, st._struct(), _abi.ptr(st.eta), _abi.ptr(st.q_dev), _abi.ptr(st.f2v),
-                                            _abi.ptr(st.v2f), _abi.stream_ptr()))
+        st._launch_init(st._struct())
 
     def v2f(self, st):
-        _abi.check(_abi.lib().lhvi_pbp_v2f(st.dg.g, st._struct(), _abi.ptr(st.f2v), _abi.ptr(st.v2f), _abi.stream_ptr()))
+        st._launch_v2f(st._struct())
 
     def proposal(self, st):
-        _abi.check(_abi.lib().lhvi_pbp_proposal(st.dg.g, st._struct(), _abi.ptr(st.f2v), _abi.ptr(st.eta), _abi.ptr(st.q_dev),
-                                                _abi.stream_ptr()))
+        st._launch_proposal(st._struct())
 
     def f2v(self, st):
-        _abi.check(_abi.lib().lhvi_pbp_f2v(st.dg.g, st.dg.p, st._struct(), _abi.ptr(st.v2f), _abi.ptr(st.f2v), _abi.stream_ptr()))
+        st._call_f2v(st._struct())
 
     def install(self, st, host_particles):
         st._draws = self.draws

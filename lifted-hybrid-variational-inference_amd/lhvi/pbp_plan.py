@@ -3,7 +3,7 @@ their arguments -- no environment, same arguments give the same bytes.  The reco
 (``lhvi_pbp_t``).  The variable side (``var_side_plan``) works on the graph's host arrays; ``lhvi/pbp.py::_setup`` uploads what it
 returns in one copy.  The factor side (``f_side_plan``, ``f2v_split``, ``pair_records``) works on tensors, on the device they
 live on -- the device in a sweep, the CPU in a test -- and takes the two device calls that describe edges as callables; its lists
-travel as one record (``F2vLists``), as the variable side's do (``V2fLists``, ``FusedLists``)."""
+travel as one record (``F2vLists``), as the variable side's do (``VarLists``, with its ``V2fLists`` and ``FusedLists``)."""
 from __future__ import annotations
 
 from collections import namedtuple
@@ -18,11 +18,6 @@ V2F_CLASSES = ('wide', 'narrow', 'hub', 'mid16', 'mid32')
 # (LHVI_PBP_V2F_RECORDS), not as a plain list; fused_records16: sixteen words per fused record (LHVI_PBP_FUSED_RECORDS16), not eight
 PlanOptions = namedtuple('PlanOptions', 'sampler_on_device listed_proposal listed_resample sliced_proposal prop_slice packed_v2f '
                                         'v2f_records fused fused_max_particles fused_records16')
-
-# host: name -> host array (or None), what goes to _abi.upload;  flags: to OR into lhvi_pbp_t.flags;  n_prop_partial: rows of
-# lhvi_pbp_t.prop_partial;  v2f: V2fLists, or None (the v -> f half addresses the variables by range);  fused: FusedLists or None
-VarSidePlan = namedtuple('VarSidePlan', 'host flags np_host T n_prop_desc n_prop_hub n_prop_partial v2f fused')
-
 
 class V2fLists(namedtuple('V2fLists', 'wide n_wide narrow n_narrow hub n_hub mid16 n_mid16 mid32 n_mid32', defaults=(None, 0) * 5)):
     """the v -> f half's five lists (``lhvi_pbp_t.v2f_wide / v2f_narrow / v2f_hub / v2f_mid16 / v2f_mid32``), each with its count;
@@ -54,6 +49,67 @@ class FusedLists(namedtuple('FusedLists', 'counts counts64 desc desc64 v2f_rest 
     def on(self, dev):
         return self._replace(desc=dev['fused_desc'], desc64=dev.get('fused64_desc'), prop_desc_rest=dev['prop_desc_rest'],
                              resample_rest=dev['resample_rest'], v2f_rest=self.v2f_rest.on(dev, 'v2f_rest_'))
+
+
+class VarLists(namedtuple('VarLists', 'np_dev resample_vars n_resample_vars static_idx prop_desc n_prop_desc prop_hub n_prop_hub prop_partial '
+                                      'v2f fused')):
+    """the variable side's lists on the device (``VarSidePlan.on``): particles per variable (``lhvi_pbp_t.np``), the sampler's records
+    with their count (None without a hidden continuous variable), `static_idx`: the rows no listed draw writes (None without any),
+    the proposal kernel's records, its hub rows with the scratch rows of their slices (``prop_partial``; None without hubs), the
+    ``V2fLists`` (None: variables by range) and the ``FusedLists`` (None: no fused pass)."""
+
+    def named(self):
+        """the lists under the names a sweep object holds them by"""
+        return dict(np_dev=self.np_dev, resample_vars=self.resample_vars, n_prop_desc=self.n_prop_desc, prop_hub=self.prop_hub,
+                    n_prop_hub=self.n_prop_hub, v2f_lists=self.v2f, _fused=self.fused)
+
+    def install(self, s, proposal_records=True):
+        """every variable through its lists; `proposal_records` off: the proposal kernel walks the graph arrays"""
+        s.np = _abi.ptr(self.np_dev)
+        if self.v2f is not None:
+            self.v2f.install(s)
+        if proposal_records and self.prop_desc is not None:
+            s.prop_desc, s.n_prop_desc = _abi.ptr(self.prop_desc), self.n_prop_desc
+            if self.prop_hub is not None:
+                s.prop_hub, s.n_prop_hub, s.prop_partial = _abi.ptr(self.prop_hub), self.n_prop_hub, _abi.ptr(self.prop_partial)
+
+    def install_range(self, s, lo, hi):
+        """the variables [lo, hi) by range (0, 0: all of them): no list of any kernel"""
+        s.np = _abi.ptr(self.np_dev)
+        s.prop_desc, s.n_prop_desc = None, 0
+        s.prop_hub, s.n_prop_hub, s.prop_partial = None, 0, None
+        s.resample_vars, s.n_resample_vars = None, 0
+        V2fLists().install(s)
+        s.var_lo, s.var_hi = int(lo), int(hi)
+
+    def install_sampler(self, s):
+        """the device sampler draws for its listed variables only"""
+        s.resample_vars, s.n_resample_vars = _abi.ptr(self.resample_vars), self.n_resample_vars
+
+    def install_rest(self, s, kernel):
+        """what the fused pass leaves to one of the three kernels, in the place of its full list (`s`: installed); `kernel`: 'v2f',
+        'proposal' or 'sampler'.  One at a time: each launch of a sweep sees the lists it has always seen."""
+        F = self.fused
+        if kernel == 'v2f':
+            F.v2f_rest.install(s)
+        elif kernel == 'proposal':
+            s.prop_desc, s.n_prop_desc = _abi.ptr(F.prop_desc_rest), F.n_prop_rest
+        else:
+            s.resample_vars, s.n_resample_vars = _abi.ptr(F.resample_rest), F.n_resample_rest
+
+
+class VarSidePlan(namedtuple('VarSidePlan', 'host flags np_host T n_prop_desc n_prop_hub n_prop_partial v2f fused')):
+    """host: name -> host array (or None), what goes to _abi.upload;  flags: to OR into lhvi_pbp_t.flags;  n_prop_partial: rows of
+    lhvi_pbp_t.prop_partial;  v2f: V2fLists, or None (the v -> f half addresses the variables by range);  fused: FusedLists or None"""
+
+    def on(self, dev, prop_partial):
+        """the lists a sweep holds: `dev` is `host` once uploaded, `prop_partial` the [n_prop_partial, 2] scratch rows (None without)"""
+        rr = dev['resample_vars']
+        return VarLists(np_dev=dev['np_dev'], resample_vars=rr, n_resample_vars=0 if rr is None else int(rr.shape[0]),
+                        static_idx=dev['_static_idx'], prop_desc=dev['prop_desc'], n_prop_desc=self.n_prop_desc,
+                        prop_hub=dev.get('prop_hub'), n_prop_hub=self.n_prop_hub, prop_partial=prop_partial,
+                        v2f=self.v2f.on(dev, 'v2f_') if self.v2f is not None else None,
+                        fused=self.fused.on(dev) if self.fused is not None else None)
 
 
 def first_edges(flat, vs, k, clamp):

@@ -474,6 +474,67 @@ def test_sharded_sweep_matches_single_gpu(world, two_part):
                     seen[gid] = (Pr[lv].copy(), Qr[lv].copy())
 
 
+@pytest.mark.gpu
+@pytest.mark.parametrize('kind', ['owner', 'sharded'])
+def test_a_runner_sweep_drops_the_query_caches_of_the_previous_sample(kind):
+    """a query between two sweeps of a runner caches the normalisers of that sample (``_batched``: quad, area, map, kl_logz); the
+    next sweep starts a new sample and must drop them, as the solver's own sweep does.  Two identical sets of two loopback ranks,
+    three sweeps each: set A answers ``kl_from`` after sweep 2 and after sweep 3, set B after sweep 3 only -- the two answers after
+    sweep 3 are the same bits (a stale normaliser of sweep 2 would shift A's by a difference of logarithms), and A's two differ"""
+    from lhvi import synth, dist, _abi
+    _abi.require_gpu()
+    flat = synth.hybrid_mrf_flat(V=300, deg=4, seed=37, frac_discrete=0.3, T=32)
+    n, world = 16, 2
+    owner = dist.partition_variables(flat, world)
+
+    def runners():
+        group = dist.LoopbackGroup(world)
+        if kind == 'owner':
+            rs = [dist.OwnerRunner(flat, n=n, seed=3, rank=r, world=world, group=group, var_owner=owner) for r in range(world)]
+        else:
+            rs = [dist.ShardedRunner(flat, n=n, seed=3, rank=r, world=world, group=group) for r in range(world)]
+            assert all(r.overlap for r in rs)                                       # the two-part schedule
+        for r in rs:
+            r.init()
+        return group, rs
+
+    def sweep(group, rs):
+        sends = [r.owned_half() if kind == 'owner' else r.pre(part=1) for r in rs]
+        for r, s in zip(rs, sends):
+            group.post(r.rank, s, r.counts)
+        for r in rs:
+            r.interior()
+        for r in rs:
+            r.boundary(group.collect(r.rank, None))
+
+    def query(r):
+        """KL of a unit Gaussian at the middle of the domain from the beliefs of a handful of owned (interior) continuous variables"""
+        lf = r.plan.flat
+        mine = r.plan.n_owned if kind == 'owner' else r.plan.n_interior
+        rows = np.flatnonzero(lf.var_hidden & lf.var_cont & (np.arange(lf.V) < mine))[:5]
+        assert rows.size == 5
+        lo, hi = lf.dom_lo[lf.var_dom[rows]], lf.dom_hi[lf.var_dom[rows]]
+        p = (np.ones((5, 1)), (0.5 * (lo + hi))[:, None], np.ones((5, 1)))
+        kl, info = r.bp.kl_from(p, rows=rows, a=lo, b=hi, info=True)
+        return kl, info['status']
+
+    ga, A = runners()
+    gb, B = runners()
+    for _ in range(2):
+        sweep(ga, A)
+    first = [query(r) for r in A]
+    sweep(ga, A)
+    second = [query(r) for r in A]
+    for _ in range(3):
+        sweep(gb, B)
+    fresh = [query(r) for r in B]
+    for (kl1, st1), (kl2, st2), (klb, stb) in zip(first, second, fresh):
+        print(kind, 'after sweep 2:', kl1.tolist(), st1.tolist(), ' after sweep 3:', kl2.tolist(), st2.tolist(), ' fresh:', klb.tolist(), stb.tolist())
+        assert np.isfinite(kl1).all() and np.isfinite(kl2).all() and np.isfinite(klb).all()
+        assert kl2.tobytes() == klb.tobytes() and st2.tolist() == stb.tolist()
+        assert kl2.tobytes() != kl1.tobytes()
+
+
 def _gpu_rank_worker(rank, world, port, out_dir, owner_reduce=False):
     sys.path[:0] = [ROOT, os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd')]
     import torch

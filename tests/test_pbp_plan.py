@@ -336,6 +336,113 @@ def test_v2f_lists_install_by_name_and_null_in_their_empty_form():
         assert getattr(s, 'v2f_' + k) is None and getattr(s, 'n_v2f_' + k) == 0
 
 
+# ---- the variable side's lists as one record -----------------------------------------------------------------------------------
+def var_lists(name, n, owned=None):
+    """the plan of graph `name` and its lists the way a sweep holds them, on CPU tensors in the place of the uploaded ones"""
+    plan = var_side_plan(graph(name), n, owned=owned, opts=OPTS)
+    dev = {k: None if a is None else torch.from_numpy(np.ascontiguousarray(a)) for k, a in plan.host.items()}
+    partial = torch.zeros(plan.n_prop_partial, 2, dtype=torch.float64) if plan.n_prop_partial else None
+    return plan, plan.on(dev, partial)
+
+
+def list_fields(s):
+    """every per-variable list of ``lhvi_pbp_t`` with its count, as the struct holds them"""
+    out = {'v2f_' + k: (getattr(s, 'v2f_' + k), getattr(s, 'n_v2f_' + k)) for k in V2F_CLASSES}
+    out.update(prop_desc=(s.prop_desc, s.n_prop_desc), prop_hub=(s.prop_hub, s.n_prop_hub), prop_partial=(s.prop_partial, 0),
+               resample_vars=(s.resample_vars, s.n_resample_vars))
+    return out
+
+
+def listed(lists, prefix=''):
+    return {prefix + k: (getattr(lists, k).data_ptr(), getattr(lists, 'n_' + k)) for k in V2F_CLASSES}
+
+
+@pytest.mark.parametrize('name,owned', [('hmln', None), ('hmln', 200), ('mrf', None), ('mrf', 200)])
+def test_var_lists_install_every_list(name, owned):
+    flat = graph(name)
+    plan, L = var_lists(name, 16, owned)
+    pv = np.flatnonzero(flat.var_hidden & flat.var_cont)
+    assert (L.fused is None) == (owned is not None) and L.v2f is not None and L.n_prop_desc == plan.n_prop_desc == L.prop_desc.shape[0]
+    # the sampler's list keeps the ghosts; the rows no listed draw writes are all the others
+    assert L.n_resample_vars == pv.size == L.resample_vars.shape[0] and L.static_idx.numel() == flat.V - pv.size
+    hubs = int((np.diff(flat.var_ptr)[pv if owned is None else pv[pv < owned]] > 64).sum())
+    assert L.n_prop_hub == hubs == (2 if name == 'hmln' else 0)                     # (hmln: two rows of more than 64 factors, owned both)
+    s = _abi.PbpStruct()
+    L.install(s)
+    want = listed(L.v2f, 'v2f_')
+    want.update(prop_desc=(L.prop_desc.data_ptr(), plan.n_prop_desc), resample_vars=(None, 0),      # (the sampler's list: install_sampler)
+                prop_hub=(L.prop_hub.data_ptr(), hubs) if hubs else (None, 0), prop_partial=(L.prop_partial.data_ptr() if hubs else None, 0))
+    assert list_fields(s) == want and s.np == L.np_dev.data_ptr() and s.var_lo == s.var_hi == 0
+    if hubs:                                                                        # a scratch row of two doubles per slice
+        assert tuple(L.prop_partial.shape) == (plan.n_prop_partial, 2) and L.prop_partial.dtype == torch.float64
+        assert plan.n_prop_partial == int((L.prop_desc[:, 1] < 0).sum())
+    L.install_sampler(s)
+    assert (s.resample_vars, s.n_resample_vars) == (L.resample_vars.data_ptr(), pv.size)
+    # without its records the proposal kernel walks the graph arrays: no record list, no hub rows; the other kernels keep theirs
+    s = _abi.PbpStruct()
+    L.install(s, proposal_records=False)
+    assert list_fields(s) == dict(want, prop_desc=(None, 0), prop_hub=(None, 0), prop_partial=(None, 0))
+    # what the record holds is what the plan built, and a sweep object holds it under these names
+    for k, a in plan.host.items():
+        t = {'np_dev': L.np_dev, 'resample_vars': L.resample_vars, '_static_idx': L.static_idx, 'prop_desc': L.prop_desc, 'prop_hub': L.prop_hub}.get(k)
+        if t is not None:
+            np.testing.assert_array_equal(t.numpy(), a)
+    named = L.named()
+    assert named['v2f_lists'] is L.v2f and named['_fused'] is L.fused and named['np_dev'] is L.np_dev and named['resample_vars'] is L.resample_vars
+    assert named['prop_hub'] is L.prop_hub and (named['n_prop_desc'], named['n_prop_hub']) == (plan.n_prop_desc, hubs)
+    assert set(named) == {'np_dev', 'resample_vars', 'n_prop_desc', 'prop_hub', 'n_prop_hub', 'v2f_lists', '_fused'}
+
+
+def test_var_lists_without_v2f_lists_install_none():
+    flat = synth.hybrid_mrf_flat(V=120, deg=4, seed=5, frac_discrete=0.0, T=32)     # every variable in the wide class: by range
+    plan = var_side_plan(flat, 64, owned=None, opts=OPTS)
+    L = plan.on({k: None if a is None else torch.from_numpy(a) for k, a in plan.host.items()}, None)
+    s = _abi.PbpStruct()
+    L.install(s)
+    assert L.v2f is None and L.fused is None and L.prop_hub is None and L.n_prop_desc == int(flat.var_hidden.sum()) < flat.V
+    assert list_fields(s) == dict({'v2f_' + k: (None, 0) for k in V2F_CLASSES}, prop_desc=(L.prop_desc.data_ptr(), L.n_prop_desc), prop_hub=(None, 0),
+                                  prop_partial=(None, 0), resample_vars=(None, 0))
+
+
+def test_var_lists_install_the_rest_of_the_fused_pass():
+    """the fused pass leaves the rows of more than 64 factors and every discrete variable to the three kernels (lhvi_pbp_var_fused)"""
+    plan, L = var_lists('hmln', 16)
+    F = L.fused
+    assert F.n_prop_rest == plan.n_prop_partial > 0 and F.n_resample_rest == L.n_prop_hub == 2 and F.v2f_rest.n_hub == 2
+    full = _abi.PbpStruct()
+    L.install(full)
+    L.install_sampler(full)
+    rest = dict(listed(F.v2f_rest, 'v2f_'), prop_desc=(F.prop_desc_rest.data_ptr(), F.n_prop_rest),
+                resample_vars=(F.resample_rest.data_ptr(), F.n_resample_rest))
+    kernel_fields = {'v2f': ['v2f_' + k for k in V2F_CLASSES], 'proposal': ['prop_desc'], 'sampler': ['resample_vars']}
+    for kernels in (('v2f',), ('proposal',), ('sampler',), ('v2f', 'proposal'), ('v2f', 'proposal', 'sampler')):
+        s = _abi.PbpStruct()
+        L.install(s)
+        L.install_sampler(s)
+        for kernel in kernels:
+            L.install_rest(s, kernel)
+        changed = sum((kernel_fields[k] for k in kernels), [])
+        # the named kernels' lists are the rest lists; everything else, the hub rows of the proposal among it, stays
+        assert list_fields(s) == dict(list_fields(full), **{k: rest[k] for k in changed}), kernels
+        assert s.np == full.np and s.prop_hub == L.prop_hub.data_ptr() and s.n_prop_hub == 2
+    # the rest lists name different variables than the full ones
+    assert F.v2f_rest.n_mid16 == 0 < L.v2f.n_mid16 and F.n_prop_rest < L.n_prop_desc and F.n_resample_rest < L.n_resample_vars
+
+
+@pytest.mark.parametrize('lo,hi', [(0, 0), (7, 90), (200, 451)])
+def test_var_lists_install_a_range_and_no_list(lo, hi):
+    plan, L = var_lists('hmln', 16)
+    for filled in (False, True):
+        s = _abi.PbpStruct()
+        if filled:                                                                  # a range takes every list out again
+            L.install(s)
+            for kernel in ('v2f', 'proposal', 'sampler'):
+                L.install_rest(s, kernel)
+        L.install_range(s, lo, hi)
+        assert all(v == (None, 0) for v in list_fields(s).values()), list_fields(s)
+        assert (s.var_lo, s.var_hi) == (lo, hi) and s.np == L.np_dev.data_ptr()
+
+
 # ---- the factor side: which described edge goes to which f -> v kernel ---------------------------------------------------------
 def words(*rows):
     """descriptor words of hand-built edges: (class, potential kind, nj, np, T, light type, uniform grid)"""
