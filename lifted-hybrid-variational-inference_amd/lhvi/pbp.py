@@ -22,7 +22,7 @@ from math import e, log, sqrt
 
 import numpy as np
 
-from . import _abi, pbp_plan
+from . import _abi, pbp_plan, pbp_query
 from .flat import flatten
 
 # Schedules of the f -> v half sweep (_ParticleSweep._launch_f2v): the lhvi_pbp_f2v calls in issue order, each as (stream, kernel
@@ -296,7 +296,9 @@ class _ParticleSweep:
             self._launch_f2v(self._struct(), f2v_events, st)
             return
         self._launch_v2f(self._struct(), st)
-        if not last:
+        if last:
+            self._batched = {}              # the queries read v2f: what was answered from the previous messages is dropped
+        else:
             self._launch_proposal(self._struct(), st)
             self._generate_sample()
             self._launch_f2v(self._struct(), f2v_events, st)
@@ -406,29 +408,47 @@ class _ParticleSweep:
             out[(rv, f)] = {x: float(V2F[e, j]) for j, x in enumerate(pts)}
         return out
 
+    # ---- the launches of the point and grid queries: each entry point's argument list, once (``_brent``, ``quad_all`` and
+    # ``kl_from`` below hold those of lhvi_pbp_map_brent, lhvi_pbp_quad and lhvi_pbp_kl) ------------------------------------------
+    def _launch_belief_points(self, qvar_t, x_t):
+        """``belief_rv`` (EPBP:196-202) of the variables `qvar_t` (int32 [R]) at the points `x_t` ([R, m]), as a tensor like `x_t`"""
+        out = _abi.require_gpu().empty_like(x_t)
+        _abi.check(_abi.lib().lhvi_pbp_belief_points(self.dg.g, self.dg.p, self._struct(), _abi.ptr(self.v2f), int(x_t.shape[0]),
+                                                     _abi.ptr(qvar_t), int(x_t.shape[1]), _abi.ptr(x_t), _abi.ptr(out), _abi.stream_ptr()))
+        return out
+
+    def _launch_edge_points(self, edge_t, x_t):
+        """the f -> v messages of the edges `edge_t` (int32 [R]) at the points `x_t` ([R, m]), as a tensor like `x_t`; no rows, no launch"""
+        out = _abi.require_gpu().empty_like(x_t)
+        if x_t.shape[0]:
+            _abi.check(_abi.lib().lhvi_pbp_edge_points(self.dg.g, self.dg.p, self._struct(), _abi.ptr(self.v2f), int(x_t.shape[0]),
+                                                       _abi.ptr(edge_t), int(x_t.shape[1]), _abi.ptr(x_t), _abi.ptr(out), _abi.stream_ptr()))
+        return out
+
+    def _launch_domain_grid(self):
+        """a new [V, n] tensor: per row a uniform grid on a continuous hidden variable's domain, the states of a discrete one"""
+        x = _abi.require_gpu().empty_like(self.particles)
+        _abi.check(_abi.lib().lhvi_pbp_domain_grid(self.dg.g, self._struct(), _abi.ptr(x), _abi.stream_ptr()))
+        return x
+
+    def _need_stable_rows(self):
+        """the batched queries take a row of the solver's graph for a variable.  A lifted query walks the GROUND variable's factors
+        (HLBP:313-317); that equals the count-weighted sum over the cluster's edges only when the partition is stable"""
+        if self.flat.lifted and not self._stable_partition:
+            raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
+
     # ---- queries (A8) ------------------------------------------------------------------------
     def _belief_rv_points(self, v, xs):
         """belief_rv(x) for one variable index at a batch of points, on the device (EPBP:196-202)"""
-        torch = _abi.require_gpu()
         xs = np.atleast_1d(np.asarray(xs, dtype=np.float64))
-        qvar = _abi.to_dev(np.array([v], dtype=np.int32))
-        x = _abi.to_dev(xs.reshape(1, -1))
-        out = torch.empty_like(x)
-        _abi.check(_abi.lib().lhvi_pbp_belief_points(self.dg.g, self.dg.p, self._struct(), _abi.ptr(self.v2f), 1,
-                                                     _abi.ptr(qvar), int(xs.size), _abi.ptr(x), _abi.ptr(out),
-                                                     _abi.stream_ptr()))
+        out = self._launch_belief_points(_abi.to_dev(np.array([v], dtype=np.int32)), _abi.to_dev(xs.reshape(1, -1)))
         return out.cpu().numpy().reshape(-1)
 
     def belief_rv_batch(self, rvs, xs):
         """log-beliefs of many variables at `xs[i]` points each, one launch (extension, not in the reference)"""
-        torch = _abi.require_gpu()
         idx = np.array([self._var_of(rv) for rv in rvs], dtype=np.int32)
         x = _abi.to_dev(np.asarray(xs, dtype=np.float64).reshape(len(rvs), -1))
-        out = torch.empty_like(x)
-        _abi.check(_abi.lib().lhvi_pbp_belief_points(self.dg.g, self.dg.p, self._struct(), _abi.ptr(self.v2f),
-                                                     len(rvs), _abi.ptr(_abi.to_dev(idx)), int(x.shape[1]),
-                                                     _abi.ptr(x), _abi.ptr(out), _abi.stream_ptr()))
-        return out.cpu().numpy()
+        return self._launch_belief_points(_abi.to_dev(idx), x).cpu().numpy()
 
     # ---- batched queries: every variable at once (extension; SURVEY.md section 8(f) row 3) ------------------------
     def belief_rv_all(self, x):
@@ -437,10 +457,7 @@ class _ParticleSweep:
         tabulates all messages, one pass adds them up per variable (count-weighted on a lifted graph with a stable
         partition: rows are clusters then).  Returns a (V, n) device tensor; rows of observed variables are 0."""
         torch = _abi.require_gpu()
-        if self.flat.lifted and not self._stable_partition:
-            # a lifted query walks the GROUND variable's factors (HLBP:313-317); that equals the count-weighted sum over
-            # the cluster's edges only when the partition is stable (run with c2f = -1)
-            raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
+        self._need_stable_rows()
         l, st = _abi.lib(), _abi.stream_ptr()
         xq = x if torch.is_tensor(x) else _abi.to_dev(np.ascontiguousarray(x, dtype=np.float64))
         assert tuple(xq.shape) == (self.flat.V, self.n) and xq.is_contiguous()
@@ -463,16 +480,14 @@ class _ParticleSweep:
         torch = _abi.require_gpu()
         l, st = _abi.lib(), _abi.stream_ptr()
         n, flat = self.n, self.flat
-        x = torch.empty(flat.V, n, dtype=torch.float64, device=self.particles.device)
+        x = self._launch_domain_grid()
         best = torch.empty(flat.V, dtype=torch.float64, device=x.device)
         val = torch.empty_like(best)
         s = self._struct()
-        _abi.check(l.lhvi_pbp_domain_grid(self.dg.g, s, _abi.ptr(x), st))
         passes = -(-int(scan) // n) if n >= 3 else 1
         if passes > 1 and bool((flat.var_hidden & flat.var_cont).any()):
             cont = _abi.to_dev(flat.var_hidden & flat.var_cont)[:, None]
-            lo = _abi.to_dev(np.where(flat.var_cont, flat.dom_lo[flat.var_dom], 0.0))[:, None]
-            hi = _abi.to_dev(np.where(flat.var_cont, flat.dom_hi[flat.var_dom], 1.0))[:, None]
+            lo, hi = (_abi.to_dev(t)[:, None] for t in pbp_query.domain_bounds(flat))
             h = (hi - lo) / (passes * (n - 1))
             j = torch.arange(n, dtype=torch.float64, device=x.device)[None, :]
             bx = bv = None
@@ -517,8 +532,7 @@ class _ParticleSweep:
         them in ONE launch, a thread each (``lhvi_pbp_map_brent``) -- and every discrete one takes its first state with the
         largest belief.  Returns (map [V], log-belief [V], evaluations [V]) as host arrays; observed rows hold their value."""
         flat = self.flat
-        if flat.lifted and not self._stable_partition:
-            raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
+        self._need_stable_rows()
         hid = np.flatnonzero(flat.var_hidden).astype(np.int32)
         out = np.nan_to_num(np.array(flat.var_value, dtype=np.float64), nan=0.0)
         val, nfev = np.zeros(flat.V), np.zeros(flat.V, dtype=np.int32)
@@ -535,8 +549,7 @@ class _ParticleSweep:
         rows that are not continuous hidden variables."""
         torch = _abi.require_gpu()
         flat = self.flat
-        if flat.lifted and not self._stable_partition:
-            raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
+        self._need_stable_rows()
         rows = np.flatnonzero(flat.var_hidden & flat.var_cont).astype(np.int32)
         z, st = np.full(flat.V, np.nan), np.zeros(flat.V, dtype=np.int32)
         if rows.size:
@@ -607,8 +620,7 @@ class _ParticleSweep:
             raise ValueError('no rows to compare')
         if sizes - {1, R}:
             raise ValueError('p, a and b must have one row or as many as rows (%d): %s' % (R, sorted(sizes - {1, R})))
-        if self.flat.lifted and not self._stable_partition:
-            raise NotImplementedError('batched queries on a lifted graph need a stable partition (run(c2f=-1))')
+        self._need_stable_rows()
         torch = _abi.require_gpu()
         kind = gmkl._Torch(torch, self.particles.device)
         wp, mup, varp = gmkl._mixture(kind, p, 'p')
@@ -642,8 +654,7 @@ class _ParticleSweep:
             raise ValueError('npts must be at least 2')
         a, b = self._per_var(a), self._per_var(b)
         n = self.n
-        x = torch.empty(self.flat.V, n, dtype=torch.float64, device=a.device)
-        _abi.check(_abi.lib().lhvi_pbp_domain_grid(self.dg.g, self._struct(), _abi.ptr(x), _abi.stream_ptr()))
+        x = self._launch_domain_grid()
         cont = _abi.to_dev(self.flat.var_hidden & self.flat.var_cont)
         step = (b - a) / (npts - 1)                                   # numpy.linspace: start + i * step, last point = stop
         lin = torch.arange(npts, dtype=torch.float64, device=a.device)[None, :] * step[:, None] + a[:, None]
@@ -674,11 +685,8 @@ class _ParticleSweep:
         m = xq.shape[1]
         if m > self.n:
             raise ValueError('at most n query points per variable')
-        lo = np.where(flat.var_cont, flat.dom_lo[flat.var_dom], 0.0)
-        hi = np.where(flat.var_cont, flat.dom_hi[flat.var_dom], 1.0)
-        z, shift = self.log_area_all(lo, hi, 20)
-        grid = torch.empty(flat.V, self.n, dtype=torch.float64, device=xq.device)
-        _abi.check(_abi.lib().lhvi_pbp_domain_grid(self.dg.g, self._struct(), _abi.ptr(grid), _abi.stream_ptr()))
+        z, shift = self._domain_area()
+        grid = self._launch_domain_grid()
         cont = _abi.to_dev(flat.var_hidden & flat.var_cont)
         grid[:, :m] = torch.where(cont[:, None], xq, grid[:, :m])     # discrete rows keep their states
         logb = self.belief_rv_all(grid)
@@ -697,10 +705,7 @@ class _ParticleSweep:
     def probability_all(self, a, b):
         """``probability(a, b, rv)`` (EPBP:356-375, HLBP:384-403) of every continuous hidden variable at once: 5-point
         trapezoid on [a[v], b[v]] over the 20-point one on the domain.  Returns a device tensor [V] (NaN elsewhere)."""
-        flat = self.flat
-        lo = np.where(flat.var_cont, flat.dom_lo[flat.var_dom], 0.0)
-        hi = np.where(flat.var_cont, flat.dom_hi[flat.var_dom], 1.0)
-        z, shift = self.log_area_all(lo, hi, 20)
+        z, shift = self._domain_area()
         num, _ = self.log_area_all(a, b, 5, shift=shift)
         return num / z
 
@@ -720,22 +725,18 @@ class _ParticleSweep:
             return self._query_cache('map_global', lambda: self.map_all(steps=6 if self.n >= 32 else 9)[0])
         return self._query_cache('map', lambda: self.map_fminbound_all()[0])
 
+    def _domain_area(self):
+        """(z, shift) of ``log_area`` over the domain with 20 points for every row (``log_area_all``): the normaliser of ``belief_all``
+        and ``probability_all``, as device tensors, computed once per sample"""
+        return self._query_cache('domain_area', lambda: self.log_area_all(*pbp_query.domain_bounds(self.flat), 20))
+
     def _cached_area(self):
-        """(z, shift) of ``log_area`` over the domain with 20 points for every row (``log_area_all``), host arrays"""
-        def fill():
-            flat = self.flat
-            lo = np.where(flat.var_cont, flat.dom_lo[flat.var_dom], 0.0)
-            hi = np.where(flat.var_cont, flat.dom_hi[flat.var_dom], 1.0)
-            z, shift = self.log_area_all(lo, hi, 20)
-            return z.cpu().numpy(), shift.cpu().numpy()
-        return self._query_cache('area', fill)
+        """``_domain_area`` as host arrays"""
+        return self._query_cache('area', lambda: tuple(t.cpu().numpy() for t in self._domain_area()))
 
     def log_message_balance(self, message):
-        """EPBP.log_message_balance (EPBP:204-215) on a host dict (used by log_area)"""
-        values = list(message.values())
-        mean_m = float(np.mean(values))
-        max_m = max(values)
-        shift = max_m - self.max_log_value if max_m - mean_m > self.max_log_value else mean_m
+        """EPBP.log_message_balance (EPBP:204-215) on a host dict"""
+        shift = pbp_query.balance_shift(list(message.values()), self.max_log_value)
         for k in message:
             message[k] = message[k] - shift
         return shift
@@ -744,18 +745,7 @@ class _ParticleSweep:
         """``log_area`` with the reference's signature (EPBP:291-308, HLBP:324-341): trapezoid of exp(f(x) - shift) on
         linspace(a, b, n) for a callable log-density ``f``; returns (area, shift)"""
         x = np.linspace(a, b, n)
-        d = x[1] - x[0]
-        y = {i: f(v) for i, v in enumerate(x)}
-        if shift is None:
-            shift = self.log_message_balance(y)
-        else:
-            y = {k: val - shift for k, val in y.items()}
-        res, prev = 0, e ** y[0]
-        for i in range(1, n):
-            cur = e ** y[i]
-            res += (prev + cur) * d
-            prev = cur
-        return res * 0.5, shift
+        return pbp_query.balanced_trapezoid([f(v) for v in x], x[1] - x[0], shift, self.max_log_value)
 
     @staticmethod
     def get_cluster(instance):
@@ -764,18 +754,7 @@ class _ParticleSweep:
     def _log_area(self, v, a, b, npts, shift=None):
         """EPBP.log_area (EPBP:291-308): trapezoid of exp(belief_rv - shift) on linspace(a, b, npts)"""
         x = np.linspace(a, b, npts)
-        d = x[1] - x[0]
-        y = dict(enumerate(self._belief_rv_points(v, x).tolist()))
-        if shift is None:
-            shift = self.log_message_balance(y)
-        else:
-            y = {k: val - shift for k, val in y.items()}
-        res, prev = 0, e ** y[0]
-        for i in range(1, npts):
-            cur = e ** y[i]
-            res += (prev + cur) * d
-            prev = cur
-        return res * 0.5, shift
+        return pbp_query.balanced_trapezoid(self._belief_rv_points(v, x).tolist(), x[1] - x[0], shift, self.max_log_value)
 
     @staticmethod
     def message_normalization(message):
@@ -789,6 +768,62 @@ class _ParticleSweep:
     def norm_pdf(x, mu, sig):
         u = (x - mu) / sig
         return np.exp(-u * u * 0.5) / (2.506628274631 * sig)
+
+    # ---- the reference's per-variable calls (EPBP:310-394, HLBP:343-424).  A solver says how a call maps to a row of a batched pass
+    # (`_row_of`: ('cluster', row of its graph), ('ground', row of the ground graph) or (None, None): one scipy run per call) and
+    # which normaliser its ``belief`` divides by (`_normaliser`) ----------------------------------------------------------------------
+    def _batched_rows(self, how, what):
+        """the batched answer to `what` ('map': values; 'area': (z, shift) of the 20-point ``log_area`` over the domain), each
+        indexed by the rows of `how`"""
+        return self._cached_map() if what == 'map' else self._cached_area()
+
+    def _area_of(self, rv):
+        """(z, shift) of the 20-point ``log_area`` over rv's domain (EPBP:364-366, HLBP:361-365), batched when possible"""
+        how, row = self._row_of(rv)
+        if how is None:
+            return self._log_area(self._var_of(rv), rv.domain.values[0], rv.domain.values[1], 20)
+        z, shift = self._batched_rows(how, 'area')
+        return float(z[row]), float(shift[row])
+
+    def _state_beliefs(self, rv):
+        """{state: normalised belief} of a discrete hidden variable"""
+        vals = rv.domain.values
+        b = dict(zip(vals, (e ** t for t in self._belief_rv_points(self._var_of(rv), vals).tolist())))
+        self.message_normalization(b)
+        return b
+
+    def _belief(self, x, rv, log_belief=False, inf_integral=False):
+        if rv.value is not None:
+            if log_belief:
+                return 0 if x == rv.value else -np.inf
+            return 1 if x == rv.value else 0
+        if rv.domain.continuous:
+            z, shift = self._normaliser(rv, inf_integral)
+            lb_x = float(self._belief_rv_points(self._var_of(rv), [x])[0]) - shift - log(z)
+            return lb_x if log_belief else e ** lb_x
+        b = self._state_beliefs(rv)
+        return log(b[x]) if log_belief else b[x]
+
+    def probability(self, a, b, rv):
+        if rv.value is None and rv.domain.continuous:
+            z, shift = self._area_of(rv)
+            num, _ = self._log_area(self._var_of(rv), a, b, 5, shift)
+            return num / z
+        return None
+
+    def map(self, rv):
+        if rv.value is not None:
+            return rv.value
+        how, row = self._row_of(rv)
+        if how is not None:
+            return pbp_query.typed_value(rv, self._batched_rows(how, 'map')[row])
+        v = self._var_of(rv)
+        if rv.domain.continuous:
+            from scipy.optimize import fminbound
+            return fminbound(lambda val: -float(self._belief_rv_points(v, [val])[0]),
+                             rv.domain.values[0], rv.domain.values[1], disp=False)
+        vals = list(rv.domain.values)           # (the particles of a discrete variable are its states)
+        return vals[int(np.argmax(self._belief_rv_points(v, vals)))]
 
 
 class EPBP(_ParticleSweep):
@@ -816,36 +851,29 @@ class EPBP(_ParticleSweep):
     def belief_rv(self, x, rv, sample=None):
         return float(self._belief_rv_points(self._var_of(rv), [x])[0])
 
-    def belief(self, x, rv, log_belief=False, inf_integral=False):
-        """EPBP.belief (EPBP:310-354): normaliser by adaptive quadrature of exp(belief_rv)"""
-        if rv.value is not None:
-            if log_belief:
-                return 0 if x == rv.value else -np.inf
-            return 1 if x == rv.value else 0
-        v = self._var_of(rv)
-        if rv.domain.continuous:
-            if rv in self.cache:
-                z, shift = self.cache[rv]
-            elif not self.exact_queries and not inf_integral:
+    def _row_of(self, rv):
+        return (None, None) if self.exact_queries else ('cluster', self._var_of(rv))
+
+    def _normaliser(self, rv, inf_integral=False):
+        """(z, shift = 0) of ``EPBP.belief`` (EPBP:321-331): adaptive quadrature of exp(belief_rv), kept per variable in ``cache``"""
+        if rv not in self.cache:
+            v = self._var_of(rv)
+            if not self.exact_queries and not inf_integral:
                 # the normalisers of all variables from one launch (quad_all), made at the first call after run()
                 zs, status = self._query_cache('quad', self.quad_all)
                 if status[v] == 3:
                     raise OverflowError('(34, \'Numerical result out of range\')')      # e ** belief_rv overflowed, as in the reference (EPBP:326)
-                z, shift = float(zs[v]), 0
-                self.cache[rv] = (z, shift)
+                z = float(zs[v])
             else:
                 from scipy.integrate import quad
                 lb, ub = (-np.inf, np.inf) if inf_integral else (rv.domain.values[0] - 20, rv.domain.values[1] + 20)
                 z = quad(lambda val: e ** float(self._belief_rv_points(v, [val])[0]), lb, ub)[0]
-                shift = 0
-                self.cache[rv] = (z, shift)
-            logz = log(z)
-            lb_x = float(self._belief_rv_points(v, [x])[0]) - shift - logz
-            return lb_x if log_belief else e ** lb_x
-        vals = rv.domain.values
-        b = dict(zip(vals, (e ** t for t in self._belief_rv_points(v, vals).tolist())))
-        self.message_normalization(b)
-        return log(b[x]) if log_belief else b[x]
+            self.cache[rv] = (z, 0)
+        return self.cache[rv]
+
+    def belief(self, x, rv, log_belief=False, inf_integral=False):
+        """EPBP.belief (EPBP:310-354): normaliser by adaptive quadrature of exp(belief_rv)"""
+        return self._belief(x, rv, log_belief, inf_integral)
 
     def _kl_logz(self):
         """``log`` of ``quad_all()``'s ``z`` (the cache ``belief`` fills too): the normaliser of ``EPBP.belief`` (EPBP:321-331);
@@ -853,33 +881,6 @@ class EPBP(_ParticleSweep):
         zs, _ = self._query_cache('quad', self.quad_all)
         with np.errstate(invalid='ignore', divide='ignore'):
             return np.log(zs)
-
-    def probability(self, a, b, rv):
-        if rv.value is None and rv.domain.continuous:
-            v = self._var_of(rv)
-            if self.exact_queries:
-                z, shift = self._log_area(v, rv.domain.values[0], rv.domain.values[1], 20)
-            else:                               # the normaliser of every variable from one batched pass (same 20-point trapezoid)
-                zs, shifts = self._cached_area()
-                z, shift = float(zs[v]), float(shifts[v])
-            num, _ = self._log_area(v, a, b, 5, shift)
-            return num / z
-        return None
-
-    def map(self, rv):
-        if rv.value is not None:
-            return rv.value
-        v = self._var_of(rv)
-        if not self.exact_queries:
-            m = self._cached_map()[v]
-            return float(m) if rv.domain.continuous else type(rv.domain.values[0])(m)
-        if rv.domain.continuous:
-            from scipy.optimize import fminbound
-            return fminbound(lambda val: -float(self._belief_rv_points(v, [val])[0]),
-                             rv.domain.values[0], rv.domain.values[1], disp=False)
-        pts = list(self.sample[rv])
-        vals = self._belief_rv_points(v, pts)
-        return pts[int(np.argmax(vals))]
 
 
 class HybridLBP(_ParticleSweep):
@@ -1047,21 +1048,11 @@ class HybridLBP(_ParticleSweep):
         (the same number of points each), one launch.  Works after any ``run_flat`` (the partition need not be stable)."""
         torch = _abi.require_gpu()
         ptr, edge, mult = self._ground_pairs()
-        dev = edge.device
         vs_t = _abi.to_dev(np.asarray(vs, dtype=np.int64))
         x = xs if torch.is_tensor(xs) else _abi.to_dev(np.ascontiguousarray(xs, dtype=np.float64))
         x = x.reshape(vs_t.numel(), -1)
-        deg = ptr[vs_t + 1] - ptr[vs_t]
-        total = int(deg.sum().item())
-        owner = torch.repeat_interleave(torch.arange(vs_t.numel(), device=dev), deg, output_size=total)
-        start = torch.cumsum(deg, 0) - deg
-        idx = ptr[vs_t][owner] + (torch.arange(total, device=dev) - start[owner])
-        xe = x[owner].contiguous()
-        out = torch.empty_like(xe)
-        if total:
-            _abi.check(_abi.lib().lhvi_pbp_edge_points(self.dg.g, self.dg.p, self._struct(), _abi.ptr(self.v2f), total,
-                                                       _abi.ptr(edge[idx].contiguous()), int(x.shape[1]), _abi.ptr(xe), _abi.ptr(out),
-                                                       _abi.stream_ptr()))
+        _, owner, idx = pbp_query.expand_rows(ptr, vs_t)
+        out = self._launch_edge_points(edge[idx].contiguous(), x[owner].contiguous())
         res = torch.zeros_like(x)
         res.index_add_(0, owner, out * mult[idx][:, None])
         return res
@@ -1081,16 +1072,11 @@ class HybridLBP(_ParticleSweep):
 
     def _belief_rv_points(self, ground_rv, xs):
         """belief_rv_query(x, rv) = sum over the ground rv's factors f of message_f_to_rv(x, f.cluster, rv.cluster)"""
-        torch = _abi.require_gpu()
         xs = np.atleast_1d(np.asarray(xs, dtype=np.float64))
         acc = self._ground_edges(ground_rv)
         edges = np.array(list(acc), dtype=np.int32)
         mult = np.array([acc[e] for e in acc], dtype=np.float64)
-        x = _abi.to_dev(np.tile(xs, (edges.size, 1)))
-        out = torch.empty_like(x)
-        _abi.check(_abi.lib().lhvi_pbp_edge_points(self.dg.g, self.dg.p, self._struct(), _abi.ptr(self.v2f), int(edges.size),
-                                                   _abi.ptr(_abi.to_dev(edges)), int(xs.size), _abi.ptr(x), _abi.ptr(out),
-                                                   _abi.stream_ptr()))
+        out = self._launch_edge_points(_abi.to_dev(edges), _abi.to_dev(np.tile(xs, (edges.size, 1))))
         return (out.cpu().numpy() * mult[:, None]).sum(axis=0)
 
     def belief_rv_batch(self, rvs, xs):
@@ -1100,11 +1086,6 @@ class HybridLBP(_ParticleSweep):
     def belief_rv_query(self, x, rv, sample=None):
         return float(self._belief_rv_points(rv, [x])[0])
 
-    @property
-    def q(self):
-        flat, Q = self.flat, self._host('q_dev')
-        return {rv: (float(Q[v, 0]), float(Q[v, 1])) for v, rv in enumerate(flat.rvs) if flat.var_hidden[v] and flat.var_cont[v]}
-
     # ---- batched queries of GROUND variables (any partition): what the per-variable calls below are answered from ---------------
     def _ground_rows(self):
         """hidden ground variables of the run's ground graph, their domain bounds and kind (arrays path only)"""
@@ -1112,10 +1093,7 @@ class HybridLBP(_ParticleSweep):
         if 'rows' not in G:
             gf = G['flat']
             hid = np.flatnonzero(gf.var_hidden)
-            cont = gf.var_cont[hid]
-            lo = np.where(cont, gf.dom_lo[gf.var_dom[hid]], 0.0)
-            hi = np.where(cont, gf.dom_hi[gf.var_dom[hid]], 1.0)
-            G['rows'] = (hid, cont, lo, hi, {int(v): i for i, v in enumerate(hid)})
+            G['rows'] = (hid, gf.var_cont[hid], *pbp_query.domain_bounds(gf, hid))
         return G['rows']
 
     def ground_map_all(self, scan=64, steps=6):
@@ -1124,7 +1102,7 @@ class HybridLBP(_ParticleSweep):
         per step: 1e-6 of the domain width after 6).  Discrete variables: the first state with the largest belief.  Returns
         (ground variable ids, MAP values)."""
         torch = _abi.require_gpu()
-        hid, cont, lo, hi, _ = self._ground_rows()
+        hid, cont, lo, hi = self._ground_rows()
         gf = self._ground['flat']
         out = np.zeros(hid.size)
         ci = np.flatnonzero(cont)
@@ -1168,7 +1146,7 @@ class HybridLBP(_ParticleSweep):
     def ground_log_area_all(self, npts=20):
         """``log_area`` (HLBP:324-341) over the domain of every hidden continuous GROUND variable: (ids, area, shift)"""
         torch = _abi.require_gpu()
-        hid, cont, lo, hi, _ = self._ground_rows()
+        hid, cont, lo, hi = self._ground_rows()
         ci = np.flatnonzero(cont)
         lin = np.linspace(lo[ci], hi[ci], npts, axis=1)          # the per-call form's abscissae, bit for bit (numpy.linspace per row)
         y = self.belief_rv_ground(hid[ci], lin).cpu().numpy() if ci.size else np.zeros((0, npts))
@@ -1178,103 +1156,65 @@ class HybridLBP(_ParticleSweep):
         area = (w[:, :-1] + w[:, 1:]).sum(axis=1) * (lin[:, 1] - lin[:, 0]) * 0.5
         return hid[ci], area, shift
 
-    def _batched_ok(self, ground_rv):
-        """can a per-variable query be answered from a batched pass?  (a stable partition: rows are clusters; an unstable one:
-        through the ground arrays of the arrays path)"""
-        if self.exact_queries:
-            return None
-        if self._stable_partition and getattr(ground_rv, 'cluster', None) in self.flat.var_index:
-            return 'cluster'
-        G = self._ground
-        if G is not None and ground_rv in G['flat'].var_index:
-            return 'ground'
-        return None
-
     def ground_map_fminbound_all(self, xtol=1e-5, maxfun=500):
         """MAP of every hidden GROUND variable the way ``HybridLBP.map`` finds it (HLBP:405-424: ``fminbound`` on
         ``-belief_rv_query``; discrete: first state with the largest belief), all in one launch; works on any partition.
         Returns (ground variable ids, MAP values)."""
-        hid, cont, lo, hi, _ = self._ground_rows()
+        hid = self._ground_rows()[0]
         ptr, edge, mult = self._ground_pairs()
         torch = _abi.require_gpu()
         hid_t = _abi.to_dev(hid.astype(np.int64))
-        deg = ptr[hid_t + 1] - ptr[hid_t]
-        qptr = torch.zeros(hid.size + 1, dtype=torch.int64, device=deg.device)
-        torch.cumsum(deg, 0, out=qptr[1:])
-        total = int(qptr[-1].item()) if hid.size else 0
-        owner = torch.repeat_interleave(torch.arange(hid.size, device=deg.device), deg, output_size=total)
-        idx = ptr[hid_t][owner] + (torch.arange(total, device=deg.device) - qptr[:-1][owner])
+        qptr, _, idx = pbp_query.expand_rows(ptr, hid_t)
         rows = self._ground['rvc'].to(torch.int32)[hid_t]
         x, _, _ = self._brent(rows, pairs=(qptr, edge[idx], mult[idx]), xtol=xtol, maxfun=maxfun)
         return hid, x.cpu().numpy()
 
-    def _cached_ground(self, what):
-        if what == 'map':
-            glob = self.map_mode == 'global'
-            what = 'map_global' if glob else 'map'
+    # ---- the per-variable calls (_ParticleSweep.map / probability / _belief): rows, batched tables and the normaliser -----------------
+    def _row_of(self, ground_rv):
+        """a stable partition: rows are clusters; an unstable one: the ground arrays of the arrays path, if the run kept them"""
+        if self.exact_queries:
+            return None, None
+        index = self.flat.var_index
+        if self._stable_partition and getattr(ground_rv, 'cluster', None) in index:
+            return 'cluster', index[ground_rv.cluster]
+        G = self._ground
+        if G is not None and ground_rv in G['flat'].var_index:
+            return 'ground', G['flat'].var_index[ground_rv]
+        return None, None
 
-            def fill():
+    def _batched_rows(self, how, what):
+        if how != 'ground':
+            return super()._batched_rows(how, what)
+        glob = self.map_mode == 'global'
+
+        def fill():                 # keyed by ground variable id: only the hidden ones have a row
+            if what == 'map':
                 ids, vals = self.ground_map_all() if glob else self.ground_map_fminbound_all()
                 return dict(zip(ids.tolist(), vals.tolist()))
-        else:
-            def fill():
-                ids, area, shift = self.ground_log_area_all(20)
-                return {int(v): (float(a), float(s_)) for v, a, s_ in zip(ids, area, shift)}
-        return self._query_cache('ground_' + what, fill)
+            ids, area, shift = (t.tolist() for t in self.ground_log_area_all(20))
+            return dict(zip(ids, area)), dict(zip(ids, shift))
+        return self._query_cache('ground_' + ('map_global' if what == 'map' and glob else what), fill)
 
-    def _area_of(self, rv):
-        """(z, shift) of the 20-point ``log_area`` over rv's domain (HLBP:361-365), batched when possible"""
-        how = self._batched_ok(rv)
-        if how == 'cluster':
-            zs, shifts = self._cached_area()
-            c = self.flat.var_index[rv.cluster]
-            return float(zs[c]), float(shifts[c])
-        if how == 'ground':
-            return self._cached_ground('area')[self._ground['flat'].var_index[rv]]
-        return self._log_area(self._var_of(rv), rv.domain.values[0], rv.domain.values[1], 20)
+    def _sig(self, rv):
+        """the key of ``query_cache``: ground variables with the same cluster and the same lifted edges share their beliefs"""
+        return rv.cluster, frozenset(self._ground_edges(rv).items())
+
+    def _normaliser(self, rv, inf_integral=False):
+        """(z, shift) of ``HybridLBP.belief`` (HLBP:361-365): the 20-point trapezoid over the domain, kept in ``query_cache``"""
+        sig = self._sig(rv)
+        if sig not in self.query_cache:
+            self.query_cache[sig] = self._area_of(rv)
+        return self.query_cache[sig]
+
+    def _state_beliefs(self, rv):
+        sig = self._sig(rv)
+        if sig not in self.query_cache:
+            self.query_cache[sig] = super()._state_beliefs(rv)
+        return self.query_cache[sig]
 
     def belief(self, x, rv, inf_integral=False):
         """HybridLBP.belief (HLBP:343-382): 20-point trapezoid normaliser, cached per cluster"""
-        if rv.value is not None:
-            return 1 if x == rv.value else 0
-        sig, v = (rv.cluster, frozenset(self._ground_edges(rv).items())), self._var_of(rv)
-        if rv.domain.continuous:
-            if sig not in self.query_cache:
-                self.query_cache[sig] = self._area_of(rv)
-            z, shift = self.query_cache[sig]
-            return e ** (float(self._belief_rv_points(v, [x])[0]) - shift - log(z))
-        if sig not in self.query_cache:
-            vals = rv.domain.values
-            b = dict(zip(vals, (e ** t for t in self._belief_rv_points(v, vals).tolist())))
-            self.message_normalization(b)
-            self.query_cache[sig] = b
-        return self.query_cache[sig][x]
-
-    def probability(self, a, b, rv):
-        if rv.value is None and rv.domain.continuous:
-            v = self._var_of(rv)
-            z, shift = self._area_of(rv)
-            num, _ = self._log_area(v, a, b, 5, shift)
-            return num / z
-        return None
-
-    def map(self, rv):
-        if rv.value is not None:
-            return rv.value
-        how = self._batched_ok(rv)
-        if how == 'cluster':
-            m = self._cached_map()[self.flat.var_index[rv.cluster]]
-            return float(m) if rv.domain.continuous else type(rv.domain.values[0])(m)
-        if how == 'ground':
-            m = self._cached_ground('map')[self._ground['flat'].var_index[rv]]
-            return float(m) if rv.domain.continuous else type(rv.domain.values[0])(m)
-        v = self._var_of(rv)
-        if rv.domain.continuous:
-            from scipy.optimize import fminbound
-            return fminbound(lambda val: -float(self._belief_rv_points(v, [val])[0]),
-                             rv.domain.values[0], rv.domain.values[1], disp=False)
-        vals = list(rv.domain.values)
-        return vals[int(np.argmax(self._belief_rv_points(v, vals)))]
+        return self._belief(x, rv)
 
 
 class _DeviceEngine:
@@ -1328,3 +1268,4 @@ class _DeviceEngine:
     @staticmethod
     def gather(t, index):
         return t.index_select(0, _abi.to_dev(np.asarray(index, dtype=np.int64))).contiguous()
+
