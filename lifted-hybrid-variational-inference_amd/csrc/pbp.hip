@@ -983,6 +983,66 @@ __device__ __forceinline__ double grid_sums32(double& g, double q, int lane) {
     }
     return fold_bit0(fold_bit1(fold_bit2(z[0], z[1]), fold_bit2(z[2], z[3]), (lane >> 1) & 1));
 }
+// ---- the same sums in quarter-wave lane groups (the heavy kernel) -------------------------------------------------------
+// Above every lane holds all 32 points of one partner, so five of the six folds move half of what is left.  Here
+// lane = 16 k + c (k = row of 16 lanes) walks the EIGHT points 8 k .. 8 k + 7 for the FOUR partners c, c + 16, c + 32, c + 48:
+// each partner lane forms its value at points 0, 8, 16, 24 (steps of q^4: the whole batch may span twice the guard's exponent
+// range, so q^8 itself can leave the double range where every product on the grid stays inside), a 4 x 4 transpose across
+// the rows (the swaps of fold_bit5 / fold_bit4 without the addition) sends each value to its row, and the ratios are
+// all-gathered across the rows once per edge.  Four partners are added in the lane; only the four folds inside the row are
+// left (bits 3, 2, 1, 0).  Point 8 k + r carries 2 k roundings of q^4 (three roundings itself) and r of q: at most one per
+// step, as in the sequential recurrence.
+__device__ __forceinline__ void swap_bit5(double& x, double& y) {     // bit 5 clear: (own x, partner's x); set: (partner's y, own y)
+    auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(x), __double2loint(y), false, false);
+    auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(x), __double2hiint(y), false, false);
+    x = __hiloint2double(hi[0], lo[0]); y = __hiloint2double(hi[1], lo[1]);
+}
+__device__ __forceinline__ void swap_bit4(double& x, double& y) {     // the same for bit 4
+    auto lo = __builtin_amdgcn_permlane16_swap(__double2loint(x), __double2loint(y), false, false);
+    auto hi = __builtin_amdgcn_permlane16_swap(__double2hiint(x), __double2hiint(y), false, false);
+    x = __hiloint2double(hi[0], lo[0]); y = __hiloint2double(hi[1], lo[1]);
+}
+// qr[k'] = the ratio of lane 16 k' + c, in every lane of column c
+__device__ __forceinline__ void grid_rows_ratios(double q, double (&qr)[4]) {
+    double lo = q, hi = q;
+    swap_bit5(lo, hi);                                  // lo: of row (own bit 4), hi: of row 2 + (own bit 4)
+    qr[0] = lo; qr[1] = lo; swap_bit4(qr[0], qr[1]);
+    qr[2] = hi; qr[3] = hi; swap_bit4(qr[2], qr[3]);
+}
+// the point whose sum a lane holds after the four folds inside its row
+__device__ __forceinline__ int grid_rows_owned_point(int lane) {
+    return 8 * (lane >> 4) + ((lane >> 3) & 1) + 2 * ((lane >> 2) & 1) + 4 * ((lane >> 1) & 1);
+}
+// g = this lane's G at the first of 32 consecutive grid points (advanced by 32 steps on return when `another` batch follows),
+// q4 = its ratio to the fourth power, qr = the gathered ratios
+__device__ __forceinline__ double grid_sums32_rows(double& g, const double (&qr)[4], double q4, bool another, int lane) {
+    double s[4];
+    s[0] = g;
+#pragma unroll
+    for (int m = 1; m < 4; ++m) s[m] = (s[m - 1] * q4) * q4;
+    if (another) g = (s[3] * q4) * q4;
+    swap_bit5(s[0], s[2]); swap_bit5(s[1], s[3]);       // s[k'] = partner 16 k' + c at point 8 k
+    swap_bit4(s[0], s[1]); swap_bit4(s[2], s[3]);
+    double w[2];
+#pragma unroll
+    for (int half = 0; half < 2; ++half) {
+        double u[2];
+#pragma unroll
+        for (int pr = 0; pr < 2; ++pr) {
+            const double v0 = (s[0] + s[1]) + (s[2] + s[3]);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) s[m] *= qr[m];
+            const double v1 = (s[0] + s[1]) + (s[2] + s[3]);
+            if (half + pr < 2) {
+#pragma unroll
+                for (int m = 0; m < 4; ++m) s[m] *= qr[m];
+            }
+            u[pr] = fold_bit3(v0, v1);                  // point 4 half + 2 pr + bit 3
+        }
+        w[half] = fold_bit2(u[0], u[1]);                // ... pr = bit 2
+    }
+    return fold_bit0(fold_bit1(w[0], w[1], (lane >> 1) & 1));   // ... half = bit 1
+}
 // The same reduce-scatter inside lane groups of W = 32 / 16 lanes (the few-particle kernel: lane = partner particle of its group's
 // edge).  W = 32: folds over bits 4..0, every lane ends with the sum of ONE of 32 consecutive points; W = 16: bits 3..0, two points
 // per lane (s0: points 0-15, s1: points 16-31 of the batch).  small_grid_point<W>(lane, k) names the point of sum k.
@@ -1234,9 +1294,12 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
             double gv = exp_core(fma(mine.b, d.gx0, mine.a), sh_tab);
             const double q = exp_core(mine.b * d.gh, sh_tab);
             // (forming the 'simple' rule's site moments in this epilogue would cost 10.67 -> 11.26 ms, profiles/r03_experiments.md)
+            double qr[4];
+            grid_rows_ratios(q, qr);
+            const double q2 = q * q, q4 = q2 * q2;
             for (int t0 = 0; t0 < d.T; t0 += 32) {
-                const double sum = grid_sums32(gv, q, lane);
-                const int t = t0 + grid_owned_point(lane);
+                const double sum = grid_sums32_rows(gv, qr, q4, t0 + 32 < d.T, lane);
+                const int t = t0 + grid_rows_owned_point(lane);
                 if (t < d.T && !(lane & 1)) {
                     const double xt = fma((double)t, d.gh, d.gx0);
                     row_store(out, (uint32_t)(n + t), sum > 0.0 ? fma(kconst * xt, xt, log_table(sum, sh_log)) : -700.0);
