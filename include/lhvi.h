@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 27 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 28 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -50,7 +50,8 @@ extern "C" {
                               * 24: lhvi_gm_kl, lhvi_gm_kl_ws_doubles, lhvi_gm_kl_host, LHVI_GMKL_MAX_PANELS;
                               * 25: lhvi_hg_energy, lhvi_hg_energy_host, lhvi_argmax_first, lhvi_argmax_first_ws_bytes, lhvi_argmax_first_host;
                               * 26: lhvi_pbp_kl, lhvi_gm_kl_fn_host;
-                              * 27: lhvi_exact_configs_at, lhvi_exact_config_at_host, lhvi_gibbs_rb_disc, lhvi_gibbs_rb_disc_host */
+                              * 27: lhvi_exact_configs_at, lhvi_exact_config_at_host, lhvi_gibbs_rb_disc, lhvi_gibbs_rb_disc_host;
+                              * 28: lhvi_gauss_chain_part_*, lhvi_gauss_chain_segments */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -875,6 +876,25 @@ int lhvi_gauss_chain_solve(int64_t B, int64_t M, int64_t n, const double* D, con
 /* the same on the HOST through the same code with one "lane" (host pointers); LHVI_E_NOT_PD when some system has a bad pivot */
 int lhvi_gauss_chain_host(int64_t B, int64_t M, int64_t n, const double* D, const double* O, const double* h, double* ws, double* mu,
                           double* var, double* cov, double* cross, double* logdet, int32_t* bad);
+/* The same systems solved in S segments along time (one level of nested dissection; csrc/gauss_chain_part.hip,
+ * docs/kernels_gauss_chain.md): S_eff = max(1, min(S, (M + 1) / 2)); S_eff - 1 single-block separators between S_eff interiors
+ * of (M - S_eff + 1) / S_eff blocks, the first (M - S_eff + 1) % S_eff of them one block longer.  lhvi_gauss_chain_segments
+ * writes the first and last block of every interior to first, last [S_eff] (either may be NULL) and returns S_eff (0 when
+ * M < 1 or S < 1); separator p is block last[p] + 1.  Three launches on the stream: one workgroup per (system, interior) solves
+ * the interior and its two spikes; the reduced chain of the separators is assembled and solved by the serial kernel; one
+ * workgroup per (system, interior) corrects the interior.  No atomics and a fixed order: with (M, n, S) fixed a system's
+ * bits do not depend on B, on its position or on cov / cross being NULL; they differ from the serial solve's and between
+ * different S.  S_eff == 1 is lhvi_gauss_chain_solve itself.  bad [B][2]: the bad pivot with the lowest block index among
+ * those met in the interiors and in the reduced chain (reported at its separator's block); the position may differ from
+ * the serial solve's, (-1, -1) holds for exactly the same systems.  ws: lhvi_gauss_chain_part_ws_doubles(B, M, n, S) doubles.
+ * Return codes as lhvi_gauss_chain_solve, and LHVI_E_ARG for S < 1. */
+size_t lhvi_gauss_chain_part_ws_doubles(int64_t B, int64_t M, int64_t n, int64_t S);
+int lhvi_gauss_chain_part_solve(int64_t B, int64_t M, int64_t n, int64_t S, const double* D, const double* O, const double* h,
+                                double* ws, double* mu, double* var, double* cov, double* cross, double* logdet, int32_t* bad,
+                                void* stream);
+int lhvi_gauss_chain_part_host(int64_t B, int64_t M, int64_t n, int64_t S, const double* D, const double* O, const double* h,
+                               double* ws, double* mu, double* var, double* cov, double* cross, double* logdet, int32_t* bad);
+int64_t lhvi_gauss_chain_segments(int64_t M, int64_t S, int64_t* first, int64_t* last);
 
 /* ---- Conditional queries on a fitted mixture belief (osi/mixture_beliefs.py:505-746, osi/utils.py:21-98; csrc/mixture.hip,
  * csrc/mixture.hpp) ---------------------------------------------------------------------------------------------------------

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 27            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 28            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -257,6 +257,10 @@ SIGNATURES = {
     'lhvi_gauss_chain_ws_doubles': (_sz, [_i64, _i64, _i64]),
     'lhvi_gauss_chain_solve': (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gauss_chain_host': (C.c_int, [_i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gauss_chain_part_ws_doubles': (_sz, [_i64, _i64, _i64, _i64]),
+    'lhvi_gauss_chain_part_solve': (C.c_int, [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gauss_chain_part_host': (C.c_int, [_i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_gauss_chain_segments': (_i64, [_i64, _i64, _vp, _vp]),
     'lhvi_mix_prepare': (C.c_int, [_i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_mix_condition_ws_doubles': (_sz, [_i64, _i32, _i32]),
     'lhvi_mix_condition': (C.c_int, [_MX, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -5,7 +5,9 @@ cannot hold: O(M n^3) work and O(M n^2) memory for M blocks of edge n instead of
 ``solve_block_tridiagonal(D, O, h)`` takes the blocks of ``J`` and ``h`` of one system or a batch; ``ExactGaussianChain(g, blocks)``
 is the solver-shaped class on a graph whose hidden variables are given in ordered blocks (``ExactGaussian``'s surface);
 ``lhvi.kalman.KalmanFilter.exact`` builds the blocks of a conditioned filter in closed form.  There is no CPU path: without a GPU
-the calls raise ``LhviError`` (``host_solve_block_tridiagonal`` runs the same code on the CPU for the tests).
+the calls raise ``LhviError`` (``host_solve_block_tridiagonal`` runs the same code on the CPU for the tests).  A system takes one
+workgroup; ``segments=`` on these calls cuts a long chain into segments solved in parallel (``csrc/gauss_chain_part.hip``,
+``segment_bounds``, ``auto_segments``).
 
 docs/kernels_gauss_chain.md: a system that is not positive definite raises ``ValueError`` naming the system, block and column;
 sizes beyond the free device memory raise ``MemoryError`` before a launch; blocks wider than 128 raise ``ValueError``.
@@ -26,20 +28,88 @@ def padded_edge(n):
     return 8 if n <= 8 else 16 if n <= 16 else 32 if n <= 32 else 64 if n <= 64 else 128
 
 
-def ws_doubles(B, M, n):
-    """``lhvi_gauss_chain_ws_doubles`` restated (checked against the library by the tests)"""
+def ws_doubles(B, M, n, segments=None):
+    """``lhvi_gauss_chain_ws_doubles`` and, with ``segments``, ``lhvi_gauss_chain_part_ws_doubles`` restated (checked against the
+    library by the tests)"""
     P = padded_edge(n)
     ld, nbuf = (P + 1 if P <= 64 else P), (0 if P < 64 else 5 if P == 64 else 6)
-    return B * (M * P * P + max(M - 1, 0) * P * P + M * P + nbuf * P * ld)
+    serial = lambda m: m * P * P + max(m - 1, 0) * P * P + m * P + nbuf * P * ld
+    S = 1 if segments is None or M < 1 else segment_bounds(M, _segments(segments, B, M, n))[0]
+    if S == 1:
+        return B * serial(M)
+    R, R1 = S - 1, max(S - 2, 0)
+    per_system = 4 * M * P * P + M * P + S * (nbuf * P * ld + 3 * n * n + 2 * n + 2)      # W, C, VL, VR, y; tiles and record per interior
+    reduced = 2 * (R + R1) * n * n + 3 * R * n + 2 + serial(R)                              # D~, O~, cov, cross; h~, mu, var; logdet, bad
+    return B * (per_system + reduced)
 
 
-def output_bytes(B, M, n, keep_cov=False):
-    """device bytes of a run: the inputs, the workspace (W_t, C_t, y_t of every block) and the results"""
+def output_bytes(B, M, n, keep_cov=False, segments=None):
+    """device bytes of a run: the inputs, the workspace (W_t, C_t, y_t of every block; with ``segments`` the spikes and the reduced
+    chain too) and the results"""
     mo = max(M - 1, 0)
-    doubles = B * (M * n * n + mo * n * n + M * n) + ws_doubles(B, M, n) + B * (2 * M * n + 1)
+    doubles = B * (M * n * n + mo * n * n + M * n) + ws_doubles(B, M, n, segments) + B * (2 * M * n + 1)
     if keep_cov:
         doubles += B * (M + mo) * n * n
     return 8 * doubles + 8 * B
+
+
+def segment_bounds(M, S):
+    """The partition of ``M`` blocks into ``S`` segments (``lhvi_gauss_chain_segments`` restated, checked against the library by the
+    tests): ``(S_eff, first [S_eff], last [S_eff])`` with ``S_eff = max(1, min(S, (M + 1) // 2))``.  ``S_eff - 1`` single-block
+    separators lie between ``S_eff`` interiors; the interiors share the other ``M - (S_eff - 1)`` blocks, the first
+    ``(M - S_eff + 1) % S_eff`` of them one block longer; interior p covers ``first[p] .. last[p]``, separator p is block
+    ``last[p] + 1``."""
+    M, S = int(M), int(S)
+    if S < 1:
+        raise ValueError('segments = %d: at least 1' % S)
+    S = max(1, min(S, (M + 1) // 2))
+    base, extra = divmod(M - (S - 1), S)
+    size = np.full(S, base, dtype=np.int64)
+    size[:extra] += 1
+    first = np.cumsum(size + 1) - (size + 1)
+    return S, first, first + size - 1
+
+
+# r: the cost of a block in stages 1 and 3 of the partitioned solve over a block of the serial solve.  Measured on the MI355X by
+# scripts/bench_gauss_chain.py --segments sweep (profiles/gauss_chain_part_bench.json): 2.16 on the long chain (n = 30, M = 19 999) at
+# S = 64, 128 and 256 and 2.10 on the batch of 64 at S = 4, each with at most one workgroup on a compute unit; 2.69 (S = 512) and
+# 2.87 (batch, S = 12) where two or three share one; 1.44 at the tree fixture's shape (n = 76, S = 4).  The operation count (a
+# serial block ~4 P^3 multiply-adds, the spikes 6 P^3, the correction 4 P^3) had suggested 4.
+SEGMENT_COST_RATIO = 2.2
+COMPUTE_UNITS = 256         # MI355X
+# workgroups of the segment kernel that r prices as running alone: one per compute unit, as the serial kernel's workgroup does
+# (the LDS would hold three at P = 32; the measured r grows by a quarter as soon as two share a compute unit)
+RESIDENT_PER_CU = 1
+# the spikes double the workspace, so 'auto' partitions only for a predicted gain of at least this factor
+AUTO_MIN_GAIN = 2.0
+
+
+def auto_segments(B, M, n):
+    """The segment count ``segments='auto'`` takes; a pure function of its arguments.  The time of a partitioned solve in serial
+    blocks is ``r ceil(M / S) + S``: stages 1 and 3 on the longest interior, then the reduced chain (``r = SEGMENT_COST_RATIO``).
+    Its relaxation ``r M / S + S`` is least at ``S = sqrt(r M)``; that value, rounded, is taken (it grows with M, which the
+    minimiser of the stepped cost does not), capped by ``(M + 1) // 2`` and so that ``B S`` stays within the resident workgroups
+    (``COMPUTE_UNITS * RESIDENT_PER_CU``).  1, the serial path, when ``M < 3``, when the batch alone fills the device, or when
+    the relaxed cost at that S is not ``AUTO_MIN_GAIN`` times below the serial M."""
+    B, M, n = int(B), int(M), int(n)
+    resident = COMPUTE_UNITS * RESIDENT_PER_CU
+    if B >= resident or M < 3:
+        return 1
+    S = min(int(round((SEGMENT_COST_RATIO * M) ** 0.5)), (M + 1) // 2, resident // max(B, 1))
+    if S < 2 or AUTO_MIN_GAIN * (SEGMENT_COST_RATIO * M / S + S) > M:
+        return 1
+    return S
+
+
+def _segments(segments, B, M, n):
+    """the S of a ``segments=`` argument (an integer or 'auto')"""
+    if isinstance(segments, str):
+        if segments != 'auto':
+            raise ValueError("segments must be None, an integer >= 1 or 'auto', got %r" % (segments,))
+        return auto_segments(B, M, n)
+    if int(segments) < 1:
+        raise ValueError('segments = %d: at least 1' % int(segments))
+    return int(segments)
 
 
 def _shapes(D, O, h):
@@ -73,13 +143,20 @@ def _pack(single, keep_cov, raise_on_bad, mu, var, logdet, cov, cross, bad):
     return out if raise_on_bad else out + (bad[0] if single else bad,)
 
 
-def solve_block_tridiagonal(D, O, h, keep_cov=False, raise_on_bad=True):
+def solve_block_tridiagonal(D, O, h, keep_cov=False, raise_on_bad=True, segments=None):
     """Exact moments of ``B`` Gaussian systems ``J x = h`` with block-tridiagonal ``J``: ``D [B][M][n][n]`` the diagonal blocks,
     ``O [B][M-1][n][n] = J[block t, block t + 1]`` (None when M = 1), ``h [B][M][n]``; arrays or device tensors, with or without
     the leading batch axis.  Returns ``mu [B][M][n]``, ``var [B][M][n]``, ``logdet [B]`` and, with ``keep_cov``, ``cov [B][M][n][n]``
     (Sig[t, t]) and ``cross [B][M-1][n][n]`` (Sig[t, t + 1]), of the kind that came in.  A system that is not positive definite
     raises ``ValueError``; with ``raise_on_bad=False`` a last value ``bad [B][2]`` (NumPy: block and column of the first bad pivot,
-    -1 where there is none) is returned instead and that system's results are meaningless."""
+    -1 where there is none) is returned instead and that system's results are meaningless.
+
+    ``segments``: None solves every system block after block in one workgroup.  An integer S, or 'auto' (``auto_segments``), cuts
+    each system into ``segment_bounds(M, S)`` segments solved in parallel and joined through a reduced chain of the separators
+    (docs/kernels_gauss_chain.md): for the single long chain that cannot fill the device otherwise.  With (M, n, S) fixed the
+    bits do not depend on B, on a system's position or on ``keep_cov``; they differ from the serial solve's and between different
+    S within the tolerance.  A system is flagged in ``bad`` exactly when the serial solve flags it, but the (block, column) is
+    that of the bad pivot with the lowest block among those the partitioned elimination meets, which may be another one."""
     torch = _abi._torch()
     tensors = torch.is_tensor(D)
     if not tensors:
@@ -92,10 +169,12 @@ def solve_block_tridiagonal(D, O, h, keep_cov=False, raise_on_bad=True):
         return _pack(single and B > 0, keep_cov, raise_on_bad, z(B, M, n), z(B, M, n), z(B), z(B, M, n, n), z(B, mo, n, n),
                      np.full((B, 2), -1, dtype=np.int32))
     torch = _abi.require_gpu()
-    need, free = output_bytes(B, M, n, keep_cov), int(torch.cuda.mem_get_info()[0])
+    S = None if segments is None else _segments(segments, B, M, n)
+    need, free = output_bytes(B, M, n, keep_cov, S), int(torch.cuda.mem_get_info()[0])
     if need > free:
-        raise MemoryError('the block-tridiagonal solve of %d systems of %d blocks of edge %d%s needs %d bytes of device memory, '
-                          '%d are free' % (B, M, n, ' with the covariances' if keep_cov else '', need, free))
+        raise MemoryError('the block-tridiagonal solve of %d systems of %d blocks of edge %d%s%s needs %d bytes of device memory, '
+                          '%d are free' % (B, M, n, ' with the covariances' if keep_cov else '',
+                                           '' if S is None else ' in %d segments' % S, need, free))
     f64 = torch.float64
 
     def dev(a):
@@ -104,13 +183,13 @@ def solve_block_tridiagonal(D, O, h, keep_cov=False, raise_on_bad=True):
         return a.to(device='cuda', dtype=f64).contiguous() if tensors else _abi.to_dev(np.ascontiguousarray(a))
     Dd, Od, hd = dev(D), dev(O), dev(h)
     l, new = _abi.lib(), lambda *s: torch.empty(*s, dtype=f64, device='cuda')
-    ws = new(int(l.lhvi_gauss_chain_ws_doubles(B, M, n)))
+    ws = new(int(l.lhvi_gauss_chain_ws_doubles(B, M, n) if S is None else l.lhvi_gauss_chain_part_ws_doubles(B, M, n, S)))
     mu, var, logdet = new(B, M, n), new(B, M, n), new(B)
     cov, cross = (new(B, M, n, n), new(B, mo, n, n)) if keep_cov else (None, None)
     bad = torch.empty(B, 2, dtype=torch.int32, device='cuda')
-    _abi.check(l.lhvi_gauss_chain_solve(B, M, n, _abi.ptr(Dd), _abi.ptr(Od) if mo else None, _abi.ptr(hd), _abi.ptr(ws), _abi.ptr(mu),
-                                        _abi.ptr(var), _abi.ptr(cov), _abi.ptr(cross) if mo else None, _abi.ptr(logdet),
-                                        _abi.ptr(bad), _abi.stream_ptr()))
+    args = (_abi.ptr(Dd), _abi.ptr(Od) if mo else None, _abi.ptr(hd), _abi.ptr(ws), _abi.ptr(mu), _abi.ptr(var), _abi.ptr(cov),
+            _abi.ptr(cross) if mo else None, _abi.ptr(logdet), _abi.ptr(bad), _abi.stream_ptr())
+    _abi.check(l.lhvi_gauss_chain_solve(B, M, n, *args) if S is None else l.lhvi_gauss_chain_part_solve(B, M, n, S, *args))
     bad = bad.cpu().numpy()
     if raise_on_bad and (bad[:, 0] >= 0).any():
         raise _bad_error(bad)
@@ -120,8 +199,9 @@ def solve_block_tridiagonal(D, O, h, keep_cov=False, raise_on_bad=True):
     return _pack(single, keep_cov, raise_on_bad, mu, var, logdet, cov, cross, bad)
 
 
-def host_solve_block_tridiagonal(D, O, h, keep_cov=False):
-    """the same on the CPU through the device's code (``lhvi_gauss_chain_host``), NumPy in and out; always returns ``bad`` last"""
+def host_solve_block_tridiagonal(D, O, h, keep_cov=False, segments=None):
+    """the same on the CPU through the device's code (``lhvi_gauss_chain_host``, with ``segments`` ``lhvi_gauss_chain_part_host``),
+    NumPy in and out; always returns ``bad`` last"""
     D, h = np.ascontiguousarray(D, dtype=np.float64), np.ascontiguousarray(h, dtype=np.float64)
     O = None if O is None else np.ascontiguousarray(O, dtype=np.float64)
     B, M, n, single = _shapes(D, O, h)
@@ -131,9 +211,11 @@ def host_solve_block_tridiagonal(D, O, h, keep_cov=False):
     bad = np.full((B, 2), -1, dtype=np.int32)
     if B and M and n:
         l = _abi.lib()
-        ws = np.zeros(int(l.lhvi_gauss_chain_ws_doubles(B, M, n)))
+        S = None if segments is None else _segments(segments, B, M, n)
+        ws = np.zeros(int(l.lhvi_gauss_chain_ws_doubles(B, M, n) if S is None else l.lhvi_gauss_chain_part_ws_doubles(B, M, n, S)))
         p = lambda a: None if a is None or a.size == 0 else a.ctypes.data
-        rc = l.lhvi_gauss_chain_host(B, M, n, p(D), p(O), p(h), p(ws), p(mu), p(var), p(cov), p(cross), p(logdet), p(bad))
+        args = (p(D), p(O), p(h), p(ws), p(mu), p(var), p(cov), p(cross), p(logdet), p(bad))
+        rc = l.lhvi_gauss_chain_host(B, M, n, *args) if S is None else l.lhvi_gauss_chain_part_host(B, M, n, S, *args)
         if rc not in (0, _abi.E_NOT_PD):
             _abi.check(rc)
     return _pack(single and B > 0, keep_cov, False, mu, var, logdet, cov, cross, bad)
@@ -217,8 +299,9 @@ class ExactGaussianChain(ExactGaussian):
         from .utils import get_joint_quadratic_params
         return get_joint_quadratic_params(self.factor_params, self.factor_scopes, self.N)
 
-    def run(self, keep_cov=False, host=False):
-        """``host=True`` runs the CPU twin instead of the device (the CPU suite's route)"""
+    def run(self, keep_cov=False, host=False, segments=None):
+        """``host=True`` runs the CPU twin instead of the device (the CPU suite's route); ``segments``: as
+        ``solve_block_tridiagonal`` takes it"""
         if not host:
             _abi.require_gpu()
         mean, var = np.array(self.flat.var_value, dtype=np.float64), np.zeros(self.flat.V)
@@ -227,8 +310,8 @@ class ExactGaussianChain(ExactGaussian):
             logdet, mub = 0.0, 0.0
         else:
             O = self.O if len(self.blocks) > 1 else None
-            out = host_solve_block_tridiagonal(self.D, O, self.h, keep_cov=keep_cov) if host else \
-                solve_block_tridiagonal(self.D, O, self.h, keep_cov=keep_cov, raise_on_bad=False)
+            out = host_solve_block_tridiagonal(self.D, O, self.h, keep_cov=keep_cov, segments=segments) if host else \
+                solve_block_tridiagonal(self.D, O, self.h, keep_cov=keep_cov, raise_on_bad=False, segments=segments)
             bad, out = out[-1], out[:-1]
             if bad[0] >= 0:
                 col = int(bad[1])

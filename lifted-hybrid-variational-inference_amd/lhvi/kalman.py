@@ -168,17 +168,19 @@ class KalmanFilter:
             h[0] += A.T @ data[:, 0] / q
         return D, O, h, float(-(yo * yo).sum() / (2 * r))
 
-    def exact(self, num_t_steps, data, keep_cov=False, host=False):
+    def exact(self, num_t_steps, data, keep_cov=False, host=False, segments=None):
         """Exact smoothed marginals of the conditioned filter on the device: ``mu [T][n]``, ``var [T][n]``, ``logZ`` (and, with
         ``keep_cov``, ``cov [T-1][n][n]`` and ``cross [T-2][n][n]`` of the hidden steps); row 0 is the evidence with variance 0.
-        ``host=True``: the CPU twin (the CPU suite's route)."""
-        out = exact_batch([self], num_t_steps, data, keep_cov=keep_cov, host=host)
+        ``host=True``: the CPU twin (the CPU suite's route).  ``segments``: None, an integer or 'auto', the partitioned solve of
+        ``gauss_chain.solve_block_tridiagonal`` for one long chain."""
+        out = exact_batch([self], num_t_steps, data, keep_cov=keep_cov, host=host, segments=segments)
         return tuple(o[0] for o in out)
 
 
-def exact_batch(filters, num_t_steps, data, keep_cov=False, host=False):
+def exact_batch(filters, num_t_steps, data, keep_cov=False, host=False, segments=None):
     """``KalmanFilter.exact`` for several filters of equal n on the same data in one launch (the demos' loop over parameter sets):
-    ``mu [B][T][n]``, ``var [B][T][n]``, ``logZ [B]`` (and ``cov``, ``cross`` with ``keep_cov``)"""
+    ``mu [B][T][n]``, ``var [B][T][n]``, ``logZ [B]`` (and ``cov``, ``cross`` with ``keep_cov``); ``segments`` is passed on to the
+    solver"""
     from .gauss_chain import LOG_2PI, _bad_error, host_solve_block_tridiagonal, solve_block_tridiagonal
     data = np.asarray(data, dtype=np.float64)
     T, n = int(num_t_steps), data.shape[0]
@@ -190,12 +192,12 @@ def exact_batch(filters, num_t_steps, data, keep_cov=False, host=False):
     D, h = np.stack([p[0] for p in parts]), np.stack([p[2] for p in parts])
     O = np.stack([p[1] for p in parts]) if M > 1 else None
     if host:
-        out = host_solve_block_tridiagonal(D, O, h, keep_cov=keep_cov)
+        out = host_solve_block_tridiagonal(D, O, h, keep_cov=keep_cov, segments=segments)
         if (out[-1][:, 0] >= 0).any():
             raise _bad_error(out[-1], 'filter')
         out = out[:-1]
     else:
-        out = solve_block_tridiagonal(D, O, h, keep_cov=keep_cov)
+        out = solve_block_tridiagonal(D, O, h, keep_cov=keep_cov, segments=segments)
     mu, var = np.zeros((B, T, n)), np.zeros((B, T, n))
     mu[:, 0], mu[:, 1:], var[:, 1:] = data[:, 0], out[0], out[1]
     const = np.array([p[3] for p in parts])

@@ -9,7 +9,15 @@ without the covariances; 2 warm-up runs, 5 repeats, median and min / max.  The d
 and their host set-up is long, so they are timed on the first ``--dense-systems`` systems of a case (default 1) and reported
 per system.
 
+With ``--segments`` the partitioned solve (``lhvi_gauss_chain_part_solve``) is timed next to the serial one in the same process, the
+dense solver and GaBP are left out, and the result goes to profiles/gauss_chain_part_bench.json.  ``--segments sweep`` takes each
+case's own list (the long chain: 64, 128, 256, 512), ``--segments 64,128`` that list for every case.  Per S: the solve with and
+without the covariances, a serial solve of S - 1 blocks (the reduced chain's share), the distance from the serial moments, and
+r = (t_part - t_reduced) / (ceil(M / S) t_serial / M): the cost of a block in stages 1 and 3 over a serial block
+(``gauss_chain.SEGMENT_COST_RATIO``).
+
 Usage: python scripts/bench_gauss_chain.py [--out profiles/gauss_chain_bench.json] [--cases 0,1,2] [--dense-systems 1]
+                                           [--segments sweep|S,S,...]
 """
 import argparse
 import json
@@ -22,9 +30,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd'))
 
 WARMUP, REPEATS = 2, 5
-CASES = [dict(name='single long chain', B=1, n=30, M=19999, dense=False),
-         dict(name='batch of short chains', B=64, n=30, M=199, dense=True),
-         dict(name='tree fixture shape', B=5, n=76, M=19, dense=True)]
+CASES = [dict(name='single long chain', B=1, n=30, M=19999, dense=False, segments=(64, 128, 256, 512)),
+         dict(name='batch of short chains', B=64, n=30, M=199, dense=True, segments=(4, 12)),
+         dict(name='tree fixture shape', B=5, n=76, M=19, dense=True, segments=(4, 10))]
 
 
 def models(B, n, M, seed=0):
@@ -60,7 +68,7 @@ def timed(fn):
     return stats(ms)
 
 
-def chain_times(kfs, data, M, n):
+def chain_times(kfs, data, M, n, segments=()):
     import torch
     from lhvi import _abi
     B = len(kfs)
@@ -78,7 +86,35 @@ def chain_times(kfs, data, M, n):
     out = {'solve_ms': timed(lambda: run(False)), 'solve_keep_cov_ms': timed(lambda: run(True)),
            'workspace_bytes': int(ws.numel()) * 8}
     assert int(bad.max().item()) == -1
-    return out, mu.cpu().numpy(), var.cpu().numpy()
+    smu, svar = mu.cpu().numpy(), var.cpu().numpy()
+    if segments:
+        from lhvi import gauss_chain
+        out['auto_segments'] = gauss_chain.auto_segments(B, M, n)
+        out['partitioned'] = []
+    for S in segments:
+        pws = new(int(l.lhvi_gauss_chain_part_ws_doubles(B, M, n, S)))
+
+        def part(keep):
+            _abi.check(l.lhvi_gauss_chain_part_solve(B, M, n, S, _abi.ptr(D), _abi.ptr(O), _abi.ptr(h), _abi.ptr(pws), _abi.ptr(mu),
+                                                     _abi.ptr(var), _abi.ptr(cov) if keep else None, _abi.ptr(cross) if keep else None,
+                                                     _abi.ptr(logdet), _abi.ptr(bad), _abi.stream_ptr()))
+        Se = int(gauss_chain.segment_bounds(M, S)[0])
+        row = {'S': S, 'S_eff': Se, 'solve_ms': timed(lambda: part(False)), 'solve_keep_cov_ms': timed(lambda: part(True)),
+               'workspace_bytes': int(pws.numel()) * 8}
+        assert int(bad.max().item()) == -1
+        row['vs_serial_max_dmu'] = float(np.abs(mu.cpu().numpy() - smu).max())
+        row['vs_serial_max_rel_dvar'] = float(np.abs(var.cpu().numpy() / svar - 1).max())
+        if Se > 1:                                     # the reduced chain's share: a serial solve of S_eff - 1 blocks, covariances kept
+            R = Se - 1
+            row['reduced_chain_ms'] = timed(lambda: _abi.check(l.lhvi_gauss_chain_solve(
+                B, R, n, _abi.ptr(D), _abi.ptr(O), _abi.ptr(h), _abi.ptr(ws), _abi.ptr(mu), _abi.ptr(var), _abi.ptr(cov),
+                _abi.ptr(cross), _abi.ptr(logdet), _abi.ptr(bad), _abi.stream_ptr())))
+            per_block = out['solve_ms']['median'] / M
+            row['r'] = (row['solve_ms']['median'] - row['reduced_chain_ms']['median']) / (-(-M // Se) * per_block)
+        row['speedup'] = out['solve_ms']['median'] / row['solve_ms']['median']
+        out['partitioned'].append(row)
+        del pws
+    return out, smu, svar
 
 
 def dense_and_gabp(kf, data, M, mu, var):
@@ -108,18 +144,22 @@ def dense_and_gabp(kf, data, M, mu, var):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('--out', default=os.path.join(ROOT, 'profiles', 'gauss_chain_bench.json'))
+    ap.add_argument('--out', default=None)
     ap.add_argument('--cases', default='0,1,2')
     ap.add_argument('--dense-systems', type=int, default=1)
+    ap.add_argument('--segments', default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, 'profiles', 'gauss_chain_part_bench.json' if args.segments else 'gauss_chain_bench.json')
     import torch
     result = {'device': torch.cuda.get_device_name(0), 'warmup': WARMUP, 'repeats': REPEATS, 'cases': []}
     for c in (CASES[int(i)] for i in args.cases.split(',')):
         kfs, data = models(c['B'], c['n'], c['M'])
         row = {k: c[k] for k in ('name', 'B', 'n', 'M')}
-        times, mu, var = chain_times(kfs, data, c['M'], c['n'])
+        segments = () if not args.segments else c['segments'] if args.segments == 'sweep' else tuple(int(x) for x in args.segments.split(','))
+        times, mu, var = chain_times(kfs, data, c['M'], c['n'], segments)
         row.update(times)
-        if c['dense']:
+        if c['dense'] and not segments:
             row['per_system'] = [dense_and_gabp(kfs[b], data, c['M'], mu[b], var[b]) for b in range(min(args.dense_systems, c['B']))]
         print(json.dumps(row), flush=True)
         result['cases'].append(row)
