@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 28 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 29 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -51,7 +51,8 @@ extern "C" {
                               * 25: lhvi_hg_energy, lhvi_hg_energy_host, lhvi_argmax_first, lhvi_argmax_first_ws_bytes, lhvi_argmax_first_host;
                               * 26: lhvi_pbp_kl, lhvi_gm_kl_fn_host;
                               * 27: lhvi_exact_configs_at, lhvi_exact_config_at_host, lhvi_gibbs_rb_disc, lhvi_gibbs_rb_disc_host;
-                              * 28: lhvi_gauss_chain_part_*, lhvi_gauss_chain_segments */
+                              * 28: lhvi_gauss_chain_part_*, lhvi_gauss_chain_segments;
+                              * 29: lhvi_ais_*, LHVI_AIS_REDUCE_OUT, LHVI_AIS_REDUCE_WS */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -820,6 +821,42 @@ int lhvi_gibbs_rb_disc(const lhvi_gibbs_t* m, int64_t chains, int32_t s_begin, i
  * m->table_scratch is ignored.  LHVI_E_ARG for a digit outside its range. */
 int lhvi_gibbs_rb_disc_host(const lhvi_gibbs_t* m, int32_t s_begin, int32_t s_end, const int32_t* disc, const double* cont,
                             double* prob_sum);
+
+/* ---- Annealed importance sampling for log Z of a hybrid Gaussian MRF (csrc/ais.hip, csrc/ais.hpp; docs/kernels_ais.md) ---------
+ * Many independent annealing runs over the model of lhvi_gibbs_t along f_beta = p~^beta f0^(1 - beta), f0 = exp(-tau0 / 2
+ * |x_c - mu0|^2) with x_d uniform, for a schedule betas [T + 1] (betas[0] = 0 <= ... <= betas[T] = 1: the caller checks).  x_c
+ * is integrated out in closed form: step t adds log m_{betas[t+1]}(x_d) - log m_{betas[t]}(x_d) to the chain's log weight, with
+ * log m_beta(x_d) = beta tables + c_beta + Nc / 2 log 2 pi - 1/2 log det J_beta + 1/2 |L_beta^-1 b_beta|^2, then (unless
+ * t = T - 1) makes one block Gibbs transition at betas[t + 1]: x_c from the factor just computed, the reduced tables at x_c,
+ * m->disc_block_its sweeps over x_d with the log probabilities multiplied by beta.  log Z0 = sum log dstates + Nc / 2
+ * log(2 pi / tau0); log Z is estimated by log Z0 + log mean exp(logw).  m->num_burnin and m->num_samples are not read.
+ * The draw of counter (chain, step, index, tag) comes from Philox4x32-10 keyed by m->seed, under tags of its own. */
+#define LHVI_AIS_REDUCE_OUT 9
+#define LHVI_AIS_REDUCE_WS 8192
+/* LDS of one workgroup of lhvi_ais_run (one wavefront, 64 / lanes chains): the workspace of lhvi_gibbs_lds_bytes plus mu0.
+ * 0 for an invalid `lanes`. */
+size_t lhvi_ais_lds_bytes(int32_t Nc, int32_t Nd, int32_t table_doubles, int32_t lanes);
+/* steps [t_begin, t_end) of every chain, 0 <= t_begin <= t_end <= T.  x_d [chains][Nd] (int32, from lhvi_gibbs_init before the
+ * first call) and logw [chains] (zeroed before the first call) are in / out, so a run is any number of calls.  betas [T + 1],
+ * mu0 [Nc]: device arrays; tau0 > 0.  lanes: lanes per chain, a power of two <= 64; a chain's x_d and logw depend neither on
+ * it, nor on `chains`, nor on the split into calls.  z [T][chains][Nc], u [T][chains][disc_block_its][Nd]: injected draws (rows
+ * by step; the transition of step t reads row t), or NULL for the Philox stream.
+ * bad [1]: the caller sets it to UINT64_MAX; a chain that meets a J_beta that is not positive definite lowers it to
+ * (chain << 32 | step) (atomic min) and keeps its x_d and logw of that moment.
+ * LHVI_E_UNSUPPORTED: Nc > LHVI_EXACT_MAX_NC or more than 64 KiB of LDS. */
+int lhvi_ais_run(const lhvi_gibbs_t* m, int64_t chains, int32_t T, const double* betas, int32_t t_begin, int32_t t_end,
+                 int32_t lanes, double tau0, const double* mu0, int32_t* x_d, double* logw, const double* z, const double* u,
+                 uint64_t* bad, void* stream);
+/* out [LHVI_AIS_REDUCE_OUT] over logw [chains], every sum in a fixed order (two stages, no floating-point atomics), with
+ * mx = max logw and d = logw - mx: log sum exp(logw), log sum exp(2 logw), sum logw, sum logw^2, mx, sum exp(d), sum exp(2 d),
+ * sum d, sum d^2.  ws: LHVI_AIS_REDUCE_WS doubles. */
+int lhvi_ais_reduce(int64_t chains, const double* logw, double* out, double* ws, void* stream);
+/* steps [t_begin, t_end) of one chain on the HOST through the device's code (csrc/ais.hpp); every pointer of m and every
+ * argument is host memory; x_d [Nd] and logw [1] are in / out.  z [T][Nc], u [T][its][Nd]: this chain's injected draws, or both
+ * NULL for the Philox stream of chain `chain`.  m->table_scratch is ignored.  LHVI_E_NOT_PD when a J_beta is not positive
+ * definite (x_d then holds the state). */
+int lhvi_ais_chain_host(const lhvi_gibbs_t* m, int64_t chain, int32_t T, const double* betas, int32_t t_begin, int32_t t_end,
+                        double tau0, const double* mu0, int32_t* x_d, double* logw, const double* z, const double* u);
 
 /* ---- Exact Gaussian-MRF marginals: dense blocked fp64 Cholesky (osi/utils.py get_gaussian_mean_params_from_quadratic_params;
  * csrc/gauss_exact.hip, csrc/gauss_exact.hpp) ----------------------------------------------------------------------------------

@@ -44,11 +44,12 @@ struct Draws {
     const double *z, *u;
     int64_t chains, chain;
     int Nc, Nd, its;
+    uint32_t tag_normal = TAG_NORMAL, tag_uniform = TAG_UNIFORM;   // the annealed sampler (csrc/ais.hpp) draws under tags of its own
     // z_r of iteration it: Box-Muller on the pair (r & ~1, r | 1) of counter draw r / 2
     LHVI_HD double normal(int it, int r) const {
         if (z) return z[((int64_t)it * chains + chain) * Nc + r];
         double u0, u1;
-        uniform2(seed, (uint32_t)chain, (uint32_t)it, (uint32_t)(r >> 1), TAG_NORMAL, u0, u1);
+        uniform2(seed, (uint32_t)chain, (uint32_t)it, (uint32_t)(r >> 1), tag_normal, u0, u1);
         const double rad = sqrt(-2.0 * log(1.0 - u0)), ang = 6.283185307179586 * u1;
         return (r & 1) ? rad * sin(ang) : rad * cos(ang);
     }
@@ -56,7 +57,7 @@ struct Draws {
     LHVI_HD double uniform(int it, int idx) const {
         if (u) return u[((int64_t)it * chains + chain) * ((int64_t)its * Nd) + idx];
         double u0, u1;
-        uniform2(seed, (uint32_t)chain, (uint32_t)it, (uint32_t)(idx >> 1), TAG_UNIFORM, u0, u1);
+        uniform2(seed, (uint32_t)chain, (uint32_t)it, (uint32_t)(idx >> 1), tag_uniform, u0, u1);
         return (idx & 1) ? u1 : u0;
     }
 };
@@ -147,6 +148,39 @@ LHVI_HD void cond_lprobs(const lhvi_gibbs_t& g, int n, const int32_t* dig, const
     }
 }
 
+// The two triangular solves of the Gaussian block, shared with the annealed sampler (csrc/ais.hpp); their floating-point
+// operations are iteration()'s own.
+//
+// forward_solve: y = L^-1 b, one column per step: row r subtracts L[r][j] y[j] for j = 0 .. r - 1 in this order.  Every y is
+// final and visible to all lanes on return.
+template <class Ctx>
+LHVI_HD void forward_solve(int Nc, const Workspace& w, const Ctx& ctx) {
+    const int ld = exact::ld_of(Nc);
+    for (int r = ctx.lane; r < Nc; r += ctx.lanes) w.y[r] = w.b[r];
+    for (int j = 0; j < Nc; ++j) {
+        for (int r = ctx.lane; r < Nc; r += ctx.lanes)
+            if (r == j) w.y[j] *= w.dinv[j];
+        ctx.sync();
+        for (int r = ctx.lane; r < Nc; r += ctx.lanes)
+            if (r > j) w.y[r] -= w.mat[r * ld + j] * w.y[j];
+    }
+}
+
+// back_solve: x_c = L^-T (y + z) with z the normals of iteration `it`: row r subtracts L[i][r] x[i] for i = Nc - 1 .. r + 1 in
+// this order.  Every x_c is final and visible to all lanes on return.
+template <class Ctx>
+LHVI_HD void back_solve(int Nc, int it, const Draws& dr, const Workspace& w, const Ctx& ctx) {
+    const int ld = exact::ld_of(Nc);
+    for (int r = ctx.lane; r < Nc; r += ctx.lanes) w.xc[r] = w.y[r] + dr.normal(it, r);
+    for (int i = Nc - 1; i >= 0; --i) {
+        for (int r = ctx.lane; r < Nc; r += ctx.lanes)
+            if (r == i) w.xc[i] *= w.dinv[i];
+        ctx.sync();
+        for (int r = ctx.lane; r < Nc; r += ctx.lanes)
+            if (r < i) w.xc[r] -= w.mat[i * ld + r] * w.xc[i];
+    }
+}
+
 // One outer iteration `it` of a chain whose x_d is in w.dig.  dead: the chain met a J that is not positive definite; it keeps
 // its x_d from then on and stores nothing.  Returns 1 when this iteration's J is not positive definite (and sets dead), the
 // same value in every lane.
@@ -154,7 +188,7 @@ template <class Ctx>
 LHVI_HD int iteration(const lhvi_gibbs_t& g, int it, const Draws& dr, const Workspace& w, const Ctx& ctx, bool& dead,
                       const Out& o) {
     const lhvi_exact_t& m = g.ex;
-    const int Nc = m.Nc, Nd = m.Nd, ld = exact::ld_of(Nc);
+    const int Nc = m.Nc, Nd = m.Nd;
     int bad = 0;
     if (Nc) {
         // 1. x_c | x_d (:217-233): J = L L^T, y = L^-1 b, x_c = L^-T (y + z) = mu + L^-T z
@@ -164,24 +198,8 @@ LHVI_HD int iteration(const lhvi_gibbs_t& g, int it, const Draws& dr, const Work
         exact::form_J(Nc, w.mat, ctx);
         bad = exact::cholesky(Nc, w.mat, w.ldiag, w.dinv, ctx, logdet);
         dead = dead || bad;
-        // forward substitution, one column per step: row r subtracts L[r][j] y[j] for j = 0 .. r - 1 in this order
-        for (int r = ctx.lane; r < Nc; r += ctx.lanes) w.y[r] = w.b[r];
-        for (int j = 0; j < Nc; ++j) {
-            for (int r = ctx.lane; r < Nc; r += ctx.lanes)
-                if (r == j) w.y[j] *= w.dinv[j];
-            ctx.sync();
-            for (int r = ctx.lane; r < Nc; r += ctx.lanes)
-                if (r > j) w.y[r] -= w.mat[r * ld + j] * w.y[j];
-        }
-        // back substitution: row r subtracts L[i][r] x[i] for i = Nc - 1 .. r + 1 in this order
-        for (int r = ctx.lane; r < Nc; r += ctx.lanes) w.xc[r] = w.y[r] + dr.normal(it, r);
-        for (int i = Nc - 1; i >= 0; --i) {
-            for (int r = ctx.lane; r < Nc; r += ctx.lanes)
-                if (r == i) w.xc[i] *= w.dinv[i];
-            ctx.sync();
-            for (int r = ctx.lane; r < Nc; r += ctx.lanes)
-                if (r < i) w.xc[r] -= w.mat[i * ld + r] * w.xc[i];
-        }
+        forward_solve(Nc, w, ctx);
+        back_solve(Nc, it, dr, w, ctx);
     }
     // 2. the reduced tables at x_c, once per outer iteration
     reduced_tables(g, w.xc, w.tab, ctx);

@@ -17,7 +17,9 @@ mixtures of all continuous variables to the kept samples on the device (``fit_ma
 Beyond the reference (docs/kernels_gibbs_rb.md): ``GibbsHybridGaussian.rb_marginals()`` / ``rb_disc_marginals()`` /
 ``rb_moments()`` and ``rao_blackwell=True`` of ``map`` / ``map_all`` / ``belief`` average the exact conditionals
 ``p(x_c | x_d)`` and ``p(x_n | x_d,-n, x_c)`` over the kept samples (``csrc/gibbs_rb.hip``); ``rb_disc_host`` runs one chain of
-the latter through the device's code on the CPU.
+the latter through the device's code on the CPU.  ``GibbsHybridGaussian.log_partition()``,
+``HybridGaussianSampler.log_partition()`` and ``ais_log_partition`` estimate ``log Z`` by annealed importance sampling
+(``csrc/ais.hip``, ``lhvi/ais.py``, docs/kernels_ais.md): the ``obj = -logZ`` the reference's Gibbs baseline leaves as a TODO.
 """
 from __future__ import annotations
 
@@ -302,6 +304,28 @@ def block_gibbs_sample(factors, Vd, Vc, num_burnin, num_samples, init_x_d=None, 
     return disc, cont
 
 
+_LOG_PARTITION_DOC = """Annealed importance sampling (Neal 2001) along ``p~^beta f0^(1 - beta)`` from the base
+    ``f0 = exp(-base_prec / 2 |x_c - base_mean|^2)`` (x_d uniform) with x_c integrated out in closed form (docs/kernels_ais.md):
+    ``chains`` independent runs of ``steps`` steps (``betas``: a schedule of its own from 0 to 1, never decreasing; default
+    ``linspace(0, 1, steps + 1)``), each step followed by one block Gibbs transition with ``disc_block_its`` sweeps.  Returns a
+    record: ``logZ`` (log of the mean weight), ``stderr`` (delta method), ``ess`` (effective sample fraction), ``lower``
+    (log Z0 + mean log weight: its expectation is at most log Z, the number to hold against an ELBO) with ``lower_stderr``,
+    ``obj`` = -logZ, and the device tensors ``log_weights`` [chains] and ``x_d`` [chains, Nd] (the final states).  A poor base
+    raises the variance of the weights and never biases the estimate of Z."""
+
+
+def ais_log_partition(factors, Vd, Vc, chains=4096, steps=256, betas=None, disc_block_its=1, seed=0, base_mean=None,
+                      base_prec=None, lanes=None, steps_per_launch=None):
+    """``log Z`` of the hybrid Gaussian MRF that ``block_gibbs_sample`` samples (same reading of the factors).  Base mean 0 and
+    precision 1 unless given."""
+    from . import ais
+    gm = GibbsModel(flatten_factors(factors, [rv.dstates for rv in Vd], len(Vc)))
+    return ais.log_partition(gm, chains, steps, betas, disc_block_its, seed, base_mean, base_prec, lanes, steps_per_launch)
+
+
+ais_log_partition.__doc__ += '\n\n    ' + _LOG_PARTITION_DOC
+
+
 def get_disc_marg_table_from_samples(samples, dstates):
     """``sampling_utils.get_disc_marg_table_from_samples``: the joint relative frequencies [v1..vN] of samples [S, N]"""
     samples = np.asarray(samples)
@@ -359,6 +383,20 @@ class HybridGaussianSampler:
         w, mu, var = fit_scalar_gm_from_samples(x, num_gm_components_for_crv)
         return get_rv_marg_map_from_bn_params(w, mu[:, None], var[:, None, None], {}, {rv: 0}, rv)
 
+    def log_partition(self, chains=4096, steps=256, betas=None, disc_block_its=1, seed=0, base_mean=None, base_prec=None,
+                      lanes=None, steps_per_launch=None):
+        """``ais_log_partition`` of the sampler's model (the reference leaves ``obj = -logZ`` of its Gibbs baseline as a TODO,
+        ``osi/hybrid_mln_experiment.py:304``).  After ``block_gibbs_sample`` the base defaults to the sample means and the
+        reciprocal of the mean sample variance of ``cont_samples``; before it, to mean 0 and precision 1."""
+        cont = getattr(self, 'cont_samples', None)
+        if cont is not None and len(self.Vc) and len(cont) > 1:
+            cont = np.asarray(cont, dtype=np.float64)
+            base_mean = cont.mean(axis=0) if base_mean is None else base_mean
+            base_prec = 1.0 / float(cont.var(axis=0).mean()) if base_prec is None else base_prec
+        return ais_log_partition(self.factors, self.Vd, self.Vc, chains, steps, betas, disc_block_its, seed, base_mean, base_prec,
+                                 lanes, steps_per_launch)
+
+    log_partition.__doc__ += '\n\n        ' + _LOG_PARTITION_DOC
 
     def joint_map(self):
         """the sample of largest joint log potential among ``disc_samples`` / ``cont_samples`` (the reference leaves this as a
@@ -629,6 +667,25 @@ class GibbsHybridGaussian:
         flat = int(np.dot(np.asarray(config, dtype=object), ex.dstride.astype(object))) if ex.M else None
         return joint_map_dict(self, config, flat, r.cont[chain, sample].cpu().numpy(), float(value.item()), chain=chain,
                               sample=sample)
+
+    def log_partition(self, chains=4096, steps=256, betas=None, disc_block_its=1, seed=0, base_mean=None, base_prec=None,
+                      lanes=None, steps_per_launch=None):
+        """``log Z`` of the model with the evidence in place (``log_const`` included): comparable with
+        ``ExactHybridGaussian.logZ`` on the same evidence, and ``obj`` = -logZ is the column the reference's Gibbs baseline
+        leaves empty.  Needs no ``run()``; after one, the base defaults to ``moments()``: the sample means and the reciprocal of
+        the mean marginal variance.  Before it, to mean 0 and precision 1."""
+        from . import ais
+        Nc = len(self.Vc)
+        if self._run is not None and Nc and (base_mean is None or base_prec is None):
+            mo = self.moments()
+            var = float(np.diag(mo.cov).mean())
+            base_mean = mo.mean if base_mean is None else base_mean
+            if base_prec is None and var > 0.0 and np.isfinite(var):
+                base_prec = 1.0 / var
+        return ais.log_partition(self.model, chains, steps, betas, disc_block_its, seed, base_mean, base_prec, lanes,
+                                 steps_per_launch, log_const=self.log_const)
+
+    log_partition.__doc__ += '\n\n        ' + _LOG_PARTITION_DOC
 
     def _bds(self):
         return np.array([[rv.domain.values[0] for rv in self.Vc], [rv.domain.values[1] for rv in self.Vc]], dtype=np.float64)
