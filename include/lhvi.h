@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 29 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 30 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -52,7 +52,8 @@ extern "C" {
                               * 26: lhvi_pbp_kl, lhvi_gm_kl_fn_host;
                               * 27: lhvi_exact_configs_at, lhvi_exact_config_at_host, lhvi_gibbs_rb_disc, lhvi_gibbs_rb_disc_host;
                               * 28: lhvi_gauss_chain_part_*, lhvi_gauss_chain_segments;
-                              * 29: lhvi_ais_*, LHVI_AIS_REDUCE_OUT, LHVI_AIS_REDUCE_WS */
+                              * 29: lhvi_ais_*, LHVI_AIS_REDUCE_OUT, LHVI_AIS_REDUCE_WS;
+                              * 30: lhvi_pt_* */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -857,6 +858,44 @@ int lhvi_ais_reduce(int64_t chains, const double* logw, double* out, double* ws,
  * definite (x_d then holds the state). */
 int lhvi_ais_chain_host(const lhvi_gibbs_t* m, int64_t chain, int32_t T, const double* betas, int32_t t_begin, int32_t t_end,
                         double tau0, const double* mu0, int32_t* x_d, double* logw, const double* z, const double* u);
+
+/* ---- Parallel tempering for the block Gibbs sampler (csrc/pt.hip, csrc/pt.hpp; docs/kernels_pt.md) ------------------------------
+ * `ladders` independent ladders of R replicas over the model of lhvi_gibbs_t.  Replica r samples f_betas[r] on the path of
+ * lhvi_ais_run (betas [R], 0 <= betas[0] <= ... <= betas[R - 1] = 1: the caller checks).  Iteration `it` of a ladder: every
+ * replica makes one block Gibbs transition at its beta (at beta = 1 the operations of lhvi_gibbs_run); from iteration
+ * m->num_burnin on replica R - 1 stores its sample and adds to the accumulators like lhvi_gibbs_run, `chains` read as `ladders`;
+ * then, when swap_every > 0 and (it + 1) % swap_every == 0, swap round s = it / swap_every proposes to exchange the digits of the
+ * pairs (r, r + 1), r = s mod 2, s mod 2 + 2, ...: accepted iff log(1 - u) <= log m_{b_r}(d_{r+1}) + log m_{b_{r+1}}(d_r)
+ * - log m_{b_r}(d_r) - log m_{b_{r+1}}(d_{r+1}) with log m_beta the collapsed mass of lhvi_ais_run.  The draws come from
+ * Philox4x32-10 keyed by m->seed: normals and sweep uniforms of counter (ladder * R + r, it, index, tag), the swap uniform of
+ * pair r of counter (ladder, it, r, tag), under tags of their own. */
+/* LDS of one workgroup of lhvi_pt_run: per ladder R workspaces of lhvi_ais_run's chains plus the exchange slots; a workgroup is
+ * R * lanes threads rounded up to whole wavefronts and holds 64 / (R * lanes) ladders when R * lanes <= 32.  0 for an invalid
+ * `lanes`, R < 1 or R * lanes > 256. */
+size_t lhvi_pt_lds_bytes(int32_t Nc, int32_t Nd, int32_t table_doubles, int32_t R, int32_t lanes);
+/* iterations [it_begin, it_end) of every ladder.  x_d [ladders][R][Nd] (int32; lhvi_gibbs_init over ladders * R rows before the
+ * first call) is in / out, so a run is any number of calls.  betas [R], mu0 [Nc]: device arrays; tau0 > 0.  lanes: lanes per
+ * replica, a power of two <= 64; a ladder's outputs depend neither on it, nor on `ladders`, nor on the split into calls.
+ * z [iters][ladders * R][Nc], u [iters][ladders * R][disc_block_its][Nd], usw [iters][ladders][max(R - 1, 1)]: injected draws
+ * (rows by absolute iteration), or NULL for the Philox stream.  disc, cont, counts, sum1, sum2: the outputs of lhvi_gibbs_run
+ * over `ladders` rows (each may be NULL; counts and sums zeroed before the first call).  swap_try, swap_acc [ladders][R - 1]
+ * (int32, zeroed before the first call, may be NULL): proposed and accepted swaps per pair.  m->table_scratch: NULL, or
+ * ladders * R rows of table_doubles.
+ * bad [1]: the caller sets it to UINT64_MAX; a ladder one of whose replicas meets a J_beta that is not positive definite lowers
+ * it to (ladder << 32 | iteration) (atomic min), keeps its x_d of that moment and stores, counts and swaps nothing more.
+ * LHVI_E_UNSUPPORTED: Nc > LHVI_EXACT_MAX_NC, R * lanes > 256 or more than 64 KiB of LDS. */
+int lhvi_pt_run(const lhvi_gibbs_t* m, int64_t ladders, int32_t R, const double* betas, int32_t it_begin, int32_t it_end,
+                int32_t swap_every, int32_t lanes, double tau0, const double* mu0, int32_t* x_d, const double* z, const double* u,
+                const double* usw, int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2, int32_t* swap_try,
+                int32_t* swap_acc, uint64_t* bad, void* stream);
+/* iterations [it_begin, it_end) of one ladder on the HOST through the device's code (csrc/pt.hpp), the replicas in order; every
+ * pointer of m and every argument is host memory; x_d [R][Nd] is in / out.  z [iters][R][Nc], u [iters][R][its][Nd],
+ * usw [iters][max(R - 1, 1)]: this ladder's injected draws, or all NULL for the Philox stream of ladder `ladder`.  The outputs
+ * are one ladder's rows.  m->table_scratch is ignored.  LHVI_E_NOT_PD when a J_beta is not positive definite. */
+int lhvi_pt_ladder_host(const lhvi_gibbs_t* m, int64_t ladder, int32_t R, const double* betas, int32_t it_begin, int32_t it_end,
+                        int32_t swap_every, double tau0, const double* mu0, int32_t* x_d, const double* z, const double* u,
+                        const double* usw, int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2,
+                        int32_t* swap_try, int32_t* swap_acc);
 
 /* ---- Exact Gaussian-MRF marginals: dense blocked fp64 Cholesky (osi/utils.py get_gaussian_mean_params_from_quadratic_params;
  * csrc/gauss_exact.hip, csrc/gauss_exact.hpp) ----------------------------------------------------------------------------------

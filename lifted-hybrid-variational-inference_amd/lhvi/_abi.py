@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 29            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 30            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -282,6 +282,11 @@ SIGNATURES = {
     'lhvi_ais_run': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_ais_reduce': (C.c_int, [_i64, _vp, _vp, _vp, _vp]),
     'lhvi_ais_chain_host': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _vp, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_pt_lds_bytes': (_sz, [_i32, _i32, _i32, _i32, _i32]),
+    'lhvi_pt_run': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _vp, _i32, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                              _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_pt_ladder_host': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit_host': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_kl_ws_doubles': (_sz, [_i32]),

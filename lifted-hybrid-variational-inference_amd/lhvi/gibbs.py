@@ -20,6 +20,9 @@ Beyond the reference (docs/kernels_gibbs_rb.md): ``GibbsHybridGaussian.rb_margin
 the latter through the device's code on the CPU.  ``GibbsHybridGaussian.log_partition()``,
 ``HybridGaussianSampler.log_partition()`` and ``ais_log_partition`` estimate ``log Z`` by annealed importance sampling
 (``csrc/ais.hip``, ``lhvi/ais.py``, docs/kernels_ais.md): the ``obj = -logZ`` the reference's Gibbs baseline leaves as a TODO.
+``GibbsHybridGaussian.run_tempered()``, ``HybridGaussianSampler.tempered_gibbs_sample()`` and ``tempered_gibbs_sample`` run the
+sampler as ladders of replicas along the same path that exchange their discrete states (parallel tempering, ``csrc/pt.hip``,
+``lhvi/pt.py``, docs/kernels_pt.md), for models whose discrete variables select the well a continuous variable sits in.
 """
 from __future__ import annotations
 
@@ -326,6 +329,28 @@ def ais_log_partition(factors, Vd, Vc, chains=4096, steps=256, betas=None, disc_
 ais_log_partition.__doc__ += '\n\n    ' + _LOG_PARTITION_DOC
 
 
+_TEMPERED_DOC = """Parallel tempering (docs/kernels_pt.md): ``ladders`` independent ladders of replicas at ``betas`` (never
+    decreasing, not negative, the last one 1; default ``linspace(0, 1, replicas)``) along ``p~^beta f0^(1 - beta)`` with the base
+    ``f0 = exp(-base_prec / 2 |x_c - base_mean|^2)`` (x_d uniform).  Every replica makes one block Gibbs transition per iteration
+    with ``disc_block_its`` sweeps; every ``swap_every`` iterations (0: never) adjacent replicas, even and odd pairs in turn,
+    propose to exchange their discrete states.  Only the ``beta = 1`` replica is kept, before the swap."""
+
+
+def tempered_gibbs_sample(factors, Vd, Vc, num_burnin, num_samples, betas=None, replicas=8, ladders=1, disc_block_its=1, swap_every=1,
+                          seed=None, base_mean=None, base_prec=None, lanes=None, its_per_launch=None):
+    """what ``block_gibbs_sample`` returns, from the ``beta = 1`` replicas of ``ladders`` ladders, ladder-major
+    ([ladders * num_samples, ...]).  Base mean 0 and precision 1 unless given."""
+    from . import pt
+    gm = GibbsModel(flatten_factors(factors, [rv.dstates for rv in Vd], len(Vc)))
+    run = pt.run(gm, ladders, replicas, betas, num_burnin, num_samples, disc_block_its, swap_every, seed, True, lanes, its_per_launch,
+                 base_mean, base_prec)
+    n = run.chains * run.num_samples
+    return run.disc.cpu().numpy().reshape(n, gm.ex.Nd).astype(np.int64), run.cont.cpu().numpy().reshape(n, gm.ex.Nc)
+
+
+tempered_gibbs_sample.__doc__ += '\n\n    ' + _TEMPERED_DOC
+
+
 def get_disc_marg_table_from_samples(samples, dstates):
     """``sampling_utils.get_disc_marg_table_from_samples``: the joint relative frequencies [v1..vN] of samples [S, N]"""
     samples = np.asarray(samples)
@@ -369,6 +394,17 @@ class HybridGaussianSampler:
         self.disc_samples, self.cont_samples = block_gibbs_sample(self.factors, self.Vd, self.Vc, num_burnin, num_samples,
                                                                   init_x_d, disc_block_its, seed, chains=chains)
         self.sampled_disc_marginal_table = get_disc_marg_table_from_samples(self.disc_samples, self.dstates)
+
+    def tempered_gibbs_sample(self, num_burnin, num_samples, betas=None, replicas=8, ladders=1, disc_block_its=1, swap_every=1,
+                              seed=None, base_mean=None, base_prec=None, lanes=None, its_per_launch=None):
+        """``block_gibbs_sample`` by parallel tempering: sets ``disc_samples``, ``cont_samples`` and
+        ``sampled_disc_marginal_table`` from the ``beta = 1`` replicas."""
+        self.disc_samples, self.cont_samples = tempered_gibbs_sample(self.factors, self.Vd, self.Vc, num_burnin, num_samples, betas,
+                                                                     replicas, ladders, disc_block_its, swap_every, seed, base_mean,
+                                                                     base_prec, lanes, its_per_launch)
+        self.sampled_disc_marginal_table = get_disc_marg_table_from_samples(self.disc_samples, self.dstates)
+
+    tempered_gibbs_sample.__doc__ += '\n\n        ' + _TEMPERED_DOC
 
     def map(self, rv, num_gm_components_for_crv=1):
         """discrete: the argmax of the variable's sampled marginal (the reference's line :296 passes ``Vd_idx`` where an index
@@ -462,8 +498,12 @@ class GibbsHybridGaussian:
             its_per_launch=None, init_x_d=None):
         if num_samples < 1:
             raise ValueError('num_samples must be positive')
-        self._run = r = _Chains(self.model, chains, num_burnin, num_samples, disc_block_its, _seed(seed), keep_samples, lanes,
-                                init_x_d=init_x_d).run(its_per_launch)
+        return self._adopt(_Chains(self.model, chains, num_burnin, num_samples, disc_block_its, _seed(seed), keep_samples, lanes,
+                                   init_x_d=init_x_d).run(its_per_launch), keep_samples)
+
+    def _adopt(self, r, keep_samples):
+        """the state a finished run leaves"""
+        self._run = r
         self.chains, self.num_samples = r.chains, r.num_samples
         self.marginals, self._fits = None, {}           # fits of an earlier run's samples
         self._energies = None
@@ -473,6 +513,45 @@ class GibbsHybridGaussian:
         self.disc_samples = r.disc.cpu().numpy() if keep_samples else None
         self.cont_samples = r.cont.cpu().numpy() if keep_samples else None
         return self
+
+    def run_tempered(self, ladders=1024, replicas=8, betas=None, num_burnin=100, num_samples=100, disc_block_its=1, swap_every=1,
+                     seed=0, keep_samples=False, lanes=None, its_per_launch=None, base_mean=None, base_prec=None):
+        """``run()`` by parallel tempering: afterwards the object is in the state ``run(chains=ladders)`` leaves, filled from the
+        ``beta = 1`` replica of every ladder, so every read-out works unchanged; ``swap_rates()`` / ``swap_counts()`` say how the
+        ladder exchanged.  The base defaults to ``log_partition``'s: the moments of an earlier run, else mean 0 and precision 1."""
+        from . import pt
+        if num_samples < 1:
+            raise ValueError('num_samples must be positive')
+        base_mean, base_prec = self._default_base(base_mean, base_prec)
+        return self._adopt(pt.run(self.model, ladders, replicas, betas, num_burnin, num_samples, disc_block_its, swap_every, seed,
+                                  keep_samples, lanes, its_per_launch, base_mean, base_prec), keep_samples)
+
+    run_tempered.__doc__ += '\n\n        ' + _TEMPERED_DOC
+
+    def swap_counts(self):
+        """(tried [R - 1], accepted [R - 1]): the swaps of every adjacent pair of replicas summed over the ladders of the last
+        ``run_tempered``"""
+        r = self._need_run()
+        if not hasattr(r, 'swap_try'):
+            raise RuntimeError('swap_counts needs run_tempered()')
+        return r.swap_counts()
+
+    def swap_rates(self):
+        """[R - 1]: the accepted fraction of the proposed swaps per adjacent pair (NaN where none was proposed)"""
+        tried, acc = self.swap_counts()
+        with np.errstate(divide='ignore', invalid='ignore'):
+            return acc / tried.astype(np.float64)
+
+    def _default_base(self, base_mean, base_prec):
+        """after a run the base defaults to ``moments()``: the sample means and the reciprocal of the mean marginal variance"""
+        Nc = len(self.Vc)
+        if self._run is not None and Nc and (base_mean is None or base_prec is None):
+            mo = self.moments()
+            var = float(np.diag(mo.cov).mean())
+            base_mean = mo.mean if base_mean is None else base_mean
+            if base_prec is None and var > 0.0 and np.isfinite(var):
+                base_prec = 1.0 / var
+        return base_mean, base_prec
 
     def _need_run(self):
         if self._run is None:
@@ -675,13 +754,7 @@ class GibbsHybridGaussian:
         leaves empty.  Needs no ``run()``; after one, the base defaults to ``moments()``: the sample means and the reciprocal of
         the mean marginal variance.  Before it, to mean 0 and precision 1."""
         from . import ais
-        Nc = len(self.Vc)
-        if self._run is not None and Nc and (base_mean is None or base_prec is None):
-            mo = self.moments()
-            var = float(np.diag(mo.cov).mean())
-            base_mean = mo.mean if base_mean is None else base_mean
-            if base_prec is None and var > 0.0 and np.isfinite(var):
-                base_prec = 1.0 / var
+        base_mean, base_prec = self._default_base(base_mean, base_prec)
         return ais.log_partition(self.model, chains, steps, betas, disc_block_its, seed, base_mean, base_prec, lanes,
                                  steps_per_launch, log_const=self.log_const)
 
