@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 30 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 31 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -53,7 +53,8 @@ extern "C" {
                               * 27: lhvi_exact_configs_at, lhvi_exact_config_at_host, lhvi_gibbs_rb_disc, lhvi_gibbs_rb_disc_host;
                               * 28: lhvi_gauss_chain_part_*, lhvi_gauss_chain_segments;
                               * 29: lhvi_ais_*, LHVI_AIS_REDUCE_OUT, LHVI_AIS_REDUCE_WS;
-                              * 30: lhvi_pt_* */
+                              * 30: lhvi_pt_*;
+                              * 31: lhvi_fgibbs_t, lhvi_fgibbs_*, LHVI_FGIBBS_MAX_STATES */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -896,6 +897,64 @@ int lhvi_pt_ladder_host(const lhvi_gibbs_t* m, int64_t ladder, int32_t R, const 
                         int32_t swap_every, double tau0, const double* mu0, int32_t* x_d, const double* z, const double* u,
                         const double* usw, int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2,
                         int32_t* swap_try, int32_t* swap_acc);
+
+/* ---- Single-site Gibbs / slice sampling on a ground flat graph (csrc/fgibbs.hip, csrc/fgibbs.hpp; docs/kernels_fgibbs.md) ---------
+ * `chains` independent chains over the hidden variables of a GROUND lhvi_graph_t (edge_count, var_mult, fac_mult NULL), any
+ * potential kind.  State: x [V][chains] (doubles) and idx [V][chains] (int32: the state index of a discrete variable, 0 of a
+ * continuous one), chain fastest; an observed variable holds its value.  The conditional log density of hidden variable v at t is
+ * g_v(t) = sum over v's var_edge row, in row order, of log phi_f(x with x_v = t): the evaluator's value where it is a logarithm,
+ * else log(value) (phi == 0: -inf).
+ *   discrete v (S <= LHVI_FGIBBS_MAX_STATES states): lp[j] = g_v(s_j); all -inf: the state stays and stuck[chain] += 1; else the
+ *     softmax and inverse-CDF pick of lhvi_gibbs_run with ONE uniform (draw 0).
+ *   continuous v (Neal's slice sampler, shrinkage only): y = g_v(x0) + log(1 - u_0); L = dom_lo, R = dom_hi; for k = 1 ..
+ *     max_shrink: x1 = L + u_k (R - L) (product rounded, then added); accept when g_v(x1) >= y, else L = x1 if x1 < x0 else R = x1.
+ *     Nothing accepted: x0 stays and capped[chain] += 1.
+ * Iteration `it` visits the colours 0, 1, ... (one launch each, plus one for the colour's hub list); no factor holds two hidden
+ * variables of one colour, so the launch equals the sequential visit of col_var in list order.  From iteration num_burnin on,
+ * every thin-th iteration is kept (sample s = (it - num_burnin) / thin < num_samples) and added to the accumulators by the thread
+ * that owns (variable, chain), in iteration order, without atomics.
+ * Draws: Philox4x32-10 keyed by seed; uniforms 2 p and 2 p + 1 of (chain, it, v) come from counter
+ * (chain | p << 24, it, v, "FGSU"); the initial state from (chain, 0, v, "FGXI").  chains <= 2^24, max_shrink <= 510. */
+#define LHVI_FGIBBS_MAX_STATES 16
+typedef struct lhvi_fgibbs {
+    int32_t n_colours;
+    const int32_t* col_ptr;     /* [n_colours + 1] into col_var */
+    const int32_t* col_var;     /* the hidden variables colour by colour, ascending ids within a colour */
+    const int32_t* hub_ptr;     /* [n_colours + 1] into hub_var */
+    const int32_t* hub_var;     /* per colour, the variables of col_var with more than hub_degree incident edges: a wavefront each */
+    int32_t max_shrink;
+    int32_t hub_degree;
+    int32_t num_burnin;
+    int32_t num_samples;
+    int32_t thin;
+    uint64_t seed;
+    const double* u;            /* injected uniforms [iterations][chains][V][1 + max_shrink], rows by absolute iteration, or NULL */
+    const double* init_x;       /* injected initial state [chains][V] (hidden rows are read), or NULL */
+    /* outputs: each may be NULL; the caller zeroes them before the first call */
+    const int32_t* cnt_off;     /* [V] first row of the variable's states in counts (hidden discrete variables), else -1 */
+    int32_t* counts;            /* [sum of states][chains] kept samples per state */
+    double* sum1;               /* [V][chains] sum of the kept x (hidden continuous rows) */
+    double* sum2;               /* [V][chains] sum of the kept x * x (product rounded, then added) */
+    const int32_t* keep_row;    /* [V] row of the variable in samples, or -1 */
+    double* samples;            /* [rows][chains * num_samples]: sample s of chain c at column c * num_samples + s */
+    int32_t* stuck;             /* [chains] discrete updates that met only -inf */
+    int32_t* capped;            /* [chains] slice updates that accepted nothing */
+    int64_t* evals;             /* [chains] evaluations of g_v */
+} lhvi_fgibbs_t;
+/* the initial state into x, idx [V][chains]: observed variables their value (a discrete one the index of its state, 0 when it
+ * is none of them), hidden discrete ones state floor(u S), hidden continuous ones lo + u (hi - lo); s->init_x replaces the draws */
+int lhvi_fgibbs_init(const lhvi_graph_t* g, const lhvi_fgibbs_t* s, int64_t chains, double* x, int32_t* idx, void* stream);
+/* iterations [it_begin, it_end) of every chain; x, idx in / out, so a run is any number of calls.  col_ptr_host, hub_ptr_host:
+ * HOST copies of s->col_ptr / s->hub_ptr (the launch sizes).  A chain's samples depend neither on `chains`, nor on the split into
+ * calls, nor on hub_degree up to the summation order of g_v (lane form: row order; hub form: 64 strided partial sums, then the
+ * fixed tree of the wave reduction).  LHVI_E_UNSUPPORTED: a lifted graph, chains > 2^24, max_shrink > 510. */
+int lhvi_fgibbs_run(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_fgibbs_t* s, int64_t chains, int32_t it_begin,
+                    int32_t it_end, const int32_t* col_ptr_host, const int32_t* hub_ptr_host, double* x, int32_t* idx, void* stream);
+/* chain `chain` of `chains` on the HOST through the device's code (csrc/fgibbs.hpp) with one "lane", in the sequential order:
+ * every pointer is host memory, the arrays have the device's layout and the chain touches its own column only.  init != 0: set
+ * the chain's initial state first. */
+int lhvi_fgibbs_chain_host(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_fgibbs_t* s, int64_t chains, int64_t chain,
+                           int32_t init, int32_t it_begin, int32_t it_end, double* x, int32_t* idx);
 
 /* ---- Exact Gaussian-MRF marginals: dense blocked fp64 Cholesky (osi/utils.py get_gaussian_mean_params_from_quadratic_params;
  * csrc/gauss_exact.hip, csrc/gauss_exact.hpp) ----------------------------------------------------------------------------------

@@ -181,6 +181,24 @@ LHVI_HD void back_solve(int Nc, int it, const Draws& dr, const Workspace& w, con
     }
 }
 
+// The draw of a discrete conditional from its log masses lp[j * stride], j < d (disc_mrf_sampler.pyx :43-70): the softmax
+// exp(v - (m + log sum)), then the first state with u <= cumulative sum; the last state catches rounding.  Shared with the
+// single-site sampler on flat graphs (csrc/fgibbs.hpp), whose lanes keep a column of LDS each (stride = the workgroup).
+LHVI_HD int softmax_pick(const double* lp, int stride, int d, double u) {
+    double mx = -__builtin_huge_val(), sum = 0.0;
+    for (int j = 0; j < d; ++j)
+        if (lp[j * stride] > mx) mx = lp[j * stride];
+    for (int j = 0; j < d; ++j) sum += exp(lp[j * stride] - mx);
+    const double scale = mx + log(sum);
+    double cum = 0.0;
+    int pick = d - 1;
+    for (int j = 0; j < d; ++j) {
+        cum += exp(lp[j * stride] - scale);
+        if (u <= cum) { pick = j; break; }
+    }
+    return pick;
+}
+
 // One outer iteration `it` of a chain whose x_d is in w.dig.  dead: the chain met a J that is not positive definite; it keeps
 // its x_d from then on and stores nothing.  Returns 1 when this iteration's J is not positive definite (and sets dead), the
 // same value in every lane.
@@ -212,17 +230,7 @@ LHVI_HD int iteration(const lhvi_gibbs_t& g, int it, const Draws& dr, const Work
             ctx.sync();
             // softmax (:43-58) and the first state with u <= cumulative sum (:62-70), by every lane with the same bits; the
             // last state catches rounding
-            double mx = -__builtin_huge_val(), sum = 0.0;
-            for (int j = 0; j < d; ++j)
-                if (w.lprobs[j] > mx) mx = w.lprobs[j];
-            for (int j = 0; j < d; ++j) sum += exp(w.lprobs[j] - mx);
-            const double scale = mx + log(sum), u = dr.uniform(it, sweep * Nd + n);
-            double cum = 0.0;
-            int pick = d - 1;
-            for (int j = 0; j < d; ++j) {
-                cum += exp(w.lprobs[j] - scale);
-                if (u <= cum) { pick = j; break; }
-            }
+            const int pick = softmax_pick(w.lprobs, 1, d, dr.uniform(it, sweep * Nd + n));
             if (ctx.lane == 0 && !dead) w.dig[n] = pick;  // no lane reads the digits between the two barriers
             ctx.sync();
         }

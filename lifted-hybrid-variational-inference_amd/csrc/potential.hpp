@@ -113,6 +113,19 @@ LHVI_POT_HD double quad_form(const double* __restrict__ A, const double* __restr
     return res + c;
 }
 
+// quad_form on x[off .. off + n): the same operations in the same order, x indexed from its base (a caller whose x is a register
+// array keeps it one: csrc/fgibbs.hpp)
+LHVI_POT_HD double quad_form_at(const double* __restrict__ A, const double* __restrict__ b, double c, int n, const double* x, int off) {
+    double res = 0.0;
+    for (int i = 0; i < n; ++i) {
+        double row = 0.0;
+        for (int j = 0; j < n; ++j) row += A[i * n + j] * x[off + j];
+        res += x[off + i] * row;
+    }
+    for (int i = 0; i < n; ++i) res += b[i] * x[off + i];
+    return res + c;
+}
+
 // value of the potential at the joint assignment x (idx = state indices of discrete arguments).
 // INTERP = false: the build for graphs without an interpreted formula (every MLN row carries a conditional-quadratic block, no
 // hard formula: lhvi_pots_t.interpreted == 0) -- the bytecode loop and its evaluation stack are not compiled in.

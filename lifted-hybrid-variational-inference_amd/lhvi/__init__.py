@@ -5,5 +5,6 @@ reference's flat modules; solvers (``gabp``, ``pbp``, ``vi``) flatten it to CSR 
 sweeps as hand-written HIP kernels through the C ABI in ``include/lhvi.h``.
 """
 from .graph import Domain, F, Graph, Potential, RV  # noqa: F401
+from .fgibbs import FlatGibbs  # noqa: F401
 
 __version__ = '0.1.0'

@@ -105,7 +105,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 30            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 31            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE
@@ -134,6 +134,16 @@ class GibbsStruct(C.Structure):
                 ('disc_block_its', C.c_int32), ('num_burnin', C.c_int32), ('num_samples', C.c_int32), ('seed', C.c_uint64)]
 
 
+class FgibbsStruct(C.Structure):
+    _fields_ = [('n_colours', C.c_int32), ('col_ptr', C.c_void_p), ('col_var', C.c_void_p), ('hub_ptr', C.c_void_p),
+                ('hub_var', C.c_void_p), ('max_shrink', C.c_int32), ('hub_degree', C.c_int32), ('num_burnin', C.c_int32),
+                ('num_samples', C.c_int32), ('thin', C.c_int32), ('seed', C.c_uint64), ('u', C.c_void_p), ('init_x', C.c_void_p),
+                ('cnt_off', C.c_void_p), ('counts', C.c_void_p), ('sum1', C.c_void_p), ('sum2', C.c_void_p),
+                ('keep_row', C.c_void_p), ('samples', C.c_void_p), ('stuck', C.c_void_p), ('capped', C.c_void_p),
+                ('evals', C.c_void_p)]
+
+
+FGIBBS_MAX_STATES = 16      # LHVI_FGIBBS_MAX_STATES
 E_NOT_PD = -5               # LHVI_E_NOT_PD
 EXACT_MAX_NC = 64           # LHVI_EXACT_MAX_NC
 GAUSS_EXACT_NB = 64         # LHVI_GAUSS_EXACT_NB
@@ -287,6 +297,9 @@ SIGNATURES = {
                               _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_pt_ladder_host': (C.c_int, [C.POINTER(GibbsStruct), _i64, _i32, _vp, _i32, _i32, _i32, _f64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_fgibbs_init': (C.c_int, [_G, C.POINTER(FgibbsStruct), _i64, _vp, _vp, _vp]),
+    'lhvi_fgibbs_run': (C.c_int, [_G, _P, C.POINTER(FgibbsStruct), _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    'lhvi_fgibbs_chain_host': (C.c_int, [_G, _P, C.POINTER(FgibbsStruct), _i64, _i64, _i32, _i32, _i32, _vp, _vp]),
     'lhvi_gm_fit': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_fit_host': (C.c_int, [_i32, _i64, _i32, _vp, _vp, _f64, _f64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     'lhvi_gm_kl_ws_doubles': (_sz, [_i32]),
