@@ -465,7 +465,8 @@ int lhvi_pbp_resample(const lhvi_graph_t* g, const lhvi_pbp_t* s, const int64_t*
  * HybridLBP.belief_rv_query (HLBP.py:313-317) sums these over a ground variable's factors. */
 int lhvi_pbp_edge_points(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_pbp_t* s, const double* v2f,
                          int32_t nq, const int32_t* qedge, int32_t npts, const double* x, double* out, void* stream);
-/* lhvi_pbp_resample followed by lhvi_pbp_uniq on the fresh particles: those two calls themselves when n > 64; for n <= 64 one fused
+/* lhvi_pbp_resample followed by lhvi_pbp_uniq on the fresh particles: those two calls themselves when n > 64 (both over the
+ * variables [var_lo, var_hi) when s names a range, as lhvi_pbp_resample alone does); for n <= 64 one fused
  * pass that draws from the same Philox blocks but takes the table logarithm and its own square root where lhvi_pbp_resample takes
  * the series logarithm -- its particles agree with lhvi_pbp_resample's to rounding (about 3 % of the drawn values differ in the
  * last bits; clipped ones are the bound in both), not to the bit, and its mask is the exact mask of its own particles

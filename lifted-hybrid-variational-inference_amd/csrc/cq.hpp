@@ -87,14 +87,18 @@ __device__ inline int cq_analyze(const lhvi_graph_t& g, const lhvi_pots_t& pots,
     int stride_t = 0, stride_z = 0, zv = -1, zce = -1, nz = 0;
     for (int a = 0; a < arity; ++a) {
         const int va = g.edge_var[base + a];
-        if (canon(g.edge_canon, base + a) != base + a) return CQ_NONE;
+        // the v2f row the argument's message is read from: its own; on an owner-computes shard a continuous ghost's row lies
+        // behind the E message rows, where it arrived (lhvi/dist.py::OwnerPlan.ghost_rows).  An alias inside the graph (a lifted
+        // cluster that repeats) stays with the generic kernel
+        const int ca = canon(g.edge_canon, base + a);
+        if (ca != base + a && ca < g.E) return CQ_NONE;
         for (int b = 0; b < a; ++b)
             if (g.edge_var[base + b] == va) return CQ_NONE;
         const double val = g.var_value[va];
         const int role = (int)v.role[a];
         if (role < 0) {
             const int ci = -1 - role;
-            cvar[ci] = va; cedge[ci] = base + a; chid[ci] = is_hidden(val); cval[ci] = val;
+            cvar[ci] = va; cedge[ci] = ca; chid[ci] = is_hidden(val); cval[ci] = val;
             if (!g.dom_cont[g.var_dom[va]]) return CQ_NONE;
             if (a == pos) tcont = ci;
         } else {
@@ -106,7 +110,7 @@ __device__ inline int cq_analyze(const lhvi_graph_t& g, const lhvi_pots_t& pots,
             if (a == pos) { stride_t = stride; }
             else if (is_hidden(val)) {
                 if (zv >= 0) return CQ_NONE;                 // two hidden discrete partners: generic
-                zv = va; zce = base + a; nz = nst; stride_z = stride;
+                zv = va; zce = ca; nz = nst; stride_z = stride;
             } else {
                 const int st = cq_state_index(g, va, val);
                 if (st < 0) return CQ_NONE;

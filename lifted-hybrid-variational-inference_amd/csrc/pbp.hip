@@ -2680,12 +2680,14 @@ __device__ __forceinline__ double philox_normal(uint64_t seed, uint64_t gid, uin
     return (j & 32u) ? zs : zc;
 }
 
-// generate_sample (EPBP:61-70): clip(normal(q.mu, sqrt(q.var)), lo, hi); discrete rvs: the domain states
+// generate_sample (EPBP:61-70): clip(normal(q.mu, sqrt(q.var)), lo, hi); discrete rvs: the domain states.
+// The variables [var_first, var_limit): all of them, or the caller's range (an owner-computes shard draws its own variables and
+// its ghosts at different times)
 __global__ void __launch_bounds__(BLOCK) pbp_resample_kernel(lhvi_graph_t g, lhvi_pbp_t s, const int64_t* __restrict__ gid,
                                                             uint64_t seed, uint32_t iteration, double* __restrict__ out) {
-    const int64_t i = (int64_t)blockIdx.x * BLOCK + threadIdx.x;
     const int n = s.n;
-    if (i >= (int64_t)g.V * n) return;
+    const int64_t i = (int64_t)var_first(s) * n + (int64_t)blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= (int64_t)var_limit(g, s) * n) return;
     const int v = (int)(i / n), j = (int)(i % n);
     if (j >= s.np[v]) return;
     const int d = g.var_dom[v];
@@ -3618,8 +3620,8 @@ int lhvi_pbp_resample(const lhvi_graph_t* g, const lhvi_pbp_t* s, const int64_t*
     if (int rc = validate_pbp(g, s)) return rc;
     if (!particles_out || !s->q) return LHVI_E_ARG;
     if (g->V == 0) return LHVI_OK;
-    hipLaunchKernelGGL(pbp_resample_kernel, dim3(grid_for((int64_t)g->V * s->n)), dim3(BLOCK), 0, as_stream(stream), *g, *s,
-                       var_gid, seed, iteration, particles_out);
+    hipLaunchKernelGGL(pbp_resample_kernel, dim3(grid_for((int64_t)(var_limit(*g, *s) - var_first(*s)) * s->n)), dim3(BLOCK), 0,
+                       as_stream(stream), *g, *s, var_gid, seed, iteration, particles_out);
     return check_launch();
 }
 
@@ -3639,10 +3641,13 @@ int lhvi_pbp_resample_uniq(const lhvi_graph_t* g, const lhvi_pbp_t* s, const int
     if (int rc = validate_pbp(g, s)) return rc;
     if (!particles_out || !uniq_out || !s->q) return LHVI_E_ARG;
     if (g->V == 0) return LHVI_OK;
-    if (s->n > WAVE) {            // general n: two passes over every variable
-        if (s->var_hi > s->var_lo) return LHVI_E_ARG;
+    if (s->n > WAVE) {            // general n: two passes over every variable, or over those of the caller's range
         if (int rc = lhvi_pbp_resample(g, s, var_gid, seed, iteration, particles_out, stream)) return rc;
-        return lhvi_pbp_uniq(g, s->n, particles_out, s->np, uniq_out, stream);
+        if (s->var_hi <= s->var_lo) return lhvi_pbp_uniq(g, s->n, particles_out, s->np, uniq_out, stream);
+        const int lo = s->var_lo, count = s->var_hi - s->var_lo;       // (validate_pbp: 0 <= lo < hi <= V)
+        hipLaunchKernelGGL(pbp_uniq_kernel, dim3(grid_for((int64_t)count * s->n)), dim3(BLOCK), 0, as_stream(stream), count, s->n,
+                           particles_out + (int64_t)lo * s->n, s->np + lo, uniq_out + (int64_t)lo * s->n);
+        return check_launch();
     }
     if (s->resample_vars && (s->n_resample_vars < 0 || s->var_hi > s->var_lo)) return LHVI_E_ARG;      // the list replaces the range
     const int64_t nvars = s->resample_vars ? s->n_resample_vars : var_limit(*g, *s) - var_first(*s);

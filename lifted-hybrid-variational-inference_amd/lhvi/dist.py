@@ -920,6 +920,20 @@ class OwnerRunner(_Runner):
         # the peers' continuous rows are read where they arrive: the receive buffer lies behind the E rows of the v -> f array and
         # the ghost edges' canonical rows point into it (OwnerPlan.ghost_rows) -- set before the work lists are described
         lay = self.lay = plan.layout(n)
+        self.n = n
+        self.n_owned, self.n_ghost = plan.n_owned, plan.n_ghost
+        self.overlap = bool(overlap) and world > 1
+        if plan.fac_ids.size == 0:
+            # a rank that owns no hidden variable holds no factor (a partition may leave one: the refined one does on a small
+            # graph cut eight ways): no sweep state and no launch; it takes part in every phase, sending and receiving nothing
+            _abi.require_gpu()
+            super().__init__(None)
+            self.send = self.recv = torch.zeros(0, dtype=torch.float64, device='cuda')
+            self.counts = list(lay['send']['counts'])
+            assert lay['send']['size'] == lay['recv']['size'] == 0
+            self.n_send_more, self.res_lists, self.idx = 0, None, {}
+            self.interior_fraction, self.split_f2v = 0.0, False
+            return
         canon, halo_rows = plan.ghost_rows(n)
         plan.flat.edge_canon = canon
         bp = EPBP(None, n=n, proposal_approximation=proposal_approximation, sampler='device', seed=seed)
@@ -928,9 +942,6 @@ class OwnerRunner(_Runner):
         bp._setup(None, flat=plan.flat, edge_key=plan.edge_key, edge_skip=plan.edge_skip, owned=plan.n_owned)
         super().__init__(bp)
         bp.var_gid = _abi.to_dev(plan.var_gid)
-        self.n = n
-        self.n_owned, self.n_ghost = plan.n_owned, plan.n_ghost
-        self.overlap = bool(overlap) and world > 1
         dev = bp.dg.device
         E = int(plan.flat.E)
         bp.v2f = torch.zeros(E + max(halo_rows, 1), n, dtype=torch.float64, device=dev)
@@ -979,6 +990,8 @@ class OwnerRunner(_Runner):
         """the v -> f array with every edge's row at its own index ([E, n]): the continuous ghost edges' rows gathered from where
         they arrived (tests compare this with the single-GPU array)"""
         import torch
+        if self.bp is None:
+            return self.recv.view(0, self.n)
         E = int(self.plan.flat.E)
         canon = _abi.to_dev(self.plan.flat.edge_canon.astype(np.int64))
         return self.bp.v2f.index_select(0, canon)[:E]
@@ -988,10 +1001,16 @@ class OwnerRunner(_Runner):
         """variables by range: owned [0, n_owned), ghosts after them; only the launches that run beside the collective leave it room"""
         return self.bp._struct((lo, hi), leave_room=self.overlap and leave_room)
 
-    # ---- the phases of a sweep ----------------------------------------------------------------------------------------------
+    # ---- the phases of a sweep (a rank without a sweep state, `bp` None, passes through each of them) -------------------------------
+    def init(self):
+        if self.bp is not None:
+            super().init()
+
     def owned_half(self):
         """v -> f and the proposal update of the owned variables.  The rows the peers need go into the send buffer as the v -> f
         half forms them (``halo_off``); a small pass adds the proposals of the owned variables that are ghosts elsewhere"""
+        if self.bp is None:
+            return self.send
         bp, l, st = self.bp, _abi.lib(), _abi.stream_ptr()
         if self.n_owned:
             s = bp._struct()                                  # the owned variables' lists (EPBP._setup(owned=...))
@@ -1025,6 +1044,8 @@ class OwnerRunner(_Runner):
 
     def interior(self, f2v_events=None):
         """what needs nothing from the peers: the owned variables' new particles, f -> v of the factors without a ghost"""
+        if self.bp is None:
+            return
         self.bp._new_sample()
         self._resample(0, self.n_owned)
         if self.split_f2v:
@@ -1032,6 +1053,8 @@ class OwnerRunner(_Runner):
 
     def boundary(self, recv, f2v_events=None):
         """the rest, once the peers' rows have arrived (after `interior`)"""
+        if self.bp is None:
+            return
         bp, l, st = self.bp, _abi.lib(), _abi.stream_ptr()
         L, ix = self.lay['recv'], self.idx
         if recv.data_ptr() != self.recv.data_ptr():            # (a loopback group's copy; a real collective wrote the rows in place)
@@ -1098,5 +1121,11 @@ class OwnerRunner(_Runner):
         return 1.0
 
     def f2v_joint_terms(self):
-        return joint_terms(self.plan.flat, self.bp.np_host, ~self.plan.edge_skip)
+        return joint_terms(self.plan.flat, self.bp.np_host, ~self.plan.edge_skip) if self.bp is not None else 0
+
+    def heavy_stats(self):
+        return super().heavy_stats() if self.bp is not None else (0, 0)
+
+    def heavy_grid_terms(self):
+        return super().heavy_grid_terms() if self.bp is not None else 0
 

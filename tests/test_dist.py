@@ -852,50 +852,13 @@ def test_owner_compute_sweep_equals_single_gpu_bit_for_bit(world):
     """`world` simulated ranks of the owner-computes split (loopback exchange) against the single-GPU sweep: proposals, particles
     and both message arrays are the same BITS -- every variable is swept once, over all its factors, in the single-GPU order, and
     ghosts are re-drawn from their owner's proposal with the sampler keyed by the global id"""
-    import torch
+    import dist_models
     from lhvi import synth, dist, _abi
-    from lhvi.pbp import EPBP
     _abi.require_gpu()
     flat = synth.hybrid_mrf_flat(V=2000, deg=4, seed=6)
-    n = 64
-    bp = EPBP(None, n=n, proposal_approximation='simple', sampler='device', seed=3)
-    bp._setup(None, flat=flat)
-    single = dist.SingleRunner(bp)
-    single.init()
-    owner = dist.partition_variables(flat, world)
-    group = dist.LoopbackGroup(world)
-    runners = [dist.OwnerRunner(flat, n=n, seed=3, rank=r, world=world, group=group, var_owner=owner) for r in range(world)]
-    for r in runners:
-        r.init()
-    for it in range(3):
-        single.sweep()
-        sends = [r.owned_half() for r in runners]
-        for r, s in zip(runners, sends):
-            group.post(r.rank, s, r.counts)
-        for r in runners:
-            r.interior()
-        for r in runners:
-            r.boundary(group.collect(r.rank, None))
-        dev = bp.q_dev.device
-        for r in runners:
-            plan = r.plan
-            gid = torch.from_numpy(plan.var_gid).to(dev)
-            own = torch.from_numpy((np.arange(plan.flat.V) < plan.n_owned) & plan.flat.var_hidden).to(dev)
-            loc = torch.from_numpy((np.arange(plan.flat.V) < plan.n_owned + plan.n_ghost) & plan.flat.var_hidden).to(dev)
-            live = torch.from_numpy(np.arange(n)[None, :] < r.bp.np_host[:, None]).to(dev)
-            assert torch.equal(r.bp.q_dev[own], bp.q_dev[gid][own])
-            cont = torch.from_numpy(plan.flat.var_cont).to(dev)
-            assert torch.equal(r.bp.q_dev[loc & cont], bp.q_dev[gid][loc & cont])            # ghosts: their owner's proposal
-            assert torch.equal(torch.where(live, r.bp.particles, 0.0)[loc], torch.where(live, bp.particles[gid], 0.0)[loc])
-            eid = torch.from_numpy(plan.edge_ids).to(dev)
-            mine = torch.from_numpy(~plan.edge_skip).to(dev)
-            le = live[torch.from_numpy(plan.flat.edge_var.astype(np.int64)).to(dev)]
-            rows = r.message_rows()                     # (continuous ghost edges: gathered from where their rows arrived)
-            assert torch.equal(torch.where(le, rows, 0.0)[mine], torch.where(le, bp.v2f[eid], 0.0)[mine])
-            assert torch.equal(r.bp.f2v[mine], bp.f2v[eid][mine])
-            hid_e = torch.from_numpy(plan.flat.var_hidden[plan.flat.edge_var]).to(dev)
-            assert torch.equal(torch.where(le, rows, 0.0)[hid_e], torch.where(le, bp.v2f[eid], 0.0)[hid_e])   # ghost edges: received rows
-    assert torch.isfinite(bp.q_dev[torch.from_numpy(flat.var_hidden).to(dev)]).all()
+    # (the loop and its comparisons live in tests/dist_models.py, shared with tests/test_gpu_dist_shapes.py)
+    stats = dist_models.assert_owner_equals_single(flat, 64, world, dist.partition_variables(flat, world), 'simple', sweeps=3)
+    assert all(st.n_owned > 0 and st.n_cut_factors > 0 and st.n_cont_ghost_edges > 0 for st in stats)
 
 
 def _owner_compute_gpu_worker(rank, world, port, out_dir):
