@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define LHVI_ABI_VERSION 31 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
+#define LHVI_ABI_VERSION 32 /* 2: lhvi_graph_t gained edge_value / slot_var / hub_vars, lhvi_pbp_t the heavy / light descriptor lists, 128-byte descriptors;
                               * 3: lhvi_pbp_t gained var_lo / var_hi;  4: f2v_ticket;  5: prop_desc;  6: lhvi_vi_t gained obs_var, lhvi_gabp_plan_t;  7: lhvi_pbp_t gained pair_desc;
                               * 8: lhvi_pbp_t gained cq_desc / n_cq, lhvi_pbp_classify takes the particle state, lhvi_pbp_describe_cq; the colour
                               *    refinement calls take a method and return four result words; lhvi_vi_t gained var_N; lhvi_vi_opt_t, lhvi_vi_adam_run;
@@ -54,7 +54,8 @@ extern "C" {
                               * 28: lhvi_gauss_chain_part_*, lhvi_gauss_chain_segments;
                               * 29: lhvi_ais_*, LHVI_AIS_REDUCE_OUT, LHVI_AIS_REDUCE_WS;
                               * 30: lhvi_pt_*;
-                              * 31: lhvi_fgibbs_t, lhvi_fgibbs_*, LHVI_FGIBBS_MAX_STATES */
+                              * 31: lhvi_fgibbs_t, lhvi_fgibbs_*, LHVI_FGIBBS_MAX_STATES;
+                              * 32: LHVI_PBP_NO_SPLIT_ROUND */
 #define LHVI_MAX_ARITY 6
 
 /* error codes */
@@ -236,6 +237,9 @@ int lhvi_log_likelihood(const lhvi_graph_t* g, const lhvi_pots_t* pots, const do
                                    * rows of f2v), find a wave slot and LDS on every CU and run beside them */
 #define LHVI_PBP_NO_GRID 128u    /* lhvi_pbp_f2v: integral points always by the direct form (one exponential per term), never by the
                                    * uniform-grid recurrence (testing / profiling aid) */
+#define LHVI_PBP_NO_SPLIT_ROUND 16777216u /* lhvi_pbp_f2v: the heavy kernel's full particle round (64 target particles on 64 lanes) through the loop of
+                                   * every other round (a record read per term) instead of the split round (the half-waves share a point pair
+                                   * and split the chains: a record read per two terms).  Same bits either way (testing / profiling aid) */
 #define LHVI_PBP_FUSED_RECORDS16 131072u /* lhvi_pbp_var_fused: desc holds SIXTEEN 32-bit words per variable (64-byte aligned) -- words 0-7 as documented
                                    * there, then 8 particles of the variable (s->np[v])  9 g->var_ptr[v]  10-15 its first six incident edges
                                    * (var_edge[var_ptr[v] + 0 .. 5]; unused ones 0) -- so that a variable's rows hang on one load behind its record */

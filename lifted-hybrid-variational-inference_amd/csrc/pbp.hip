@@ -731,6 +731,70 @@ __device__ __forceinline__ double fast_accumulate_floor(const AB* __restrict__ s
     return (acc0 + acc1) * sft.scale;
 }
 
+// The same sums for one FULL round (64 points, lane = point) with half the record reads: the two half-waves share the point
+// pair (l & 31, (l & 31) + 32) and split the four CHAINS instead -- lanes 0-31 run chains 0 and 2 (records 4m, 4m + 2) of both
+// points, lanes 32-63 chains 1 and 3 (records 4m + 1, 4m + 3).  Per iteration a lane reads two records (one ds_read_b128 each, two
+// addresses per wave) and runs four independent chains, as above; a wave-iteration still covers 4 records x 64 points.  Every chain
+// adds its terms in the order of fast_accumulate_floor<4>, chains 0 + 2 and 1 + 3 are folded inside the round-down window, and one
+// v_permlane32_swap per dword then hands each lane the other half's partial sum of ITS OWN point: (acc0 + acc2) + (acc1 + acc3)
+// and the product with the point's scale are formed in round-to-nearest.
+// `sh` holds 64 records, those from nj on padding (terms that are exactly 0): the loop runs ceil(nj / 4) whole iterations, which
+// is the list padded to a multiple of four, term for term what the remainder code above computes.
+// The result is held bit for bit to what the heavy kernel's unpinned fast_accumulate_floor<4>(sh, tab, nj, X, k X X) gives
+// (LHVI_PBP_NO_SPLIT_ROUND, tests/test_gpu_pbp_split_round.py), so every operation that rounds is pinned here to the mode it runs
+// under THERE.  In that instantiation the compiler sinks the second half of exp_shift_floor below the term loop, into the window:
+// the steps of C and the rounding constant are formed in round-to-nearest, the remainder of C and its exponential
+// (exp_shift_floor_rest) in round-DOWN, the factor LHVI_EXPF_SCALE and the closing sum and product in round-to-nearest again.
+__device__ __forceinline__ double fast_accumulate_floor_split(const AB* __restrict__ sh, const double* __restrict__ tab, int nj_, double X,
+                                                              double kconst, int lane) {
+    const int iters = __builtin_amdgcn_readfirstlane((nj_ + 3) >> 2);
+    // (the asm keeps what hangs on the half out of the registers held across the caller's edge loop: a mask pair and an LDS address)
+    asm volatile("" : "+v"(lane));
+    const bool upper = lane >= 32;
+    // each lane forms the constants of its own point (the one whose sum it finishes); v_permlane32_swap a, b (a's upper half <->
+    // b's lower half) of a value with itself then leaves point l & 31's in a and point (l & 31) + 32's in b, in both halves
+    double c_own = kconst * X * X;
+    asm volatile("" : "+v"(c_own));
+    double k_own = exp_shift_floor_steps(c_own);
+    const double m_own = exp_shift_floor_magic(k_own);
+    double xa, xb, ma, mb;
+    {
+        auto x_lo = __builtin_amdgcn_permlane32_swap(__double2loint(X), __double2loint(X), false, false);
+        auto x_hi = __builtin_amdgcn_permlane32_swap(__double2hiint(X), __double2hiint(X), false, false);
+        auto m_lo = __builtin_amdgcn_permlane32_swap(__double2loint(m_own), __double2loint(m_own), false, false);
+        auto m_hi = __builtin_amdgcn_permlane32_swap(__double2hiint(m_own), __double2hiint(m_own), false, false);
+        xa = __hiloint2double(x_hi[0], x_lo[0]); xb = __hiloint2double(x_hi[1], x_lo[1]);
+        ma = __hiloint2double(m_hi[0], m_lo[0]); mb = __hiloint2double(m_hi[1], m_lo[1]);
+    }
+    asm volatile("" : "+v"(ma), "+v"(mb), "+v"(c_own), "+v"(k_own));
+    const AB* __restrict__ mine = sh + (upper ? 1 : 0);
+    double a0 = 0.0, a1 = 0.0, b0 = 0.0, b1 = 0.0;             // point a / b, the half's first / second chain
+    round_down_on();
+    asm volatile("" : "+v"(c_own), "+v"(k_own));               // (what depends on these runs behind the mode write ...
+    double scale = exp_shift_floor_rest(c_own, k_own);
+    asm volatile("" : "+v"(scale));                            //  ... and this value exists before the next one)
+    const auto step = [&](int m) {
+        const AB r0 = mine[4 * m], r1 = mine[4 * m + 2];
+        a0 = exp_accumulate_floor(a0, fma(r0.b, xa, r0.a), ma, tab);
+        b0 = exp_accumulate_floor(b0, fma(r0.b, xb, r0.a), mb, tab);
+        a1 = exp_accumulate_floor(a1, fma(r1.b, xa, r1.a), ma, tab);
+        b1 = exp_accumulate_floor(b1, fma(r1.b, xb, r1.a), mb, tab);
+    };
+    int m = 0;
+    for (; m + 2 <= iters; m += 2) { step(m); step(m + 1); }   // (two iterations per address update)
+    if (m < iters) step(m);
+    a0 += a1; b0 += b1;                                        // acc0 += acc2 (lower half) / acc1 += acc3 (upper half), per point
+    asm volatile("" : "+v"(a0), "+v"(b0));
+    round_down_off();
+    asm volatile("" : "+v"(a0), "+v"(b0), "+v"(scale));
+    scale *= LHVI_EXPF_SCALE;
+    // a0's upper half <-> b0's lower half: lane l < 32 holds (its chains 0 + 2, the upper half's chains 1 + 3) of point l, lane
+    // l >= 32 (the lower half's chains 0 + 2, its chains 1 + 3) of point l
+    auto lo = __builtin_amdgcn_permlane32_swap(__double2loint(a0), __double2loint(b0), false, false);
+    auto hi = __builtin_amdgcn_permlane32_swap(__double2hiint(a0), __double2hiint(b0), false, false);
+    return (__hiloint2double(hi[0], lo[0]) + __hiloint2double(hi[1], lo[1])) * scale;
+}
+
 // FAST edges: persistent kernel, one wavefront per edge at a time (each wave strides over the work list).
 // Partner coefficients are staged in wave-private LDS in tiles of 64; each lane owns one output point per round and
 // accumulates sum_j exp(.).  A final partial round splits the partner range over idle lanes and folds the partial
@@ -1320,6 +1384,14 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
                 if (valid && sub == 0) row_store(out, (uint32_t)(n + t0 + pl), acc > 0.0 ? log_table(acc, sh_log) : -700.0);
             }
         }
+        // (the flags from the argument block, as the pointers above: tested against s.flags the result is a scalar pair held across
+        // the edge loop, or s.flags itself is -- the kernel has no scalar register to spare)
+        const uint32_t split_flags = heavy_arg_reload<uint32_t>(offsetof(HeavyArgs, flags));
+        if (np == 64 && npts == 64 && !(split_flags & (LHVI_PBP_SKIP_TERMS | LHVI_PBP_NO_SPLIT_ROUND))) {
+            // the dominant shape again (heavy_fetch): one full round, a record read serves two terms
+            const double acc = fast_accumulate_floor_split(sh, sh_tab, nj, x0, kconst, lane);
+            row_store(out, (uint32_t)lane, acc > 0.0 ? log_table(acc, sh_log) : -700.0);
+        } else {
 #pragma nounroll
         for (int r = 0; r < 2; ++r) {
             const int rem = npts - 64 * r;
@@ -1334,6 +1406,7 @@ __global__ void __launch_bounds__(HEAVY_BLOCK) __attribute__((amdgpu_waves_per_e
             double acc = fast_accumulate_floor<LHVI_HEAVY_UNROLL>(sh + sub * chunk, sh_tab, chunk, X1, C);
             for (int off = width; off < 64; off <<= 1) acc += __shfl_xor(acc, off);
             if (valid && sub == 0) row_store(out, (uint32_t)(p < np ? p : n + (p - np)), acc > 0.0 ? log_table(acc, sh_log) : -700.0);
+        }
         }
         if (!more) break;
         cur.advance(nxt, lane, ticket);

@@ -97,6 +97,7 @@ PBP_WIDE_PAIRS = 16384
 PBP_SHARE_CUS = 32768
 PBP_POW2_GROUPS = 65536
 PBP_FUSED_RECORDS16 = 131072
+PBP_NO_SPLIT_ROUND = 16777216
 # the kernel families of one lhvi_pbp_f2v call (LHVI_PBP_F2V_*; none set: all of them)
 PBP_F2V_HEAVY = 262144
 PBP_F2V_SMALL = 524288
@@ -105,7 +106,7 @@ PBP_F2V_FAST = 2097152
 PBP_F2V_CQ = 4194304
 PBP_F2V_GENERIC = 8388608
 PBP_F2V_ALL = PBP_F2V_HEAVY | PBP_F2V_SMALL | PBP_F2V_PAIR | PBP_F2V_FAST | PBP_F2V_CQ | PBP_F2V_GENERIC
-ABI_VERSION = 31            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
+ABI_VERSION = 32            # LHVI_ABI_VERSION of include/lhvi.h (struct layouts)
 PBP_DESC_BYTES = 128
 COLOR_HASH, COLOR_SORT = 0, 1     # method of lhvi_color_refine_* (LHVI_COLOR_HASH / LHVI_COLOR_SORT)
 HUB_DEGREE = 64              # LHVI_HUB_DEGREE

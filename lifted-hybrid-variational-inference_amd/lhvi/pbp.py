@@ -109,7 +109,9 @@ class _ParticleSweep:
                      (_abi.PBP_EPBP_DISCRETE if self._epbp_discrete else 0) | \
                      (_abi.PBP_CQ if self.cq_routing and bool((flat.pot_kind == 8).any()) else 0) | \
                      (_abi.PBP_POW2_GROUPS if os.environ.get('LHVI_PBP_POW2_GROUPS', '0') == '1' else 0) | \
-                     plan.flags                                 # (LHVI_PBP_POW2_GROUPS: tuning aid, scripts/diag/narrow_groups.sh)
+                     (_abi.PBP_NO_SPLIT_ROUND if os.environ.get('LHVI_PBP_SPLIT_ROUND', '1') == '0' else 0) | \
+                     plan.flags                                 # (LHVI_PBP_POW2_GROUPS: tuning aid, scripts/diag/narrow_groups.sh;
+                                                                #  LHVI_PBP_SPLIT_ROUND=0: the heavy kernel's full round by the one-term-per-read loop, profiles/split_round_experiments.md)
         self._views, self._batched = {}, {}
         self._draws = 0
         self._static_rows = False           # the rows no listed draw writes are filled once, by the first draw (_generate_sample)
