@@ -6,6 +6,7 @@
 //                        floating-point atomics: the same bits on every run)
 #include "common.hpp"
 #include "ais.hpp"
+#include "hg_launch.hpp"
 
 namespace lhvi {
 namespace ais {
@@ -14,14 +15,8 @@ constexpr int RB = 256;            // workgroup of the reductions
 constexpr int PARTS = 1024;        // partial results of the two-stage reductions
 constexpr int SUMS = 6;            // sums of the second pass
 
-struct DevCtx {
-    int lane, lanes;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
-
-__device__ __forceinline__ int lds_disc_doubles(const lhvi_gibbs_t& g) {
-    return g.max_states + (g.table_scratch ? 0 : g.table_doubles);
-}
+using hg::DevCtx;
+using hg::lds_disc_doubles;
 
 __global__ void __launch_bounds__(WAVE) ais_chain_kernel(lhvi_gibbs_t g, int64_t chains, int T, const double* __restrict__ betas,
                                                          int t_begin, int t_end, int lanes, double tau0,
@@ -138,20 +133,6 @@ __global__ void __launch_bounds__(RB) ais_sum_final_kernel(int n, const double* 
     }
 }
 
-static int model_check(const lhvi_gibbs_t* g) {
-    if (!g) return LHVI_E_ARG;
-    const lhvi_exact_t& m = g->ex;
-    if (m.Nd < 0 || m.Nc < 0 || m.n_quad < 0 || m.n_tab < 0 || g->n_hyb < 0 || g->table_doubles < 0 || g->max_states < 1)
-        return LHVI_E_ARG;
-    if (g->disc_block_its < 0) return LHVI_E_ARG;
-    if (m.Nd && (!m.dstates || !g->dstate_off || !g->vt_ptr || !g->vh_ptr)) return LHVI_E_ARG;
-    if (m.n_quad && (!m.quad_ptr || !m.quad_desc || !m.quad_par)) return LHVI_E_ARG;
-    if (m.n_tab && (!m.tab_ptr || !m.tab_desc || !m.tab_par || !g->vt_fac)) return LHVI_E_ARG;
-    if (g->n_hyb && (!g->hyb_quad || !g->hyb_off || !g->vh_fac)) return LHVI_E_ARG;
-    if (m.Nc > LHVI_EXACT_MAX_NC) return LHVI_E_UNSUPPORTED;
-    return LHVI_OK;
-}
-
 static int run_check(const lhvi_gibbs_t* m, int32_t T, const double* betas, int32_t t_begin, int32_t t_end, double tau0,
                      const double* mu0, const int32_t* x_d, const double* logw) {
     if (T < 1 || !betas || t_begin < 0 || t_end < t_begin || t_end > T || !logw) return LHVI_E_ARG;
@@ -168,27 +149,24 @@ using namespace lhvi::ais;
 extern "C" {
 
 size_t lhvi_ais_lds_bytes(int32_t Nc, int32_t Nd, int32_t table_doubles, int32_t lanes) {
-    if (Nc < 0 || Nd < 0 || table_doubles < 0 || lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return 0;
-    return (size_t)(WAVE / lanes) * (((size_t)ais::ws_doubles(Nc, Nd, table_doubles) + 1) & ~(size_t)1) * sizeof(double);
+    if (Nc < 0 || Nd < 0 || table_doubles < 0 || !hg::lanes_ok(lanes)) return 0;
+    return hg::wave_lds_bytes(lanes, ais::ws_doubles(Nc, Nd, table_doubles));
 }
 
 int lhvi_ais_run(const lhvi_gibbs_t* m, int64_t chains, int32_t T, const double* betas, int32_t t_begin, int32_t t_end,
                  int32_t lanes, double tau0, const double* mu0, int32_t* x_d, double* logw, const double* z, const double* u,
                  uint64_t* bad, void* stream) {
-    int rc = ais::model_check(m);
+    int rc = hg::gibbs_check(m, hg::ITS);            // a run reads neither num_burnin nor num_samples
     if (rc) return rc;
     if (chains < 0 || chains > 0xffffffffLL || !bad) return LHVI_E_ARG;
     rc = run_check(m, T, betas, t_begin, t_end, tau0, mu0, x_d, logw);
     if (rc) return rc;
-    if (lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return LHVI_E_ARG;
-    const int disc_doubles = m->max_states + (m->table_scratch ? 0 : m->table_doubles);
-    const size_t lds = lhvi_ais_lds_bytes(m->ex.Nc, m->ex.Nd, disc_doubles, lanes);
-    if (lds > 64 * 1024) return LHVI_E_UNSUPPORTED;
-    if (chains == 0 || t_end == t_begin) return LHVI_OK;
-    const int gpb = WAVE / lanes;
-    const int64_t blocks = (chains + gpb - 1) / gpb;
-    if (blocks > 0x7fffffff) return LHVI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(ais_chain_kernel, dim3((unsigned)blocks), dim3(WAVE), lds, as_stream(stream), *m, chains, (int)T, betas,
+    if (!hg::lanes_ok(lanes)) return LHVI_E_ARG;
+    const int64_t work = t_end == t_begin ? 0 : chains;
+    hg::WaveShape sh;
+    rc = hg::wave_shape(work, lanes, ais::ws_doubles(m->ex.Nc, m->ex.Nd, lds_disc_doubles(*m)), sh);
+    if (rc || !work) return rc;
+    hipLaunchKernelGGL(ais_chain_kernel, dim3((unsigned)sh.blocks), dim3(WAVE), sh.lds, as_stream(stream), *m, chains, (int)T, betas,
                        (int)t_begin, (int)t_end, (int)lanes, tau0, mu0, x_d, logw, z, u,
                        reinterpret_cast<unsigned long long*>(bad));
     return check_launch();
@@ -208,7 +186,7 @@ int lhvi_ais_reduce(int64_t chains, const double* logw, double* out, double* ws,
 
 int lhvi_ais_chain_host(const lhvi_gibbs_t* m, int64_t chain, int32_t T, const double* betas, int32_t t_begin, int32_t t_end,
                         double tau0, const double* mu0, int32_t* x_d, double* logw, const double* z, const double* u) {
-    int rc = ais::model_check(m);
+    int rc = hg::gibbs_check(m, hg::ITS);
     if (rc) return rc;
     rc = run_check(m, T, betas, t_begin, t_end, tau0, mu0, x_d, logw);
     if (rc) return rc;
@@ -216,13 +194,12 @@ int lhvi_ais_chain_host(const lhvi_gibbs_t* m, int64_t chain, int32_t T, const d
     if (chain < 0 || chain > 0xffffffffLL) return LHVI_E_ARG;
     const bool injected = z || u;
     if (injected && ((Nc && !z) || (Nd && m->disc_block_its && !u))) return LHVI_E_ARG;     // both streams, or neither
-    lhvi_gibbs_t g = *m;
-    g.table_scratch = nullptr;
-    const int dd = g.max_states + g.table_doubles;
-    double* W = new double[ais::ws_doubles(Nc, Nd, dd) + 2];
+    hg::HostWork hw(*m);
+    const lhvi_gibbs_t& g = hw.g;
+    double* W = hw.alloc(ais::ws_doubles(Nc, Nd, hw.dd) + 2);
     const gibbs::Workspace w = gibbs::layout(g, W, nullptr);
-    double* m0 = base_mean(Nc, Nd, dd, W);
-    for (int n = 0; n < Nd; ++n) w.dig[n] = x_d[n];
+    double* m0 = base_mean(Nc, Nd, hw.dd, W);
+    hw.digits_in(w, x_d);
     for (int r = 0; r < Nc; ++r) m0[r] = mu0[r];
     // injected draws are this chain's rows (z [T][Nc], u [T][its][Nd]); the Philox stream is that of chain `chain`
     gibbs::Draws dr{g.seed, z, u, 1, 0, Nc, Nd, g.disc_block_its};
@@ -233,9 +210,8 @@ int lhvi_ais_chain_host(const lhvi_gibbs_t* m, int64_t chain, int32_t T, const d
     double lw = *logw;
     bool dead = false;
     for (int t = t_begin; t < t_end; ++t) step(g, t, T, betas, base, dr, w, exact::HostCtx(), dead, lw);
-    for (int n = 0; n < Nd; ++n) x_d[n] = w.dig[n];
+    hw.digits_out(w, x_d);
     *logw = lw;
-    delete[] W;
     return dead ? LHVI_E_NOT_PD : LHVI_OK;
 }
 

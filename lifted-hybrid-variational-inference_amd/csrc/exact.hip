@@ -8,6 +8,7 @@
 //   exact_polish_kernel   safeguarded Newton on the log density from given starts, clipped to the domain (marginal MAP)
 #include "common.hpp"
 #include "exact.hpp"
+#include "hg_launch.hpp"
 
 namespace lhvi {
 namespace exact {
@@ -16,10 +17,7 @@ constexpr int RB = 256;            // workgroup of the reductions
 constexpr int PARTS = 1024;        // partial results of the two-stage reductions
 constexpr int MIX_PTS = 4;         // query points of one mixture workgroup
 
-struct DevCtx {
-    int lane, lanes;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
+using hg::DevCtx;
 
 __global__ void __launch_bounds__(WAVE) exact_config_kernel(lhvi_exact_t m, int64_t begin, int64_t count, int lanes, double* logp,
                                                             double* means, double* vars, double* covs, unsigned long long* bad) {
@@ -215,23 +213,20 @@ using namespace lhvi::exact;
 extern "C" {
 
 size_t lhvi_exact_lds_bytes(int32_t Nc, int32_t Nd, int32_t lanes) {
-    if (Nc < 0 || Nd < 0 || lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return 0;
-    return (size_t)(WAVE / lanes) * ((ws_doubles(Nc, Nd) + 1) & ~1) * sizeof(double);
+    if (Nc < 0 || Nd < 0 || !hg::lanes_ok(lanes)) return 0;
+    return hg::wave_lds_bytes(lanes, ws_doubles(Nc, Nd));
 }
 
 int lhvi_exact_configs(const lhvi_exact_t* m, int64_t cfg_begin, int64_t cfg_count, int32_t lanes, double* logp, double* means,
                        double* vars, double* covs, uint64_t* bad, void* stream) {
-    const int rc = model_check(m);
+    int rc = model_check(m);
     if (rc) return rc;
     if (cfg_begin < 0 || cfg_count < 0 || cfg_begin + cfg_count > m->M || !logp || !means || !vars || !bad) return LHVI_E_ARG;
-    if (lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return LHVI_E_ARG;
-    const size_t lds = lhvi_exact_lds_bytes(m->Nc, m->Nd, lanes);
-    if (lds > 64 * 1024) return LHVI_E_UNSUPPORTED;
-    if (cfg_count == 0) return LHVI_OK;
-    const int gpb = WAVE / lanes;
-    const int64_t blocks = (cfg_count + gpb - 1) / gpb;
-    if (blocks > 0x7fffffff) return LHVI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(exact_config_kernel, dim3((unsigned)blocks), dim3(WAVE), lds, as_stream(stream), *m, cfg_begin, cfg_count,
+    if (!hg::lanes_ok(lanes)) return LHVI_E_ARG;
+    hg::WaveShape sh;
+    rc = hg::wave_shape(cfg_count, lanes, ws_doubles(m->Nc, m->Nd), sh);
+    if (rc || !cfg_count) return rc;
+    hipLaunchKernelGGL(exact_config_kernel, dim3((unsigned)sh.blocks), dim3(WAVE), sh.lds, as_stream(stream), *m, cfg_begin, cfg_count,
                        (int)lanes, logp, means, vars, covs, reinterpret_cast<unsigned long long*>(bad));
     return check_launch();
 }

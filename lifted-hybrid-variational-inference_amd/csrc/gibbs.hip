@@ -5,20 +5,15 @@
 //   gibbs_init_kernel    the initial x_d from the Philox stream
 #include "common.hpp"
 #include "gibbs.hpp"
+#include "hg_launch.hpp"
 
 namespace lhvi {
 namespace gibbs {
 
 constexpr int IB = 256;
 
-struct DevCtx {
-    int lane, lanes;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
-
-__device__ __forceinline__ int lds_disc_doubles(const lhvi_gibbs_t& g) {
-    return g.max_states + (g.table_scratch ? 0 : g.table_doubles);
-}
+using hg::DevCtx;
+using hg::lds_disc_doubles;
 
 __global__ void __launch_bounds__(WAVE) gibbs_chain_kernel(lhvi_gibbs_t g, int64_t chains, int it_begin, int it_end, int lanes,
                                                            int32_t* x_d, const double* z, const double* u, int32_t* disc,
@@ -68,20 +63,6 @@ __global__ void __launch_bounds__(IB) gibbs_init_kernel(lhvi_gibbs_t g, int64_t 
     x_d[i] = k < d - 1 ? k : d - 1;
 }
 
-static int model_check(const lhvi_gibbs_t* g) {
-    if (!g) return LHVI_E_ARG;
-    const lhvi_exact_t& m = g->ex;
-    if (m.Nd < 0 || m.Nc < 0 || m.n_quad < 0 || m.n_tab < 0 || g->n_hyb < 0 || g->table_doubles < 0 || g->max_states < 1)
-        return LHVI_E_ARG;
-    if (g->disc_block_its < 0 || g->num_burnin < 0 || g->num_samples < 0) return LHVI_E_ARG;
-    if (m.Nd && (!m.dstates || !g->dstate_off || !g->vt_ptr || !g->vh_ptr)) return LHVI_E_ARG;
-    if (m.n_quad && (!m.quad_ptr || !m.quad_desc || !m.quad_par)) return LHVI_E_ARG;
-    if (m.n_tab && (!m.tab_ptr || !m.tab_desc || !m.tab_par || !g->vt_fac)) return LHVI_E_ARG;
-    if (g->n_hyb && (!g->hyb_quad || !g->hyb_off || !g->vh_fac)) return LHVI_E_ARG;
-    if (m.Nc > LHVI_EXACT_MAX_NC) return LHVI_E_UNSUPPORTED;
-    return LHVI_OK;
-}
-
 }  // namespace gibbs
 }  // namespace lhvi
 
@@ -91,12 +72,12 @@ using namespace lhvi::gibbs;
 extern "C" {
 
 size_t lhvi_gibbs_lds_bytes(int32_t Nc, int32_t Nd, int32_t table_doubles, int32_t lanes) {
-    if (Nc < 0 || Nd < 0 || table_doubles < 0 || lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return 0;
-    return (size_t)(WAVE / lanes) * (((size_t)ws_doubles(Nc, Nd, table_doubles) + 1) & ~(size_t)1) * sizeof(double);
+    if (Nc < 0 || Nd < 0 || table_doubles < 0 || !hg::lanes_ok(lanes)) return 0;
+    return hg::wave_lds_bytes(lanes, ws_doubles(Nc, Nd, table_doubles));
 }
 
 int lhvi_gibbs_init(const lhvi_gibbs_t* m, int64_t chains, int32_t* x_d, void* stream) {
-    const int rc = model_check(m);
+    const int rc = hg::gibbs_check(m, hg::ALL_COUNTS);
     if (rc) return rc;
     if (chains < 0 || chains > 0xffffffffLL) return LHVI_E_ARG;
     if (chains == 0 || m->ex.Nd == 0) return LHVI_OK;
@@ -108,19 +89,15 @@ int lhvi_gibbs_init(const lhvi_gibbs_t* m, int64_t chains, int32_t* x_d, void* s
 int lhvi_gibbs_run(const lhvi_gibbs_t* m, int64_t chains, int32_t it_begin, int32_t it_end, int32_t lanes, int32_t* x_d,
                    const double* z, const double* u, int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2,
                    uint64_t* bad, void* stream) {
-    const int rc = model_check(m);
+    int rc = hg::gibbs_check(m, hg::ALL_COUNTS);
     if (rc) return rc;
     if (chains < 0 || chains > 0xffffffffLL || it_begin < 0 || it_end < it_begin || !bad) return LHVI_E_ARG;
-    if (m->ex.Nd && !x_d) return LHVI_E_ARG;
-    if (lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return LHVI_E_ARG;
-    const int disc_doubles = m->max_states + (m->table_scratch ? 0 : m->table_doubles);
-    const size_t lds = lhvi_gibbs_lds_bytes(m->ex.Nc, m->ex.Nd, disc_doubles, lanes);
-    if (lds > 64 * 1024) return LHVI_E_UNSUPPORTED;
-    if (chains == 0 || it_end == it_begin) return LHVI_OK;
-    const int gpb = WAVE / lanes;
-    const int64_t blocks = (chains + gpb - 1) / gpb;
-    if (blocks > 0x7fffffff) return LHVI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(gibbs_chain_kernel, dim3((unsigned)blocks), dim3(WAVE), lds, as_stream(stream), *m, chains, (int)it_begin,
+    if ((m->ex.Nd && !x_d) || !hg::lanes_ok(lanes)) return LHVI_E_ARG;
+    const int64_t work = it_end == it_begin ? 0 : chains;
+    hg::WaveShape sh;
+    rc = hg::wave_shape(work, lanes, ws_doubles(m->ex.Nc, m->ex.Nd, lds_disc_doubles(*m)), sh);
+    if (rc || !work) return rc;
+    hipLaunchKernelGGL(gibbs_chain_kernel, dim3((unsigned)sh.blocks), dim3(WAVE), sh.lds, as_stream(stream), *m, chains, (int)it_begin,
                        (int)it_end, (int)lanes, x_d, z, u, disc, cont, counts, sum1, sum2,
                        reinterpret_cast<unsigned long long*>(bad));
     return check_launch();
@@ -128,21 +105,19 @@ int lhvi_gibbs_run(const lhvi_gibbs_t* m, int64_t chains, int32_t it_begin, int3
 
 int lhvi_gibbs_chain_host(const lhvi_gibbs_t* m, int32_t it_begin, int32_t it_end, int32_t* x_d, const double* z, const double* u,
                           int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2) {
-    const int rc = model_check(m);
+    const int rc = hg::gibbs_check(m, hg::ALL_COUNTS);
     if (rc) return rc;
     const int Nc = m->ex.Nc, Nd = m->ex.Nd;
     if (it_begin < 0 || it_end < it_begin || (Nd && !x_d) || (Nc && !z) || (Nd && m->disc_block_its && !u)) return LHVI_E_ARG;
-    lhvi_gibbs_t g = *m;
-    g.table_scratch = nullptr;
-    double* W = new double[ws_doubles(Nc, Nd, g.max_states + g.table_doubles) + 2];
-    const Workspace w = layout(g, W, nullptr);
-    for (int n = 0; n < Nd; ++n) w.dig[n] = x_d[n];
+    hg::HostWork hw(*m);
+    const lhvi_gibbs_t& g = hw.g;
+    const Workspace w = layout(g, hw.alloc(ws_doubles(Nc, Nd, hw.dd) + 2), nullptr);
+    hw.digits_in(w, x_d);
     const Draws dr{g.seed, z, u, 1, 0, Nc, Nd, g.disc_block_its};
     const Out o{disc, cont, counts, sum1, sum2};
     bool dead = false;
     for (int it = it_begin; it < it_end; ++it) iteration(g, it, dr, w, exact::HostCtx(), dead, o);
-    for (int n = 0; n < Nd; ++n) x_d[n] = w.dig[n];
-    delete[] W;
+    hw.digits_out(w, x_d);
     return dead ? LHVI_E_NOT_PD : LHVI_OK;
 }
 

@@ -7,14 +7,14 @@
 //                            row in sample order; the workspace and the place of the reduced tables of gibbs_chain_kernel
 #include "common.hpp"
 #include "gibbs_rb.hpp"
+#include "hg_launch.hpp"
 
 namespace lhvi {
 namespace gibbs_rb {
 
-struct DevCtx {
-    int lane, lanes;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
+using hg::DevCtx;
+using hg::lds_disc_doubles;
+using hg::lanes_ok;
 
 __global__ void __launch_bounds__(WAVE) exact_config_at_kernel(lhvi_exact_t m, int64_t S, const int32_t* __restrict__ x_d, int lanes,
                                                                double* logp, double* means, double* vars,
@@ -40,7 +40,7 @@ __global__ void __launch_bounds__(WAVE) gibbs_rb_disc_kernel(lhvi_gibbs_t g, int
     const int64_t idx = (int64_t)blockIdx.x * gpb + grp;
     const bool valid = idx < chains;
     const int64_t chain = valid ? idx : chains - 1;             // a padding group repeats the last chain, stores nothing
-    const int ws = (gibbs::ws_doubles(Nc, Nd, g.max_states + (g.table_scratch ? 0 : g.table_doubles)) + 1) & ~1;
+    const int ws = (gibbs::ws_doubles(Nc, Nd, lds_disc_doubles(g)) + 1) & ~1;
     DevCtx ctx{(int)threadIdx.x % lanes, lanes};
     // a padding group has a scratch row of its own (rows are allocated for a multiple of 64 chains)
     const gibbs::Workspace w = gibbs::layout(g, lds + grp * ws, g.table_scratch ? g.table_scratch + idx * g.table_doubles : nullptr);
@@ -48,30 +48,6 @@ __global__ void __launch_bounds__(WAVE) gibbs_rb_disc_kernel(lhvi_gibbs_t g, int
     disc_probs(g, s_begin, s_end, disc + chain * g.num_samples * Nd, cont + chain * g.num_samples * Nc, w, ctx,
                valid ? prob_sum + chain * n_states : nullptr);
 }
-
-// the model of lhvi_exact_configs_at: lhvi_exact_configs' without M and dstride
-static int exact_check(const lhvi_exact_t* m) {
-    if (!m || m->Nd < 0 || m->Nc < 0 || m->n_quad < 0 || m->n_tab < 0) return LHVI_E_ARG;
-    if (m->Nd && !m->dstates) return LHVI_E_ARG;
-    if (m->n_quad && (!m->quad_ptr || !m->quad_desc || !m->quad_par)) return LHVI_E_ARG;
-    if (m->n_tab && (!m->tab_ptr || !m->tab_desc || !m->tab_par)) return LHVI_E_ARG;
-    if (m->Nc > LHVI_EXACT_MAX_NC) return LHVI_E_UNSUPPORTED;
-    return LHVI_OK;
-}
-
-// the model of lhvi_gibbs_rb_disc: what lhvi_gibbs_run asks of the fields this reads
-static int gibbs_check(const lhvi_gibbs_t* g) {
-    if (!g) return LHVI_E_ARG;
-    const int rc = exact_check(&g->ex);
-    if (rc) return rc;
-    if (g->n_hyb < 0 || g->table_doubles < 0 || g->max_states < 1 || g->num_samples < 0) return LHVI_E_ARG;
-    if (g->ex.Nd && (!g->dstate_off || !g->vt_ptr || !g->vh_ptr)) return LHVI_E_ARG;
-    if (g->ex.n_tab && !g->vt_fac) return LHVI_E_ARG;
-    if (g->n_hyb && (!g->hyb_quad || !g->hyb_off || !g->vh_fac)) return LHVI_E_ARG;
-    return LHVI_OK;
-}
-
-static bool lanes_ok(int32_t lanes) { return lanes >= 1 && lanes <= WAVE && !(lanes & (lanes - 1)); }
 
 }  // namespace gibbs_rb
 }  // namespace lhvi
@@ -83,22 +59,19 @@ extern "C" {
 
 int lhvi_exact_configs_at(const lhvi_exact_t* m, int64_t S, const int32_t* x_d, int32_t lanes, double* logp, double* means,
                           double* vars, uint64_t* bad, void* stream) {
-    const int rc = exact_check(m);
+    int rc = hg::exact_check(m);
     if (rc) return rc;
     if (S < 0 || !means || !vars || !bad || (m->Nd && S && !x_d) || !lanes_ok(lanes)) return LHVI_E_ARG;
-    const size_t lds = (size_t)(WAVE / lanes) * ((exact::ws_doubles(m->Nc, m->Nd) + 1) & ~1) * sizeof(double);
-    if (lds > 64 * 1024) return LHVI_E_UNSUPPORTED;
-    if (S == 0) return LHVI_OK;
-    const int gpb = WAVE / lanes;
-    const int64_t blocks = (S + gpb - 1) / gpb;
-    if (blocks > 0x7fffffff) return LHVI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(exact_config_at_kernel, dim3((unsigned)blocks), dim3(WAVE), lds, as_stream(stream), *m, S, x_d, (int)lanes,
+    hg::WaveShape sh;
+    rc = hg::wave_shape(S, lanes, exact::ws_doubles(m->Nc, m->Nd), sh);
+    if (rc || !S) return rc;
+    hipLaunchKernelGGL(exact_config_at_kernel, dim3((unsigned)sh.blocks), dim3(WAVE), sh.lds, as_stream(stream), *m, S, x_d, (int)lanes,
                        logp, means, vars, reinterpret_cast<unsigned long long*>(bad));
     return check_launch();
 }
 
 int lhvi_exact_config_at_host(const lhvi_exact_t* m, const int32_t* x_d_row, double* logp, double* mean, double* var) {
-    const int rc = exact_check(m);
+    const int rc = hg::exact_check(m);
     if (rc) return rc;
     if (m->Nd && !x_d_row) return LHVI_E_ARG;
     for (int n = 0; n < m->Nd; ++n)
@@ -111,28 +84,24 @@ int lhvi_exact_config_at_host(const lhvi_exact_t* m, const int32_t* x_d_row, dou
 
 int lhvi_gibbs_rb_disc(const lhvi_gibbs_t* m, int64_t chains, int32_t s_begin, int32_t s_end, int32_t lanes, const int32_t* disc,
                        const double* cont, double* prob_sum, void* stream) {
-    const int rc = gibbs_check(m);
+    int rc = hg::gibbs_check(m, hg::SAMPLES);        // what lhvi_gibbs_run asks of the fields this reads
     if (rc) return rc;
     if (chains < 0 || chains > 0xffffffffLL || s_begin < 0 || s_end < s_begin || s_end > m->num_samples || !lanes_ok(lanes))
         return LHVI_E_ARG;
     const int Nc = m->ex.Nc, Nd = m->ex.Nd;
-    const size_t lds = (size_t)(WAVE / lanes) *
-                       (((size_t)gibbs::ws_doubles(Nc, Nd, m->max_states + (m->table_scratch ? 0 : m->table_doubles)) + 1) & ~(size_t)1) *
-                       sizeof(double);
-    if (lds > 64 * 1024) return LHVI_E_UNSUPPORTED;
-    if (chains == 0 || s_end == s_begin || Nd == 0) return LHVI_OK;
+    const int64_t work = s_end == s_begin || Nd == 0 ? 0 : chains;
+    hg::WaveShape sh;
+    rc = hg::wave_shape(work, lanes, gibbs::ws_doubles(Nc, Nd, lds_disc_doubles(*m)), sh);
+    if (rc || !work) return rc;
     if (!disc || !prob_sum || (Nc && !cont)) return LHVI_E_ARG;
-    const int gpb = WAVE / lanes;
-    const int64_t blocks = (chains + gpb - 1) / gpb;
-    if (blocks > 0x7fffffff) return LHVI_E_UNSUPPORTED;
-    hipLaunchKernelGGL(gibbs_rb_disc_kernel, dim3((unsigned)blocks), dim3(WAVE), lds, as_stream(stream), *m, chains, (int)s_begin,
+    hipLaunchKernelGGL(gibbs_rb_disc_kernel, dim3((unsigned)sh.blocks), dim3(WAVE), sh.lds, as_stream(stream), *m, chains, (int)s_begin,
                        (int)s_end, (int)lanes, disc, cont, prob_sum);
     return check_launch();
 }
 
 int lhvi_gibbs_rb_disc_host(const lhvi_gibbs_t* m, int32_t s_begin, int32_t s_end, const int32_t* disc, const double* cont,
                             double* prob_sum) {
-    const int rc = gibbs_check(m);
+    const int rc = hg::gibbs_check(m, hg::SAMPLES);
     if (rc) return rc;
     const int Nc = m->ex.Nc, Nd = m->ex.Nd;
     if (s_begin < 0 || s_end < s_begin || s_end > m->num_samples) return LHVI_E_ARG;
@@ -141,11 +110,9 @@ int lhvi_gibbs_rb_disc_host(const lhvi_gibbs_t* m, int32_t s_begin, int32_t s_en
     for (int s = s_begin; s < s_end; ++s)
         for (int n = 0; n < Nd; ++n)
             if (disc[(int64_t)s * Nd + n] < 0 || disc[(int64_t)s * Nd + n] >= m->ex.dstates[n]) return LHVI_E_ARG;
-    lhvi_gibbs_t g = *m;
-    g.table_scratch = nullptr;
-    double* W = new double[gibbs::ws_doubles(Nc, Nd, g.max_states + g.table_doubles) + 2];
-    disc_probs(g, s_begin, s_end, disc, cont, gibbs::layout(g, W, nullptr), exact::HostCtx(), prob_sum);
-    delete[] W;
+    hg::HostWork hw(*m);
+    disc_probs(hw.g, s_begin, s_end, disc, cont, gibbs::layout(hw.g, hw.alloc(gibbs::ws_doubles(Nc, Nd, hw.dd) + 2), nullptr),
+               exact::HostCtx(), prob_sum);
     return LHVI_OK;
 }
 

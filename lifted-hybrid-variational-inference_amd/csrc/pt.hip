@@ -7,6 +7,7 @@
 //                        wavefronts.
 #include "common.hpp"
 #include "pt.hpp"
+#include "hg_launch.hpp"
 
 namespace lhvi {
 namespace pt {
@@ -17,10 +18,8 @@ constexpr int MAX_BLOCK = 256;
 // and takes part in every barrier
 constexpr int NO_LANE = 1 << 30;
 
-struct DevCtx {
-    int lane, lanes;
-    __device__ __forceinline__ void sync() const { __syncthreads(); }
-};
+using hg::DevCtx;
+using hg::lds_disc_doubles;
 
 struct Shape {
     int per_ladder, ladders_per_block, block;
@@ -32,10 +31,6 @@ __host__ __device__ inline Shape shape_of(int R, int lanes) {
     s.ladders_per_block = s.per_ladder <= WAVE / 2 ? WAVE / s.per_ladder : 1;
     s.block = s.ladders_per_block > 1 ? WAVE : (s.per_ladder + WAVE - 1) / WAVE * WAVE;
     return s;
-}
-
-__device__ __forceinline__ int lds_disc_doubles(const lhvi_gibbs_t& g) {
-    return g.max_states + (g.table_scratch ? 0 : g.table_doubles);
 }
 
 // Everything a launch passes beyond the model, as the kernel's SECOND argument (the model is the first, at offset 0 of the
@@ -170,20 +165,6 @@ __global__ void __launch_bounds__(MAX_BLOCK) pt_ladder_kernel(lhvi_gibbs_t, Args
     }
 }
 
-static int model_check(const lhvi_gibbs_t* g) {
-    if (!g) return LHVI_E_ARG;
-    const lhvi_exact_t& m = g->ex;
-    if (m.Nd < 0 || m.Nc < 0 || m.n_quad < 0 || m.n_tab < 0 || g->n_hyb < 0 || g->table_doubles < 0 || g->max_states < 1)
-        return LHVI_E_ARG;
-    if (g->disc_block_its < 0 || g->num_burnin < 0 || g->num_samples < 0) return LHVI_E_ARG;
-    if (m.Nd && (!m.dstates || !g->dstate_off || !g->vt_ptr || !g->vh_ptr)) return LHVI_E_ARG;
-    if (m.n_quad && (!m.quad_ptr || !m.quad_desc || !m.quad_par)) return LHVI_E_ARG;
-    if (m.n_tab && (!m.tab_ptr || !m.tab_desc || !m.tab_par || !g->vt_fac)) return LHVI_E_ARG;
-    if (g->n_hyb && (!g->hyb_quad || !g->hyb_off || !g->vh_fac)) return LHVI_E_ARG;
-    if (m.Nc > LHVI_EXACT_MAX_NC) return LHVI_E_UNSUPPORTED;
-    return LHVI_OK;
-}
-
 static int run_check(const lhvi_gibbs_t* m, int32_t R, const double* betas, int32_t it_begin, int32_t it_end, int32_t swap_every,
                      double tau0, const double* mu0, const int32_t* x_d) {
     if (R < 1 || !betas || it_begin < 0 || it_end < it_begin || swap_every < 0) return LHVI_E_ARG;
@@ -200,7 +181,7 @@ using namespace lhvi::pt;
 extern "C" {
 
 size_t lhvi_pt_lds_bytes(int32_t Nc, int32_t Nd, int32_t table_doubles, int32_t R, int32_t lanes) {
-    if (Nc < 0 || Nd < 0 || table_doubles < 0 || R < 1 || lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return 0;
+    if (Nc < 0 || Nd < 0 || table_doubles < 0 || R < 1 || !hg::lanes_ok(lanes)) return 0;
     if ((int64_t)R * lanes > MAX_BLOCK) return 0;
     return (size_t)shape_of(R, lanes).ladders_per_block * (size_t)pt::ws_doubles(Nc, Nd, table_doubles, R) * sizeof(double);
 }
@@ -209,16 +190,14 @@ int lhvi_pt_run(const lhvi_gibbs_t* m, int64_t ladders, int32_t R, const double*
                 int32_t swap_every, int32_t lanes, double tau0, const double* mu0, int32_t* x_d, const double* z, const double* u,
                 const double* usw, int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2, int32_t* swap_try,
                 int32_t* swap_acc, uint64_t* bad, void* stream) {
-    int rc = pt::model_check(m);
+    int rc = hg::gibbs_check(m, hg::ALL_COUNTS);
     if (rc) return rc;
     rc = run_check(m, R, betas, it_begin, it_end, swap_every, tau0, mu0, x_d);
     if (rc) return rc;
-    if (ladders < 0 || !bad || ladders * (int64_t)R > 0xffffffffLL) return LHVI_E_ARG;
-    if (lanes < 1 || lanes > WAVE || (lanes & (lanes - 1))) return LHVI_E_ARG;
+    if (ladders < 0 || !bad || ladders * (int64_t)R > 0xffffffffLL || !hg::lanes_ok(lanes)) return LHVI_E_ARG;
     if ((int64_t)R * lanes > MAX_BLOCK) return LHVI_E_UNSUPPORTED;
-    const int disc_doubles = m->max_states + (m->table_scratch ? 0 : m->table_doubles);
-    const size_t lds = lhvi_pt_lds_bytes(m->ex.Nc, m->ex.Nd, disc_doubles, R, lanes);
-    if (lds > 64 * 1024) return LHVI_E_UNSUPPORTED;
+    const size_t lds = lhvi_pt_lds_bytes(m->ex.Nc, m->ex.Nd, lds_disc_doubles(*m), R, lanes);
+    if (lds > hg::LDS_LIMIT) return LHVI_E_UNSUPPORTED;
     if (ladders == 0 || it_end == it_begin) return LHVI_OK;
     const Shape sh = shape_of(R, lanes);
     const int64_t blocks = (ladders + sh.ladders_per_block - 1) / sh.ladders_per_block;
@@ -238,7 +217,7 @@ int lhvi_pt_ladder_host(const lhvi_gibbs_t* m, int64_t ladder, int32_t R, const 
                         int32_t swap_every, double tau0, const double* mu0, int32_t* x_d, const double* z, const double* u,
                         const double* usw, int32_t* disc, double* cont, int32_t* counts, double* sum1, double* sum2,
                         int32_t* swap_try, int32_t* swap_acc) {
-    int rc = pt::model_check(m);
+    int rc = hg::gibbs_check(m, hg::ALL_COUNTS);
     if (rc) return rc;
     rc = run_check(m, R, betas, it_begin, it_end, swap_every, tau0, mu0, x_d);
     if (rc) return rc;
@@ -246,11 +225,10 @@ int lhvi_pt_ladder_host(const lhvi_gibbs_t* m, int64_t ladder, int32_t R, const 
     if (ladder < 0 || ladder * (int64_t)R > 0xffffffffLL) return LHVI_E_ARG;
     const bool injected = z || u || usw;
     if (injected && ((Nc && !z) || (Nd && m->disc_block_its && !u) || (R > 1 && swap_every && !usw))) return LHVI_E_ARG;
-    lhvi_gibbs_t g = *m;
-    g.table_scratch = nullptr;
-    const int dd = g.max_states + g.table_doubles;
-    const int cw = chain_doubles(Nc, Nd, dd);
-    double* W = new double[pt::ws_doubles(Nc, Nd, dd, R)];
+    hg::HostWork hw(*m);
+    const lhvi_gibbs_t& g = hw.g;
+    const int dd = hw.dd, cw = chain_doubles(Nc, Nd, dd);
+    double* W = hw.alloc(pt::ws_doubles(Nc, Nd, dd, R));
     const Slots sl = slots(Nc, Nd, dd, R, W);
     gibbs::Workspace* w = new gibbs::Workspace[R];
     gibbs::Draws* dr = new gibbs::Draws[R];
@@ -258,7 +236,7 @@ int lhvi_pt_ladder_host(const lhvi_gibbs_t* m, int64_t ladder, int32_t R, const 
     for (int r = 0; r < R; ++r) {
         w[r] = gibbs::layout(g, W + r * cw, nullptr);
         double* m0 = ais::base_mean(Nc, Nd, dd, W + r * cw);
-        for (int n = 0; n < Nd; ++n) w[r].dig[n] = x_d[r * Nd + n];
+        hw.digits_in(w[r], x_d + r * Nd);
         for (int i = 0; i < Nc; ++i) m0[i] = mu0[i];
         // injected draws are this ladder's rows (z [iters][R][Nc], u [iters][R][its][Nd], usw [iters][max(R - 1, 1)]); the Philox
         // stream is that of ladder `ladder`
@@ -291,12 +269,10 @@ int lhvi_pt_ladder_host(const lhvi_gibbs_t* m, int64_t ladder, int32_t R, const 
                 for (int r = 0; r < R; ++r) decide(Nd, R, it, s, r, sl, sd, w[r].dig, 2 * (int64_t)cw, ctx, swap_try, swap_acc);
         }
     }
-    for (int r = 0; r < R; ++r)
-        for (int n = 0; n < Nd; ++n) x_d[r * Nd + n] = w[r].dig[n];
+    for (int r = 0; r < R; ++r) hw.digits_out(w[r], x_d + r * Nd);
     delete[] base;
     delete[] dr;
     delete[] w;
-    delete[] W;
     return dead ? LHVI_E_NOT_PD : LHVI_OK;
 }
 

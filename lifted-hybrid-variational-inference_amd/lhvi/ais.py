@@ -14,15 +14,13 @@ Out of scope: reverse AIS and bridge sampling, adaptive schedules, weighted-samp
 """
 from __future__ import annotations
 
-import ctypes as C
 import math
 import types
 
 import numpy as np
 
 from . import _abi
-from .exact import MAX_NC
-from .gibbs import LDS_LIMIT, _block_its, _not_pd_message, _seed, default_lanes
+from .gibbs import _block_its, _check_host, _check_states, _dev_ptr, _host_ptr, _Run, _seed
 
 STEPS_PER_LAUNCH = 256          # annealing steps of one launch
 REDUCE_OUT, REDUCE_WS = 9, 8192  # LHVI_AIS_REDUCE_OUT, LHVI_AIS_REDUCE_WS
@@ -76,105 +74,52 @@ def chain_host(gm, x_d, betas, tau0, mu0, disc_block_its=1, z=None, u=None, seed
         z, u = z.reshape(len(z), Nc), u.reshape(len(u), its, Nd)
         if (Nc and z.shape[0] < T) or (Nd and its and u.shape[0] < T):
             raise ValueError('fewer injected draws than steps')
-    arrs = {n: np.ascontiguousarray(a) for n, a in gm.arrays().items()}
-    s = gm.struct(lambda n: C.c_void_p(arrs[n].ctypes.data if arrs[n].size else 0), its, 0, 0, seed)
+    s = gm.host_struct(its, 0, 0, seed)
     r = types.SimpleNamespace(x_d=np.array(x_d, dtype=np.int32).reshape(Nd))
-    if Nd and (r.x_d.min() < 0 or (r.x_d >= ex.dstates).any()):
-        raise ValueError('x_d holds a state outside its variable\'s range')
+    _check_states('x_d', r.x_d, ex.dstates)
     lw = np.array([logw], dtype=np.float64)
-    p = lambda a: a.ctypes.data if a is not None and a.size else None                   # noqa: E731
-    rc = _abi.lib().lhvi_ais_chain_host(s, int(chain), T, betas.ctypes.data, int(t_begin), t_end, tau0, p(mu0), p(r.x_d),
-                                        lw.ctypes.data, p(z), p(u))
-    if rc == _abi.E_NOT_PD:
-        raise ValueError(_not_pd_message(r.x_d))
-    _abi.check(rc)
+    p = _host_ptr
+    _check_host(_abi.lib().lhvi_ais_chain_host(s, int(chain), T, betas.ctypes.data, int(t_begin), t_end, tau0, p(mu0), p(r.x_d),
+                                               lw.ctypes.data, p(z), p(u)), r.x_d)
     r.logw = float(lw[0])
     return r
 
 
-class _AisChains:
+class _AisChains(_Run):
     """`chains` annealing runs on the device.  After ``run()``: x_d [chains, Nd] and logw [chains] as device tensors.
     z / u: injected draws (host arrays [T, chains, Nc] / [T, chains, its, Nd]) for the tests; tables: 'lds' / 'global' forces
     where the reduced tables live (default: LDS when the workspace fits)."""
 
+    LDS_BYTES = 'lhvi_ais_lds_bytes'
+    NOUNS = ('chain', 'step')
+    PER_LAUNCH = ('steps_per_launch', STEPS_PER_LAUNCH)
+    ZERO_FILL_MISSING = True        # like the host twin: a test injects the stream it is about
+
     def __init__(self, gm, chains, betas, tau0, mu0, disc_block_its, seed, lanes=None, init_x_d=None, z=None, u=None, tables=None):
-        ex = gm.ex
-        Nd, Nc = ex.Nd, ex.Nc
         chains = int(chains)
         if chains < 1:
             raise ValueError('chains >= 1 is required')
-        if Nc > MAX_NC:
-            raise ValueError('Nc = %d continuous variables exceed LHVI_EXACT_MAX_NC = %d' % (Nc, MAX_NC))
-        l = _abi.lib()
-        its = _block_its(Nd, disc_block_its)
-        T = betas.size - 1
-        lds_of = lambda lanes, in_lds: int(l.lhvi_ais_lds_bytes(                        # noqa: E731
-            Nc, Nd, gm.max_states + (gm.table_doubles if in_lds else 0), lanes))
-        if lanes is None:
-            lanes = default_lanes(Nc)
-            while lanes < 64 and lds_of(lanes, tables == 'lds') > LDS_LIMIT:
-                lanes *= 2
-        lanes = int(lanes)
-        if lanes < 1 or lanes > 64 or lanes & (lanes - 1):
-            raise ValueError('lanes must be a power of two up to 64')
-        in_lds = lds_of(lanes, True) <= LDS_LIMIT if tables is None else tables == 'lds'
-        if lds_of(lanes, in_lds) > LDS_LIMIT:
-            raise ValueError('a workgroup of %d chains needs %d bytes of LDS, more than %d' % (64 // lanes, lds_of(lanes, in_lds),
-                                                                                            LDS_LIMIT))
-        torch = _abi.require_gpu()
-        scratch_rows = 0 if in_lds else (chains + 63) // 64 * 64
-        self.gm, self.chains, self.lanes, self.in_lds, self.its, self.T = gm, chains, lanes, in_lds, its, T
-        self.t = t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype)) for n, a in gm.arrays().items()})
-        dev = t['dstates'].device
-        self.scratch = None if in_lds else torch.empty(scratch_rows, max(gm.table_doubles, 1), dtype=torch.float64, device=dev)
-        self.s = gm.struct(lambda n: _abi.ptr(t[n]), its, 0, 0, seed, _abi.ptr(self.scratch))
+        self.T = betas.size - 1
+        super().__init__(gm, chains, self.T, disc_block_its, seed, lanes, tables, init_x_d, dict(z=z, u=u))
         self.tau0 = float(tau0)
         self.betas = _abi.to_dev(betas)
-        self.mu0 = _abi.to_dev(mu0 if Nc else np.zeros(1))
-        self.x_d = torch.zeros(chains, Nd, dtype=torch.int32, device=dev)
-        if init_x_d is not None:
-            init = np.asarray(init_x_d, dtype=np.int64)
-            init = np.broadcast_to(init.reshape(init.size // max(Nd, 1) if Nd else 1, Nd), (chains, Nd))
-            if Nd and (init.min() < 0 or (init >= ex.dstates[None, :]).any()):
-                raise ValueError('init_x_d holds a state outside its variable\'s range')
-            self.x_d = _abi.to_dev(np.ascontiguousarray(init, dtype=np.int32))
-        else:
-            _abi.check(l.lhvi_gibbs_init(self.s, chains, _abi.ptr(self.x_d) if Nd else None, _abi.stream_ptr()))
-        self.logw = torch.zeros(chains, dtype=torch.float64, device=dev)
-        self.z = self.u = None
-        if z is not None or u is not None:
-            z = np.ascontiguousarray(np.zeros((T, chains, Nc)) if z is None else z, dtype=np.float64)
-            u = np.ascontiguousarray(np.zeros((T, chains, its, Nd)) if u is None else u, dtype=np.float64)
-            z, u = z.reshape(len(z), chains, Nc), u.reshape(len(u), chains, its, Nd)
-            if (Nc and z.shape[0] < T) or (Nd and its and u.shape[0] < T):
-                raise ValueError('fewer injected draws than steps')
-            self.z = _abi.to_dev(z) if z.size else None
-            self.u = _abi.to_dev(u) if u.size else None
-        self.bad = torch.full((1,), -1, dtype=torch.int64, device=dev)          # UINT64_MAX
-        self.done = 0
+        self.mu0 = _abi.to_dev(mu0 if gm.ex.Nc else np.zeros(1))
+
+    def _device_bytes(self, keep_samples):
+        return None                 # a state and a weight per chain: never checked against the free memory (kept as it was)
+
+    def _alloc_outputs(self, torch, dev, keep_samples):
+        self.logw = torch.zeros(self.chains, dtype=torch.float64, device=dev)
+
+    def _streams(self):
+        return ('z', (self.chains, self.gm.ex.Nc)), ('u', (self.chains, self.its, self.gm.ex.Nd))
 
     def advance(self, t_end):
-        """steps [done, t_end) in one launch"""
-        p = lambda a: _abi.ptr(a) if a is not None and a.numel() else None              # noqa: E731
+        p = _dev_ptr
         _abi.check(_abi.lib().lhvi_ais_run(self.s, self.chains, self.T, _abi.ptr(self.betas), self.done, int(t_end), self.lanes,
                                            self.tau0, _abi.ptr(self.mu0), p(self.x_d), _abi.ptr(self.logw), p(self.z), p(self.u),
                                            _abi.ptr(self.bad), _abi.stream_ptr()))
         self.done = int(t_end)
-
-    def run(self, steps_per_launch=None):
-        step = STEPS_PER_LAUNCH if steps_per_launch is None else int(steps_per_launch)
-        if step < 1:
-            raise ValueError('steps_per_launch must be positive')
-        while self.done < self.T:
-            self.advance(min(self.T, self.done + step))
-        self.check()
-        return self
-
-    def check(self):
-        first = int(self.bad.item())
-        if first != -1:
-            chain = (first & (2 ** 64 - 1)) >> 32
-            raise ValueError(_not_pd_message(self.x_d[chain].cpu().numpy()) + ' (chain %d, step %d)' % (chain, first & 0xffffffff))
 
 
 def reduce(logw):

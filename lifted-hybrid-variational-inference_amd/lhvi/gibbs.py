@@ -39,6 +39,7 @@ from .potentials import LogTable
 
 LDS_LIMIT = 64 * 1024
 ITS_PER_LAUNCH = 256            # outer iterations of one launch
+MAX_BLOCK = 256                 # threads of a workgroup: the replicas of a ladder times their lanes may not exceed it
 
 
 # ---- host: flat model -> sampler model ----------------------------------------------------------------------------------------------
@@ -96,6 +97,14 @@ class GibbsModel:
         out.update({n: getattr(self, n) for n in self.FIELDS})
         return out
 
+    def host_struct(self, disc_block_its, num_burnin, num_samples, seed):
+        """``struct`` over the host arrays, which it keeps alive (``ExactModel.host_struct``): the model of a host twin"""
+        arrs = {n: np.ascontiguousarray(a) for n, a in self.arrays().items()}
+        s = self.struct(lambda n: C.c_void_p(arrs[n].ctypes.data if arrs[n].size else 0), disc_block_its, num_burnin, num_samples,
+                        seed)
+        s._keep = arrs
+        return s
+
 
 def _block_its(Nd, disc_block_its):
     """one sweep samples p(x_d | x_c) exactly when there is one discrete variable (:167-168)"""
@@ -106,6 +115,29 @@ def _block_its(Nd, disc_block_its):
 
 def _not_pd_message(state):
     return 'the precision matrix J = -2A is not positive definite at the discrete state %r' % (tuple(int(s) for s in state),)
+
+
+def _host_ptr(a):
+    """the address of a host array for a twin's call (None: no array, or an empty one)"""
+    return a.ctypes.data if a is not None and a.size else None
+
+
+def _dev_ptr(t):
+    """the address of a device tensor for a launch (None: no tensor, or an empty one)"""
+    return _abi.ptr(t) if t is not None and t.numel() else None
+
+
+def _check_states(what, x, dstates):
+    """x [..., Nd]: every digit inside its variable's range"""
+    if x.size and (x.min() < 0 or (x >= np.asarray(dstates)).any()):
+        raise ValueError('%s holds a state outside its variable\'s range' % what)
+
+
+def _check_host(rc, state):
+    """the return code of a host twin: ``LHVI_E_NOT_PD`` names the discrete state it happened at"""
+    if rc == _abi.E_NOT_PD:
+        raise ValueError(_not_pd_message(state))
+    _abi.check(rc)
 
 
 def chain_host(gm, x_d, z, u, disc_block_its, num_burnin, num_samples, it_begin=0, it_end=None):
@@ -119,20 +151,15 @@ def chain_host(gm, x_d, z, u, disc_block_its, num_burnin, num_samples, it_begin=
     u = np.ascontiguousarray(u, dtype=np.float64).reshape(len(u), its, Nd)
     if (Nc and z.shape[0] < it_end) or (Nd and its and u.shape[0] < it_end):
         raise ValueError('fewer injected draws than iterations')
-    arrs = {n: np.ascontiguousarray(a) for n, a in gm.arrays().items()}
-    s = gm.struct(lambda n: C.c_void_p(arrs[n].ctypes.data if arrs[n].size else 0), its, num_burnin, num_samples, 0)
+    s = gm.host_struct(its, num_burnin, num_samples, 0)
     r = types.SimpleNamespace(
         disc=np.zeros((num_samples, Nd), dtype=np.int32), cont=np.zeros((num_samples, Nc)),
         counts=np.zeros(gm.n_states, dtype=np.int32), sum1=np.zeros(Nc), sum2=np.zeros(Nc * (Nc + 1) // 2),
         x_d=np.array(x_d, dtype=np.int32).reshape(Nd))
-    if Nd and (r.x_d.min() < 0 or (r.x_d >= ex.dstates).any()):
-        raise ValueError('x_d holds a state outside its variable\'s range')
-    p = lambda a: a.ctypes.data if a.size else None                                     # noqa: E731
-    rc = _abi.lib().lhvi_gibbs_chain_host(s, int(it_begin), int(it_end), p(r.x_d), p(z), p(u), p(r.disc), p(r.cont), p(r.counts),
-                                          p(r.sum1), p(r.sum2))
-    if rc == _abi.E_NOT_PD:
-        raise ValueError(_not_pd_message(r.x_d))
-    _abi.check(rc)
+    _check_states('x_d', r.x_d, ex.dstates)
+    p = _host_ptr
+    _check_host(_abi.lib().lhvi_gibbs_chain_host(s, int(it_begin), int(it_end), p(r.x_d), p(z), p(u), p(r.disc), p(r.cont),
+                                                 p(r.counts), p(r.sum1), p(r.sum2)), r.x_d)
     return r
 
 
@@ -146,12 +173,10 @@ def rb_disc_host(gm, disc, cont, s_begin=0, s_end=None, prob_sum=None):
     disc = np.ascontiguousarray(disc, dtype=np.int32).reshape(num_samples, Nd)
     cont = np.ascontiguousarray(cont, dtype=np.float64).reshape(num_samples, Nc)
     s_end = num_samples if s_end is None else int(s_end)
-    if Nd and disc.size and (disc.min() < 0 or (disc >= ex.dstates[None, :]).any()):
-        raise ValueError('disc holds a state outside its variable\'s range')
-    arrs = {n: np.ascontiguousarray(a) for n, a in gm.arrays().items()}
-    s = gm.struct(lambda n: C.c_void_p(arrs[n].ctypes.data if arrs[n].size else 0), 1, 0, num_samples, 0)
+    _check_states('disc', disc, ex.dstates)
+    s = gm.host_struct(1, 0, num_samples, 0)
     out = np.zeros(gm.n_states) if prob_sum is None else np.ascontiguousarray(prob_sum, dtype=np.float64).reshape(gm.n_states)
-    p = lambda a: a.ctypes.data if a.size else None                                     # noqa: E731
+    p = _host_ptr
     _abi.check(_abi.lib().lhvi_gibbs_rb_disc_host(s, int(s_begin), s_end, p(disc), p(cont), p(out)))
     return out
 
@@ -165,6 +190,38 @@ def default_lanes(Nc):
     return lanes
 
 
+def place(lds_bytes, Nc, Nd, max_states, table_doubles, lanes=None, tables=None, R=None):
+    """(lanes, in_lds) of a run: the lanes of a chain and whether its reduced tables live in LDS.  ``lds_bytes``: the sampler's
+    ``lhvi_*_lds_bytes`` (a host function of the library: this needs no device); ``tables``: 'lds' / 'global' forces the place;
+    ``R``: the replicas of a ladder, None for the plain and the annealed sampler.  Without ``lanes`` a chain gets
+    ``default_lanes(Nc)``: doubled while a workgroup of chains is over 64 KiB (sized with the tables in LDS only when they are
+    forced there), or halved while the R replicas of a ladder exceed a workgroup's threads and never grown (the tables leave LDS
+    before a ladder is refused).  Raises ``ValueError`` for lanes that are no power of two up to 64 and for a workgroup that is
+    still too large."""
+    shape = () if R is None else (R,)
+    lds_of = lambda lanes, in_lds: int(lds_bytes(Nc, Nd, max_states + (table_doubles if in_lds else 0), *shape, lanes))  # noqa: E731
+    if R is not None and R > MAX_BLOCK:
+        raise ValueError('%d replicas exceed the %d threads of a workgroup' % (R, MAX_BLOCK))
+    if lanes is None and R is None:
+        lanes = default_lanes(Nc)
+        while lanes < 64 and lds_of(lanes, tables == 'lds') > LDS_LIMIT:
+            lanes *= 2
+    elif lanes is None:
+        lanes = default_lanes(Nc)
+        while lanes > 1 and R * lanes > MAX_BLOCK:
+            lanes //= 2
+    lanes = int(lanes)
+    if lanes < 1 or lanes > 64 or lanes & (lanes - 1):
+        raise ValueError('lanes must be a power of two up to 64')
+    if R is not None and R * lanes > MAX_BLOCK:
+        raise ValueError('%d replicas of %d lanes exceed the %d threads of a workgroup' % (R, lanes, MAX_BLOCK))
+    in_lds = lds_of(lanes, True) <= LDS_LIMIT if tables is None else tables == 'lds'
+    if lds_of(lanes, in_lds) > LDS_LIMIT:
+        raise ValueError('a workgroup of %d %s needs %d bytes of LDS, more than %d'
+                         % (((64 // lanes, 'chains') if R is None else (R, 'replicas')) + (lds_of(lanes, in_lds), LDS_LIMIT)))
+    return lanes, in_lds
+
+
 def output_bytes(gm, chains, num_samples, keep_samples):
     """device bytes of the outputs of a run: the state, the accumulators (, the samples)"""
     Nd, Nc = gm.ex.Nd, gm.ex.Nc
@@ -172,93 +229,151 @@ def output_bytes(gm, chains, num_samples, keep_samples):
     return n + (chains * num_samples * (4 * Nd + 8 * Nc) if keep_samples else 0)
 
 
-class _Chains:
+class _Run:
+    """The run layer under the plain, the annealed and the tempered sampler: `units` chains (or ladders of R replicas, a chain
+    each) of ``gm`` on the device.  It decides the lanes and the place of the reduced tables (``place``, before a device is asked
+    for), uploads the model (``t``, ``scratch``, ``s``), starts the states ``x_d`` (given, or drawn on the device), uploads the
+    injected draws, and runs ``total`` iterations in launches of ``advance``, which a subclass supplies with what else differs:
+
+    LDS_BYTES   its ``lhvi_*_lds_bytes``
+    NOUNS       what an error message calls a unit and an iteration
+    PER_LAUNCH  the name and the default of ``run``'s argument
+    _device_bytes / _alloc_outputs / _streams / _bad_state   (below)"""
+
+    LDS_BYTES = None
+    NOUNS = ('chain', 'iteration')
+    PER_LAUNCH = ('its_per_launch', ITS_PER_LAUNCH)
+    # An injected stream that is missing while another is given: zeros in its place, or (the plain sampler, which takes both
+    # streams or neither; kept for compatibility) the error of converting None.
+    ZERO_FILL_MISSING = False
+    # An injected stream nothing reads (no x_c, no sweep): no pointer, or a placeholder of one double.
+    PLACEHOLDER = False
+
+    def __init__(self, gm, units, total, disc_block_its, seed, lanes, tables, init_x_d, draws, num_burnin=0, num_samples=0,
+                 keep_samples=False, R=None):
+        ex = gm.ex
+        Nd, Nc = ex.Nd, ex.Nc
+        if Nc > MAX_NC:
+            raise ValueError('Nc = %d continuous variables exceed LHVI_EXACT_MAX_NC = %d' % (Nc, MAX_NC))
+        l = _abi.lib()
+        its = _block_its(Nd, disc_block_its)
+        lanes, in_lds = place(getattr(l, self.LDS_BYTES), Nc, Nd, gm.max_states, gm.table_doubles, lanes, tables, R)
+        torch = _abi.require_gpu()
+        chains = units * (1 if R is None else R)
+        scratch_rows = 0 if in_lds else (chains + 63) // 64 * 64       # rb_disc pads its chains to 64
+        self.gm, self.chains, self.lanes, self.in_lds, self.its, self.total = gm, units, lanes, in_lds, its, total
+        self.num_burnin, self.num_samples = num_burnin, num_samples
+        need = self._device_bytes(keep_samples)
+        if need is not None:
+            need, what = need[0] + 8 * scratch_rows * gm.table_doubles, need[1]
+            free = int(torch.cuda.mem_get_info()[0])
+            if need > free:
+                raise MemoryError('%s (Nd = %d, Nc = %d) need %d bytes of device memory, %d are free' % (what, Nd, Nc, need, free))
+        self.t = t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype)) for n, a in gm.arrays().items()})
+        dev = t['dstates'].device
+        self.scratch = None if in_lds else torch.empty(scratch_rows, max(gm.table_doubles, 1), dtype=torch.float64, device=dev)
+        self.s = gm.struct(lambda n: _abi.ptr(t[n]), its, num_burnin, num_samples, seed, _abi.ptr(self.scratch))
+        if init_x_d is not None:
+            init = np.asarray(init_x_d, dtype=np.int64)
+            init = np.broadcast_to(init.reshape(init.size // max(Nd, 1) if Nd else 1, Nd), (chains, Nd))
+            _check_states('init_x_d', init, ex.dstates)
+            x_d = _abi.to_dev(np.ascontiguousarray(init, dtype=np.int32))
+        else:
+            x_d = torch.zeros(chains, Nd, dtype=torch.int32, device=dev)
+            _abi.check(l.lhvi_gibbs_init(self.s, chains, _abi.ptr(x_d) if Nd else None, _abi.stream_ptr()))
+        self.x_d = x_d if R is None else x_d.reshape(units, R, Nd)
+        self._alloc_outputs(torch, dev, keep_samples)
+        streams = self._streams()
+        for name, _ in streams:
+            setattr(self, name, None)
+        if any(draws[name] is not None for name, _ in streams):
+            given = []
+            for name, shape in streams:
+                a = np.zeros((total,) + shape) if draws[name] is None and self.ZERO_FILL_MISSING else draws[name]
+                given.append(np.ascontiguousarray(a, dtype=np.float64))
+            given = [a.reshape((len(a),) + shape) for a, (_, shape) in zip(given, streams)]
+            if any(a.shape[0] < total for a in given if all(a.shape[1:])):          # (a stream with an empty row is not read)
+                raise ValueError('fewer injected draws than %ss' % self.NOUNS[1])
+            for a, (name, _) in zip(given, streams):
+                setattr(self, name, _abi.to_dev(a) if a.size else _abi.to_dev(np.zeros(1)) if self.PLACEHOLDER else None)
+        self.bad = torch.full((1,), -1, dtype=torch.int64, device=dev)          # UINT64_MAX
+        self.done = 0
+
+    def _device_bytes(self, keep_samples):
+        """(the device bytes of the outputs, how the error names the run), or None for no check against the free memory"""
+        raise NotImplementedError
+
+    def _alloc_outputs(self, torch, dev, keep_samples):
+        raise NotImplementedError
+
+    def _streams(self):
+        """((attribute, the shape of one iteration's row), ...) of the injected draws"""
+        raise NotImplementedError
+
+    def advance(self, end):
+        """iterations [done, end) in one launch"""
+        raise NotImplementedError
+
+    def _bad_state(self, unit):
+        """the discrete state an error names for a unit whose precision matrix was not positive definite"""
+        return self.x_d[unit].cpu().numpy()
+
+    def run(self, per_launch=None):
+        step = self.PER_LAUNCH[1] if per_launch is None else int(per_launch)
+        if step < 1:
+            raise ValueError('%s must be positive' % self.PER_LAUNCH[0])
+        while self.done < self.total:
+            self.advance(min(self.total, self.done + step))
+        self.check()
+        return self
+
+    def check(self):
+        first = int(self.bad.item())
+        if first != -1:
+            unit = (first & (2 ** 64 - 1)) >> 32
+            raise ValueError(_not_pd_message(self._bad_state(unit)) + ' (%s %d, %s %d)'
+                             % (self.NOUNS[0], unit, self.NOUNS[1], first & 0xffffffff))
+
+
+class _Chains(_Run):
     """`chains` chains on the device.  After ``run()``: x_d [chains, Nd], counts [chains, sum dstates], sum1 [chains, Nc],
     sum2 [chains, Nc (Nc + 1) / 2] and, with keep_samples, disc [chains, num_samples, Nd] / cont [chains, num_samples, Nc]
     as device tensors.  z / u: injected draws (host arrays [iters, chains, Nc] / [iters, chains, its, Nd]) for the tests;
     tables: 'lds' / 'global' forces where the reduced tables live (default: LDS when the workspace fits)."""
 
+    LDS_BYTES = 'lhvi_gibbs_lds_bytes'
+
     def __init__(self, gm, chains, num_burnin, num_samples, disc_block_its, seed, keep_samples=False, lanes=None, init_x_d=None,
                  z=None, u=None, tables=None):
-        ex = gm.ex
-        Nd, Nc = ex.Nd, ex.Nc
         chains, num_burnin, num_samples = int(chains), int(num_burnin), int(num_samples)
         if chains < 1 or num_burnin < 0 or num_samples < 0:
             raise ValueError('chains >= 1, num_burnin >= 0 and num_samples >= 0 are required')
-        if Nc > MAX_NC:
-            raise ValueError('Nc = %d continuous variables exceed LHVI_EXACT_MAX_NC = %d' % (Nc, MAX_NC))
-        l = _abi.lib()
-        its = _block_its(Nd, disc_block_its)
-        lds_of = lambda lanes, in_lds: int(l.lhvi_gibbs_lds_bytes(                      # noqa: E731
-            Nc, Nd, gm.max_states + (gm.table_doubles if in_lds else 0), lanes))
-        if lanes is None:
-            lanes = default_lanes(Nc)
-            while lanes < 64 and lds_of(lanes, tables == 'lds') > LDS_LIMIT:
-                lanes *= 2
-        lanes = int(lanes)
-        if lanes < 1 or lanes > 64 or lanes & (lanes - 1):
-            raise ValueError('lanes must be a power of two up to 64')
-        in_lds = lds_of(lanes, True) <= LDS_LIMIT if tables is None else tables == 'lds'
-        if lds_of(lanes, in_lds) > LDS_LIMIT:
-            raise ValueError('a workgroup of %d chains needs %d bytes of LDS, more than %d' % (64 // lanes, lds_of(lanes, in_lds),
-                                                                                            LDS_LIMIT))
-        torch = _abi.require_gpu()
-        scratch_rows = 0 if in_lds else (chains + 63) // 64 * 64
-        need = output_bytes(gm, chains, num_samples, keep_samples) + 8 * scratch_rows * gm.table_doubles
-        free = int(torch.cuda.mem_get_info()[0])
-        if need > free:
-            raise MemoryError('%d chains of %d kept samples (Nd = %d, Nc = %d) need %d bytes of device memory, %d are free'
-                              % (chains, num_samples, Nd, Nc, need, free))
-        self.gm, self.chains, self.lanes, self.in_lds = gm, chains, lanes, in_lds
-        self.num_burnin, self.num_samples, self.its = num_burnin, num_samples, its
-        self.t = t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype)) for n, a in gm.arrays().items()})
-        dev = t['dstates'].device
-        self.scratch = None if in_lds else torch.empty(scratch_rows, max(gm.table_doubles, 1), dtype=torch.float64, device=dev)
-        self.s = gm.struct(lambda n: _abi.ptr(t[n]), its, num_burnin, num_samples, seed, _abi.ptr(self.scratch))
+        super().__init__(gm, chains, num_burnin + num_samples, disc_block_its, seed, lanes, tables, init_x_d, dict(z=z, u=u),
+                         num_burnin, num_samples, keep_samples)
+
+    def _device_bytes(self, keep_samples):
+        return (output_bytes(self.gm, self.chains, self.num_samples, keep_samples),
+                '%d chains of %d kept samples' % (self.chains, self.num_samples))
+
+    def _alloc_outputs(self, torch, dev, keep_samples):
+        gm, n, S = self.gm, self.chains, self.num_samples
+        Nd, Nc = gm.ex.Nd, gm.ex.Nc
         f64, i32 = torch.float64, torch.int32
-        self.x_d = torch.zeros(chains, Nd, dtype=i32, device=dev)
-        if init_x_d is not None:
-            init = np.asarray(init_x_d, dtype=np.int64)
-            init = np.broadcast_to(init.reshape(init.size // max(Nd, 1) if Nd else 1, Nd), (chains, Nd))
-            if Nd and (init.min() < 0 or (init >= ex.dstates[None, :]).any()):
-                raise ValueError('init_x_d holds a state outside its variable\'s range')
-            self.x_d = _abi.to_dev(np.ascontiguousarray(init, dtype=np.int32))
-        else:
-            _abi.check(l.lhvi_gibbs_init(self.s, chains, _abi.ptr(self.x_d) if Nd else None, _abi.stream_ptr()))
-        self.counts = torch.zeros(chains, gm.n_states, dtype=i32, device=dev)
-        self.sum1 = torch.zeros(chains, Nc, dtype=f64, device=dev)
-        self.sum2 = torch.zeros(chains, Nc * (Nc + 1) // 2, dtype=f64, device=dev)
-        self.disc = torch.zeros(chains, num_samples, Nd, dtype=i32, device=dev) if keep_samples else None
-        self.cont = torch.zeros(chains, num_samples, Nc, dtype=f64, device=dev) if keep_samples else None
-        iters = num_burnin + num_samples
-        self.z = self.u = None
-        if z is not None or u is not None:
-            z = np.ascontiguousarray(z, dtype=np.float64).reshape(len(z), chains, Nc)
-            u = np.ascontiguousarray(u, dtype=np.float64).reshape(len(u), chains, its, Nd)
-            if (Nc and z.shape[0] < iters) or (Nd and its and u.shape[0] < iters):
-                raise ValueError('fewer injected draws than iterations')
-            self.z = _abi.to_dev(z) if z.size else None
-            self.u = _abi.to_dev(u) if u.size else None
-        self.bad = torch.full((1,), -1, dtype=torch.int64, device=dev)          # UINT64_MAX
-        self.done = 0
+        self.counts = torch.zeros(n, gm.n_states, dtype=i32, device=dev)
+        self.sum1 = torch.zeros(n, Nc, dtype=f64, device=dev)
+        self.sum2 = torch.zeros(n, Nc * (Nc + 1) // 2, dtype=f64, device=dev)
+        self.disc = torch.zeros(n, S, Nd, dtype=i32, device=dev) if keep_samples else None
+        self.cont = torch.zeros(n, S, Nc, dtype=f64, device=dev) if keep_samples else None
+
+    def _streams(self):
+        return ('z', (self.chains, self.gm.ex.Nc)), ('u', (self.chains, self.its, self.gm.ex.Nd))
 
     def advance(self, it_end):
-        """iterations [done, it_end) in one launch"""
-        p = lambda a: _abi.ptr(a) if a is not None and a.numel() else None              # noqa: E731
+        p = _dev_ptr
         _abi.check(_abi.lib().lhvi_gibbs_run(self.s, self.chains, self.done, int(it_end), self.lanes, p(self.x_d), p(self.z),
                                              p(self.u), p(self.disc), p(self.cont), p(self.counts), p(self.sum1), p(self.sum2),
                                              _abi.ptr(self.bad), _abi.stream_ptr()))
         self.done = int(it_end)
-
-    def run(self, its_per_launch=None):
-        step = ITS_PER_LAUNCH if its_per_launch is None else int(its_per_launch)
-        if step < 1:
-            raise ValueError('its_per_launch must be positive')
-        iters = self.num_burnin + self.num_samples
-        while self.done < iters:
-            self.advance(min(iters, self.done + step))
-        self.check()
-        return self
 
     def rb_disc(self, s_begin=0, s_end=None, prob_sum=None, lanes=None):
         """prob_sum [chains, sum dstates] (device tensor, zeros when not given) += the conditional probabilities
@@ -271,18 +386,10 @@ class _Chains:
             prob_sum = torch.zeros(self.chains, max(self.gm.n_states, 1), dtype=torch.float64, device=self.x_d.device)
         if prob_sum.shape != (self.chains, max(self.gm.n_states, 1)) or prob_sum.dtype != torch.float64 or not prob_sum.is_contiguous():
             raise ValueError('prob_sum must be a contiguous float64 tensor [chains, sum dstates]')
-        p = lambda a: _abi.ptr(a) if a is not None and a.numel() else None              # noqa: E731
         _abi.check(_abi.lib().lhvi_gibbs_rb_disc(self.s, self.chains, int(s_begin), self.num_samples if s_end is None else int(s_end),
-                                                 self.lanes if lanes is None else int(lanes), p(self.disc), p(self.cont),
+                                                 self.lanes if lanes is None else int(lanes), _dev_ptr(self.disc), _dev_ptr(self.cont),
                                                  _abi.ptr(prob_sum), _abi.stream_ptr()))
         return prob_sum
-
-    def check(self):
-        first = int(self.bad.item())
-        if first != -1:
-            chain = (first & (2 ** 64 - 1)) >> 32
-            raise ValueError(_not_pd_message(self.x_d[chain].cpu().numpy()) + ' (chain %d, iteration %d)'
-                             % (chain, first & 0xffffffff))
 
 
 def _seed(seed):
@@ -440,8 +547,7 @@ class HybridGaussianSampler:
         first one wins on ties.  A dict: config (state indices), xd (domain values), xc, energy, sample (its row)."""
         model = flatten_factors(self.factors, self.dstates, len(self.Vc))
         disc = np.asarray(self.disc_samples)
-        if disc.size and (disc.min() < 0 or (disc >= np.asarray(self.dstates)[None, :]).any()):
-            raise ValueError('disc_samples holds a state outside its variable\'s range')
+        _check_states('disc_samples', disc, self.dstates)
         t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype)) for n, a in ((n, getattr(model, n)) for n in ExactModel.FIELDS)})
         e = hg_energy.energies(model.struct(lambda n: _abi.ptr(t[n])), x_d=_abi.to_dev(disc.astype(np.int32)),
                                x_c=_abi.to_dev(np.asarray(self.cont_samples, dtype=np.float64)))

@@ -16,17 +16,13 @@ tempering for ``FlatGraph`` models.
 """
 from __future__ import annotations
 
-import ctypes as C
 import types
 
 import numpy as np
 
 from . import _abi
 from .ais import base
-from .exact import MAX_NC
-from .gibbs import ITS_PER_LAUNCH, LDS_LIMIT, _block_its, _Chains, _not_pd_message, default_lanes, output_bytes
-
-MAX_BLOCK = 256                 # threads of a workgroup: replicas * lanes may not exceed it
+from .gibbs import MAX_BLOCK, _block_its, _Chains, _check_host, _check_states, _dev_ptr, _host_ptr, _Run, output_bytes, place  # noqa: F401
 
 
 def schedule(replicas=None, betas=None):
@@ -77,8 +73,7 @@ def ladder_host(gm, x_d, betas, tau0, mu0, disc_block_its, num_burnin, num_sampl
         z, u, usw = z.reshape(len(z), R, Nc), u.reshape(len(u), R, its, Nd), usw.reshape(len(usw), max(R - 1, 1))
         if (Nc and z.shape[0] < it_end) or (Nd and its and u.shape[0] < it_end) or usw.shape[0] < it_end:
             raise ValueError('fewer injected draws than iterations')
-    arrs = {n: np.ascontiguousarray(a) for n, a in gm.arrays().items()}
-    s = gm.struct(lambda n: C.c_void_p(arrs[n].ctypes.data if arrs[n].size else 0), its, num_burnin, num_samples, seed)
+    s = gm.host_struct(its, num_burnin, num_samples, seed)
     if state is None:
         r = types.SimpleNamespace(
             disc=np.zeros((num_samples, Nd), dtype=np.int32), cont=np.zeros((num_samples, Nc)),
@@ -89,15 +84,12 @@ def ladder_host(gm, x_d, betas, tau0, mu0, disc_block_its, num_burnin, num_sampl
     if x_d is not None or state is None:
         rows = np.asarray(x_d, dtype=np.int32)
         r.x_d = np.array(np.broadcast_to(rows.reshape(rows.size // Nd if Nd else 1, Nd), (R, Nd)), order='C')      # a copy
-    if Nd and (r.x_d.min() < 0 or (r.x_d >= ex.dstates[None, :]).any()):
-        raise ValueError('x_d holds a state outside its variable\'s range')
-    p = lambda a: a.ctypes.data if a is not None and a.size else None                   # noqa: E731
+    _check_states('x_d', r.x_d, ex.dstates)
+    p = _host_ptr
     rc = _abi.lib().lhvi_pt_ladder_host(s, int(ladder), R, betas.ctypes.data, int(it_begin), it_end, swap_every, tau0, p(mu0),
                                         p(r.x_d), p(z), p(u), p(usw), p(r.disc), p(r.cont), p(r.counts), p(r.sum1), p(r.sum2),
                                         p(r.swap_try), p(r.swap_acc))
-    if rc == _abi.E_NOT_PD:
-        raise ValueError(_not_pd_message(_failed_state(gm, r.x_d)))
-    _abi.check(rc)
+    _check_host(rc, _failed_state(gm, r.x_d) if rc == _abi.E_NOT_PD else None)
     return r
 
 
@@ -120,123 +112,60 @@ class _Ladders(_Chains):
     (host arrays [iters, ladders * R, Nc] / [iters, ladders * R, its, Nd] / [iters, ladders, max(R - 1, 1)]) for the tests;
     tables: 'lds' / 'global' forces where the reduced tables live (default: LDS when the workgroup fits)."""
 
+    LDS_BYTES = 'lhvi_pt_lds_bytes'
+    NOUNS = ('ladder', 'iteration')
+    ZERO_FILL_MISSING = True        # like the host twin: a test injects the stream it is about
+    PLACEHOLDER = True              # a stream that is not read still has to be there when another is injected: the kernel
+                                    # takes one non-null stream for "all are injected" and tests each pointer alone
+
     def __init__(self, gm, ladders, betas, tau0, mu0, num_burnin, num_samples, disc_block_its, swap_every, seed, keep_samples=False,
                  lanes=None, init_x_d=None, z=None, u=None, usw=None, tables=None):
-        ex = gm.ex
-        Nd, Nc = ex.Nd, ex.Nc
         ladders, num_burnin, num_samples = int(ladders), int(num_burnin), int(num_samples)
         if ladders < 1 or num_burnin < 0 or num_samples < 0:
             raise ValueError('ladders >= 1, num_burnin >= 0 and num_samples >= 0 are required')
-        if Nc > MAX_NC:
-            raise ValueError('Nc = %d continuous variables exceed LHVI_EXACT_MAX_NC = %d' % (Nc, MAX_NC))
-        R = int(betas.size)
-        l = _abi.lib()
-        its = _block_its(Nd, disc_block_its)
-        lds_of = lambda lanes, in_lds: int(l.lhvi_pt_lds_bytes(                         # noqa: E731
-            Nc, Nd, gm.max_states + (gm.table_doubles if in_lds else 0), R, lanes))
-        if R > MAX_BLOCK:
-            raise ValueError('%d replicas exceed the %d threads of a workgroup' % (R, MAX_BLOCK))
-        if lanes is None:
-            # the plain sampler's lanes, fewer when the replicas would not fit a workgroup; the tables leave LDS before a
-            # ladder is refused
-            lanes = default_lanes(Nc)
-            while lanes > 1 and R * lanes > MAX_BLOCK:
-                lanes //= 2
-        lanes = int(lanes)
-        if lanes < 1 or lanes > 64 or lanes & (lanes - 1):
-            raise ValueError('lanes must be a power of two up to 64')
-        if R * lanes > MAX_BLOCK:
-            raise ValueError('%d replicas of %d lanes exceed the %d threads of a workgroup' % (R, lanes, MAX_BLOCK))
-        in_lds = lds_of(lanes, True) <= LDS_LIMIT if tables is None else tables == 'lds'
-        if lds_of(lanes, in_lds) > LDS_LIMIT:
-            raise ValueError('a workgroup of %d replicas needs %d bytes of LDS, more than %d' % (R, lds_of(lanes, in_lds), LDS_LIMIT))
-        torch = _abi.require_gpu()
-        scratch_rows = 0 if in_lds else (ladders * R + 63) // 64 * 64      # rb_disc pads its chains to 64
-        need = output_bytes(gm, ladders, num_samples, keep_samples) + 4 * ladders * (R * Nd + 2 * R) + 8 * scratch_rows * gm.table_doubles
-        free = int(torch.cuda.mem_get_info()[0])
-        if need > free:
-            raise MemoryError('%d ladders of %d replicas and %d kept samples (Nd = %d, Nc = %d) need %d bytes of device memory, %d '
-                              'are free' % (ladders, R, num_samples, Nd, Nc, need, free))
-        self.gm, self.chains, self.ladders, self.R, self.lanes, self.in_lds = gm, ladders, ladders, R, lanes, in_lds
-        self.num_burnin, self.num_samples, self.its, self.swap_every = num_burnin, num_samples, its, _swap_every(swap_every)
-        self.t = t = _abi.upload({n: (a if a.size else np.zeros(1, dtype=a.dtype)) for n, a in gm.arrays().items()})
-        dev = t['dstates'].device
-        self.scratch = None if in_lds else torch.empty(scratch_rows, max(gm.table_doubles, 1), dtype=torch.float64, device=dev)
-        self.s = gm.struct(lambda n: _abi.ptr(t[n]), its, num_burnin, num_samples, seed, _abi.ptr(self.scratch))
+        self.ladders, self.R = ladders, int(betas.size)
+        # (not _Chains.__init__: that is the plain sampler's arguments; _Chains lends the outputs and rb_disc)
+        _Run.__init__(self, gm, ladders, num_burnin + num_samples, disc_block_its, seed, lanes, tables, init_x_d,
+                      dict(z=z, u=u, usw=usw), num_burnin, num_samples, keep_samples, self.R)
+        self.swap_every = _swap_every(swap_every)
         self.tau0, self.betas_host = float(tau0), betas
         self.betas = _abi.to_dev(betas)
-        self.mu0 = _abi.to_dev(mu0 if Nc else np.zeros(1))
-        f64, i32 = torch.float64, torch.int32
-        self.x_d = torch.zeros(ladders, R, Nd, dtype=i32, device=dev)
-        if init_x_d is not None:
-            init = np.asarray(init_x_d, dtype=np.int64)
-            init = np.broadcast_to(init.reshape(init.size // max(Nd, 1) if Nd else 1, Nd), (ladders * R, Nd))
-            if Nd and (init.min() < 0 or (init >= ex.dstates[None, :]).any()):
-                raise ValueError('init_x_d holds a state outside its variable\'s range')
-            self.x_d = _abi.to_dev(np.ascontiguousarray(init, dtype=np.int32).reshape(ladders, R, Nd))
-        else:
-            _abi.check(l.lhvi_gibbs_init(self.s, ladders * R, _abi.ptr(self.x_d) if Nd else None, _abi.stream_ptr()))
-        self.counts = torch.zeros(ladders, gm.n_states, dtype=i32, device=dev)
-        self.sum1 = torch.zeros(ladders, Nc, dtype=f64, device=dev)
-        self.sum2 = torch.zeros(ladders, Nc * (Nc + 1) // 2, dtype=f64, device=dev)
-        self.disc = torch.zeros(ladders, num_samples, Nd, dtype=i32, device=dev) if keep_samples else None
-        self.cont = torch.zeros(ladders, num_samples, Nc, dtype=f64, device=dev) if keep_samples else None
-        self.swap_try = torch.zeros(ladders, R - 1, dtype=i32, device=dev)
-        self.swap_acc = torch.zeros(ladders, R - 1, dtype=i32, device=dev)
-        iters = num_burnin + num_samples
-        self.z = self.u = self.usw = None
-        if z is not None or u is not None or usw is not None:
-            z = np.ascontiguousarray(np.zeros((iters, ladders * R, Nc)) if z is None else z, dtype=np.float64)
-            u = np.ascontiguousarray(np.zeros((iters, ladders * R, its, Nd)) if u is None else u, dtype=np.float64)
-            usw = np.ascontiguousarray(np.zeros((iters, ladders, max(R - 1, 1))) if usw is None else usw, dtype=np.float64)
-            z, u = z.reshape(len(z), ladders * R, Nc), u.reshape(len(u), ladders * R, its, Nd)
-            usw = usw.reshape(len(usw), ladders, max(R - 1, 1))
-            if (Nc and z.shape[0] < iters) or (Nd and its and u.shape[0] < iters) or usw.shape[0] < iters:
-                raise ValueError('fewer injected draws than iterations')
-            # a stream that is not read still has to be there when another is injected: the kernel tests each pointer alone
-            self.z = _abi.to_dev(z if z.size else np.zeros(1))
-            self.u = _abi.to_dev(u if u.size else np.zeros(1))
-            self.usw = _abi.to_dev(usw)
-        self.bad = torch.full((1,), -1, dtype=torch.int64, device=dev)          # UINT64_MAX
-        self.done = 0
+        self.mu0 = _abi.to_dev(mu0 if gm.ex.Nc else np.zeros(1))
+
+    def _device_bytes(self, keep_samples):
+        return (output_bytes(self.gm, self.ladders, self.num_samples, keep_samples)
+                + 4 * self.ladders * (self.R * self.gm.ex.Nd + 2 * self.R),
+                '%d ladders of %d replicas and %d kept samples' % (self.ladders, self.R, self.num_samples))
+
+    def _alloc_outputs(self, torch, dev, keep_samples):
+        super()._alloc_outputs(torch, dev, keep_samples)
+        self.swap_try = torch.zeros(self.ladders, self.R - 1, dtype=torch.int32, device=dev)
+        self.swap_acc = torch.zeros(self.ladders, self.R - 1, dtype=torch.int32, device=dev)
+
+    def _streams(self):
+        n, Nd, Nc = self.ladders * self.R, self.gm.ex.Nd, self.gm.ex.Nc
+        return ('z', (n, Nc)), ('u', (n, self.its, Nd)), ('usw', (self.ladders, max(self.R - 1, 1)))
 
     def advance(self, it_end):
-        """iterations [done, it_end) in one launch"""
-        p = lambda a: _abi.ptr(a) if a is not None and a.numel() else None              # noqa: E731
+        p = _dev_ptr
         _abi.check(_abi.lib().lhvi_pt_run(self.s, self.ladders, self.R, _abi.ptr(self.betas), self.done, int(it_end), self.swap_every,
                                           self.lanes, self.tau0, _abi.ptr(self.mu0), p(self.x_d), p(self.z), p(self.u), p(self.usw),
                                           p(self.disc), p(self.cont), p(self.counts), p(self.sum1), p(self.sum2), p(self.swap_try),
                                           p(self.swap_acc), _abi.ptr(self.bad), _abi.stream_ptr()))
         self.done = int(it_end)
 
-    def run(self, its_per_launch=None):
-        step = ITS_PER_LAUNCH if its_per_launch is None else int(its_per_launch)
-        if step < 1:
-            raise ValueError('its_per_launch must be positive')
-        iters = self.num_burnin + self.num_samples
-        while self.done < iters:
-            self.advance(min(iters, self.done + step))
-        self.check()
-        return self
-
     def rb_disc(self, s_begin=0, s_end=None, prob_sum=None, lanes=None):
         """``_Chains.rb_disc`` over the beta = 1 replica's kept samples; lanes default to the plain sampler's choice (a ladder's
-        lanes are sized for R replicas a workgroup)"""
+        lanes are sized for R replicas a workgroup) with the tables where the ladder's are (one chain of 64 lanes fits where a
+        ladder did, so this never refuses)"""
         if lanes is None:
-            l = _abi.lib()
-            Nc, Nd = self.gm.ex.Nc, self.gm.ex.Nd
-            dd = self.gm.max_states + (self.gm.table_doubles if self.in_lds else 0)
-            lanes = default_lanes(Nc)
-            while lanes < 64 and int(l.lhvi_gibbs_lds_bytes(Nc, Nd, dd, lanes)) > LDS_LIMIT:
-                lanes *= 2
+            gm = self.gm
+            lanes = place(_abi.lib().lhvi_gibbs_lds_bytes, gm.ex.Nc, gm.ex.Nd, gm.max_states, gm.table_doubles,
+                          tables='lds' if self.in_lds else 'global')[0]
         return super().rb_disc(s_begin, s_end, prob_sum, lanes)
 
-    def check(self):
-        first = int(self.bad.item())
-        if first != -1:
-            ladder = (first & (2 ** 64 - 1)) >> 32
-            raise ValueError(_not_pd_message(_failed_state(self.gm, self.x_d[ladder].cpu().numpy()))
-                             + ' (ladder %d, iteration %d)' % (ladder, first & 0xffffffff))
+    def _bad_state(self, ladder):
+        return _failed_state(self.gm, self.x_d[ladder].cpu().numpy())
 
     def swap_counts(self):
         """(tried [R - 1], accepted [R - 1]) summed over the ladders, as int64 host arrays"""
