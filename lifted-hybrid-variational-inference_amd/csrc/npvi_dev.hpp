@@ -1,6 +1,7 @@
 // npvi_dev.hpp -- the device side that csrc/npvi.hip and csrc/oneshot.hip share: the factor kernel (with its switch for the
-// Bethe-free-energy expectant), the fixed-order block reduction, the gather kernels (with their switch for what is added to the
-// edges' sums), the argument checks and the step of the update.  npvi_colsum_kernel and npvi_update_kernel are defined in npvi.hip.
+// Bethe-free-energy expectant) and its launch, the fixed-order block reduction and the gather kernels (with their switch for what
+// is added to the edges' sums).  npvi_colsum_kernel and npvi_update_kernel are defined in npvi.hip.  The host side the two share --
+// workspace, checks, the Adam loops, the entry points' bodies -- is csrc/npvi_run.hpp.
 #pragma once
 #include "common.hpp"
 #include "npvi.hpp"
@@ -142,29 +143,6 @@ __global__ void __launch_bounds__(BLOCK) npvi_gather_hub_kernel(lhvi_graph_t g, 
         }
     }
     if (lane == 0) gather_finish<BFE>(g, p, var_count, SS, v, m, vi, c0, c1, g_c, g_rho);
-}
-
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-inline int check_args(const lhvi_graph_t* g, const lhvi_pots_t* pots, const lhvi_vi_t* p, const double* obj, const double* g_tau,
-                      const double* g_c, const double* g_rho) {
-    if (!g || !pots || !p || !obj || !g_tau || !g_c || !g_rho) return LHVI_E_ARG;
-    if (p->K < 1 || p->K > LHVI_NPVI_MAX_K || p->T < 1 || p->Dmax < 1 || g->V < 1 || g->F < 0) return LHVI_E_ARG;
-    if (!p->gh_x || !p->gh_w || !p->w || !p->eta_c || !p->eta_d || (g->E > 0 && !p->edge_axis) || p->obs_var) return LHVI_E_ARG;
-    return LHVI_OK;
-}
-
-inline int check_opt(const lhvi_npvi_opt_t* o, int32_t iterations) {
-    if (!o || iterations < 0) return LHVI_E_ARG;
-    if (!o->tau || !o->theta_c || !o->rho || !o->m_tau || !o->s_tau || !o->m_c || !o->s_c || !o->m_rho || !o->s_rho || !o->g_tau ||
-        !o->g_c || !o->g_rho || !o->obj || !o->w || !o->eta_c || !o->eta_d || !o->mu_lo || !o->mu_hi)
-        return LHVI_E_ARG;
-    return LHVI_OK;
-}
-
-inline Step make_step(const lhvi_npvi_opt_t* o, int it, int32_t fix_mix_its) {
-    const double t = (double)(o->t + it + 1);
-    return Step{o->lr * sqrt(1.0 - pow(o->b2, t)) / (1.0 - pow(o->b1, t)), o->b1, o->b2, o->eps, it < fix_mix_its ? 1 : 0};
 }
 
 template <int SL, int MA, bool INTERP, bool BFE = false>

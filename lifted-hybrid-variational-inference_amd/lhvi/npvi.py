@@ -66,6 +66,8 @@ class NPVI(_Variational):
     _param_names = ('tau', 'theta_c', 'rho')
     belief_normaliser = 'gaussian'      # the components are normal densities: what MixtureBelief.from_solver and every query evaluate
     adam_eps = 1e-8                     # tf.train.AdamOptimizer's epsilon
+    _stem = 'npvi'                      # the entry points are lhvi_<stem>_{workspace_bytes, grad, run, grad_host, run_host}
+    _extra = ()                         # the solver's own [V] input arrays (attributes), after fac_count in grad, after the options in run
 
     @staticmethod
     def norm_pdf(x, eta):
@@ -210,10 +212,12 @@ class NPVI(_Variational):
                      fac_count=None if self.fac_count is None else _abi.to_dev(self.fac_count))
             for name, a in self._h.items():
                 d[name] = _abi.to_dev(a)
+            for name in self._extra:
+                d[name] = _abi.to_dev(getattr(self, name))
             for name in self._param_names:
                 d['g_' + name] = torch.zeros_like(d[name])
             self._dev = d
-            ws_bytes = int(_abi.lib().lhvi_npvi_workspace_bytes(self.dg.g, self._struct()))
+            ws_bytes = int(self._entry('workspace_bytes')(self.dg.g, self._struct()))
             d['ws'] = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=self.dg.device)
             d['ws_bytes'] = ws_bytes
             self._dirty = False
@@ -251,25 +255,37 @@ class NPVI(_Variational):
             self._h[name] = np.ascontiguousarray(d[name].cpu().numpy())
         self._cache = {}
 
+    def _entry(self, what):
+        return getattr(_abi.lib(), 'lhvi_%s_%s' % (self._stem, what))
+
     # ---- objective and gradient -------------------------------------------------------------------------------------------
     def grad(self, host=False):
         """``(obj, g_tau [K], g_c [V, K, 2] = (d / d Mu, d / d lVar), g_rho [V, K, Dmax])``: the negative ELBO at the current
         parameters and the gradient of the reference's auxiliary objective"""
-        l = _abi.lib()
         flat, K = self.flat, self.K
         if host:
             out = dict(obj=np.zeros(1), g_tau=np.zeros(K), g_c=np.zeros((flat.V, K, 2)), g_rho=np.zeros((flat.V, K, self.Dmax)))
             p = self._host_struct()
-            _abi.check(l.lhvi_npvi_grad_host(self._hg.g, self._hg.p, p, _np_ptr(self.var_count), _np_ptr(self.fac_count),
-                                             _np_ptr(out['obj']), _np_ptr(out['g_tau']), _np_ptr(out['g_c']), _np_ptr(out['g_rho'])))
+            _abi.check(self._entry('grad_host')(self._hg.g, self._hg.p, p, _np_ptr(self.var_count), _np_ptr(self.fac_count),
+                                                *[_np_ptr(getattr(self, name)) for name in self._extra], _np_ptr(out['obj']),
+                                                _np_ptr(out['g_tau']), _np_ptr(out['g_c']), _np_ptr(out['g_rho'])))
             return float(out['obj'][0]), out['g_tau'], out['g_c'], out['g_rho']
         d = self._ensure_dev()
-        _abi.check(l.lhvi_npvi_grad(self.dg.g, self.dg.p, self._struct(), _abi.ptr(d['var_count']), _abi.ptr(d['fac_count']),
-                                    int(self.max_slots), int(self.max_arity), _abi.ptr(d['obj']), _abi.ptr(d['g_tau']), _abi.ptr(d['g_theta_c']),
-                                    _abi.ptr(d['g_rho']), _abi.ptr(d['ws']), d['ws_bytes'], _abi.stream_ptr()))
+        _abi.check(self._entry('grad')(self.dg.g, self.dg.p, self._struct(), _abi.ptr(d['var_count']), _abi.ptr(d['fac_count']),
+                                       *[_abi.ptr(d[name]) for name in self._extra], int(self.max_slots), int(self.max_arity),
+                                       _abi.ptr(d['obj']), _abi.ptr(d['g_tau']), _abi.ptr(d['g_theta_c']), _abi.ptr(d['g_rho']),
+                                       _abi.ptr(d['ws']), d['ws_bytes'], _abi.stream_ptr()))
         return (float(d['obj'].item()), d['g_tau'].cpu().numpy(), d['g_theta_c'].cpu().numpy(), d['g_rho'].cpu().numpy())
 
     # ---- optimisation -----------------------------------------------------------------------------------------------------
+    def _enqueue(self, n, lr, fix_mix_its, log_dev):
+        """enqueues `n` updates on the current stream, the objective before each into ``log_dev[:n]``; the host copies go stale"""
+        d = self._ensure_dev()
+        o = self._opt_struct(d, _abi.ptr, lr)
+        _abi.check(self._entry('run')(self.dg.g, self.dg.p, self._struct(), C.byref(o), *[_abi.ptr(d[name]) for name in self._extra],
+                                      n, fix_mix_its, _abi.ptr(log_dev), _abi.ptr(d['ws']), d['ws_bytes'], _abi.stream_ptr()))
+        self.t += n
+
     def run(self, its=100, lr=5e-2, fix_mix_its=0, host=False):
         """NPVI.run (NPVI.py:184-319): `its` updates of TensorFlow's Adam from the current parameters (the Adam state continues
         across calls; ``set_params`` / ``init_param`` reset it).  ``fix_mix_its``: the mixture weights stay uniform during that many
@@ -282,7 +298,6 @@ class NPVI(_Variational):
         if fix_mix_its == 'all':
             fix_mix_its = its
         fix_mix_its = int(fix_mix_its)
-        l = _abi.lib()
         if host:
             log = np.zeros(max(its, 1))
             h = dict(self._h)
@@ -291,19 +306,18 @@ class NPVI(_Variational):
                      fac_count=self.fac_count)
             p = self._host_struct()
             o = self._opt_struct(h, _np_ptr, lr)
-            _abi.check(l.lhvi_npvi_run_host(self._hg.g, self._hg.p, p, C.byref(o), its, fix_mix_its, _np_ptr(log)))
+            _abi.check(self._entry('run_host')(self._hg.g, self._hg.p, p, C.byref(o), *[_np_ptr(getattr(self, name)) for name in self._extra],
+                                               its, fix_mix_its, _np_ptr(log)))
             self._dirty = True
             self._cache = {}
+            self.t += its
         else:
             torch = _abi.require_gpu()
-            d = self._ensure_dev()
+            self._ensure_dev()
             log_dev = torch.zeros(max(its, 1), dtype=torch.float64, device=self.dg.device)
-            o = self._opt_struct(d, _abi.ptr, lr)
-            _abi.check(l.lhvi_npvi_run(self.dg.g, self.dg.p, self._struct(), C.byref(o), its, fix_mix_its, _abi.ptr(log_dev),
-                                       _abi.ptr(d['ws']), d['ws_bytes'], _abi.stream_ptr()))
+            self._enqueue(its, lr, fix_mix_its, log_dev)
             log = log_dev.cpu().numpy()
             self._download()
-        self.t += its
         return self._result([float(x) for x in log[:its]])
 
     def _result(self, obj):

@@ -39,20 +39,11 @@ def measure(label, flat, K, T, updates):
                 updates_per_window=updates)
     s = NPVI(flat, K, T, seed=0)
     s._ensure_dev()
-    import ctypes as C
-    from lhvi import _abi
-    d, l = s._dev, _abi.lib()
     log = torch.zeros(updates, dtype=torch.float64, device=s.dg.device)
-
-    def npvi_loop(n):
-        o = s._opt_struct(d, _abi.ptr, 0.05)
-        _abi.check(l.lhvi_npvi_run(s.dg.g, s.dg.p, s._struct(), C.byref(o), n, 0, _abi.ptr(log), _abi.ptr(d['ws']), d['ws_bytes'],
-                                   _abi.stream_ptr()))
-        s.t += n
-    t_npvi, w_npvi = timed(npvi_loop, updates)
+    t_npvi, w_npvi = timed(lambda n: s._enqueue(n, 0.05, 0, log), updates)
     obj = float(log[updates - 1].item())
     kernel = 'interpreter' if s.dg.p.interpreted or s.max_arity > 3 else ('lean, 8 slots' if s.max_slots <= 8 else 'lean, 24 slots')
-    del s, d, log
+    del s, log
     torch.cuda.empty_cache()
 
     vi = VarInference(None, K, T)

@@ -6,7 +6,6 @@ is bench.py).  Writes profiles/oneshot_bench.json and prints one JSON line per m
     python scripts/bench_oneshot.py [--updates 20] [--copies 286] [--out profiles/oneshot_bench.json] [--small] [--only-k2]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -15,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, 'lifted-hybrid-variational-inference_amd')]
 import numpy as np
 import torch
-from lhvi import _abi, synth
+from lhvi import synth
 from lhvi.npvi import NPVI
 from lhvi.oneshot import OneShot
 from lhvi.vi import VarInference
@@ -39,23 +38,12 @@ def timed(fn, updates, reps=3):
 def time_solver(cls, flat, K, T, updates):
     s = cls(flat, K, T, seed=0)
     s._ensure_dev()
-    d, l = s._dev, _abi.lib()
     log = torch.zeros(updates, dtype=torch.float64, device=s.dg.device)
-
-    def loop(n):
-        o = s._opt_struct(d, _abi.ptr, 0.05)
-        if cls is OneShot:
-            _abi.check(l.lhvi_oneshot_run(s.dg.g, s.dg.p, s._struct(), C.byref(o), _abi.ptr(d['var_coef']), n, 0, _abi.ptr(log),
-                                          _abi.ptr(d['ws']), d['ws_bytes'], _abi.stream_ptr()))
-        else:
-            _abi.check(l.lhvi_npvi_run(s.dg.g, s.dg.p, s._struct(), C.byref(o), n, 0, _abi.ptr(log), _abi.ptr(d['ws']), d['ws_bytes'],
-                                       _abi.stream_ptr()))
-        s.t += n
-    t, w = timed(loop, updates)
+    t, w = timed(lambda n: s._enqueue(n, 0.05, 0, log), updates)
     obj = float(log[updates - 1].item())
     kernel = 'interpreter' if s.dg.p.interpreted or s.max_arity > 3 else ('lean, 8 slots' if s.max_slots <= 8 else 'lean, 24 slots')
     skipped = int((s.var_coef[s.flat.var_hidden] == 0).sum()) if cls is OneShot else None
-    del s, d, log
+    del s, log
     torch.cuda.empty_cache()
     return t, w, obj, kernel, skipped
 

@@ -325,8 +325,51 @@ def high_arity_graph(seed=9):
     return _graph([a, b, x, y, z, o1, o2], fs)
 
 
+def long_chain(n=1025):
+    """n continuous variables of degree 2 and 3.  At n = 1 025 the reductions over the variables take five blocks of 256, the last one
+    holding a single variable; at K = 2 OneShot's variable kernel takes 128 variables a block -- nine blocks, the last one holding a
+    single group"""
+    rvs = [RV(cdom()) for _ in range(n)]
+    unary = [QuadraticPotential(np.array([[-0.5 - 0.05 * i]]), np.array([0.3 * i - 0.6]), 0.0) for i in range(5)]
+    pair = [QuadraticPotential(np.array([[-0.4, a], [a, -0.6]]), np.array([0.1, -0.1]), 0.0) for a in (0.25, -0.2, 0.1)]
+    fs = [F(unary[i % 5], nb=[rvs[i]]) for i in range(n)] + [F(pair[i % 3], nb=[rvs[i], rvs[i + 1]]) for i in range(n - 1)]
+    return _graph(rvs, fs)
+
+
+def hub_graph(deg=70):
+    """one variable of degree 70 (> LHVI_HUB_DEGREE = 64; OneShot's kappa = -69): its gather takes the wavefront path; the leaves
+    have degree 1 (OneShot's variable kernel skips them)"""
+    hub = RV(cdom())
+    leaves = [RV(cdom()) for _ in range(deg - 1)]
+    pair = QuadraticPotential(np.array([[-0.05, 0.02], [0.02, -0.6]]), np.array([0.01, -0.2]), 0.0)
+    fs = [F(pair, nb=[hub, x]) for x in leaves] + [F(QuadraticPotential(np.array([[-0.4]]), np.array([0.2]), 0.0), nb=[hub])]
+    return _graph([hub] + leaves, fs)
+
+
 def start_params(tw, seed, spread=1.0):
     """a random start in the solver's layout: (tau [K], Mu [V, K], lVar [V, K], Rho [V, K, Dmax])"""
     rng = np.random.RandomState(seed)
     V, K = len(tw.rvs), tw.K
     return rng.randn(K) * 0.5, rng.randn(V, K) * spread, np.log(rng.uniform(0.2, 2.0, size=(V, K))), rng.randn(V, K, tw.Dmax)
+
+
+# ---- comparisons the host and the GPU modules of NPVI and OneShot share ---------------------------------------------------------
+def assert_close(got, want, tol, what):
+    scale = max(float(np.max(np.abs(want))), 1e-300)
+    err = float(np.max(np.abs(np.asarray(got) - np.asarray(want)))) / scale
+    assert err <= tol, '%s: %.3g of the largest entry %.3g' % (what, err, scale)
+
+
+def param_diff(s, tw):
+    h = s._h
+    cont, mask = s._cont[:, None], s._mask_d[:, None, :]
+    return max(float(np.max(np.abs(h['tau'] - tw.tau.detach().numpy()))),
+               float(np.max(np.abs(np.where(cont, h['theta_c'][:, :, 0] - tw.Mu.detach().numpy(), 0.0)))),
+               float(np.max(np.abs(np.where(cont, h['theta_c'][:, :, 1] - tw.lVar.detach().numpy(), 0.0)))),
+               float(np.max(np.abs(np.where(mask, h['rho'] - tw.Rho.detach().numpy(), 0.0)))))
+
+
+def device_bits(s):
+    """the bytes of every device array of a solver, the workspace included, of its host copies, and its update count"""
+    dev = {n: a.cpu().numpy().tobytes() for n, a in s._dev.items() if isinstance(a, torch.Tensor)}
+    return dev, {n: a.tobytes() for n, a in s._h.items()}, s.t

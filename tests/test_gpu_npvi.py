@@ -9,39 +9,18 @@ import pytest
 
 import npvi_models as nm
 import test_npvi_host as th
-from lhvi import mixture
-from lhvi.graph import RV, F
+from lhvi import _abi, mixture
 from lhvi.mixture import MixtureBelief
 from lhvi.npvi import NPVI, LiftedNPVI
-from lhvi.potentials import QuadraticPotential
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
 
 
-def long_chain(n=1025):
-    """1 025 continuous variables: five blocks of 256 in the entropy reduction, the last one holding a single variable"""
-    rng = np.random.RandomState(12)
-    rvs = [RV(nm.cdom()) for _ in range(n)]
-    unary = [QuadraticPotential(np.array([[-0.5 - 0.05 * i]]), np.array([0.3 * i - 0.6]), 0.0) for i in range(5)]
-    pair = [QuadraticPotential(np.array([[-0.4, a], [a, -0.6]]), np.array([0.1, -0.1]), 0.0) for a in (0.25, -0.2, 0.1)]
-    fs = [F(unary[i % 5], nb=[rvs[i]]) for i in range(n)] + [F(pair[i % 3], nb=[rvs[i], rvs[i + 1]]) for i in range(n - 1)]
-    return nm._graph(rvs, fs), rng
-
-
-def hub_graph(deg=70):
-    """one variable of degree 70 (> LHVI_HUB_DEGREE = 64): its gather takes the wavefront path"""
-    hub = RV(nm.cdom())
-    leaves = [RV(nm.cdom()) for _ in range(deg - 1)]
-    pair = QuadraticPotential(np.array([[-0.05, 0.02], [0.02, -0.6]]), np.array([0.01, -0.2]), 0.0)
-    fs = [F(pair, nb=[hub, x]) for x in leaves] + [F(QuadraticPotential(np.array([[-0.4]]), np.array([0.2]), 0.0), nb=[hub])]
-    return nm._graph([hub] + leaves, fs)
-
-
 @functools.lru_cache(maxsize=None)
 def shape_case(name):
     """(solver, twin reference) of a launch-shape case, computed once"""
-    g = long_chain()[0] if name == 'chain1025' else hub_graph()
+    g = nm.long_chain() if name == 'chain1025' else nm.hub_graph()
     K = 2 if name == 'chain1025' else 3
     tw, s = nm.Twin(g, K, 3), NPVI(g, K, 3)
     params = nm.start_params(tw, 21, spread=0.5)
@@ -109,6 +88,23 @@ def test_gaussian_optimum_on_the_device():
                                                     np.max(np.abs(res['Var'][:, 0] - 1 / np.diag(J)))))
     np.testing.assert_allclose(res['Mu'][:, 0], np.linalg.solve(J, h), rtol=0, atol=1e-8)
     np.testing.assert_allclose(res['Var'][:, 0], 1 / np.diag(J), rtol=0, atol=1e-8)
+
+
+def test_device_entry_points_refuse_a_short_workspace_before_any_launch():
+    """lhvi_npvi_grad and lhvi_npvi_run with ws_bytes one short: LHVI_E_ARG, and no array of the solver has changed"""
+    s = NPVI(nm.gaussian_chain(5), 2, 3, seed=3)
+    d = s._ensure_dev()
+    assert d['ws_bytes'] == _abi.lib().lhvi_npvi_workspace_bytes(s.dg.g, s._struct()) > 0
+    before = nm.device_bits(s)
+    d['ws_bytes'] -= 1
+    with pytest.raises(_abi.LhviError):
+        s.grad()
+    with pytest.raises(_abi.LhviError):
+        s.run(its=2, lr=0.05)
+    assert nm.device_bits(s) == before
+    d['ws_bytes'] += 1
+    assert len(s.run(its=2, lr=0.05)['record']['obj']) == 2 and s.t == 2
+    assert nm.device_bits(s) != before
 
 
 def fitted_hybrid(its=30):

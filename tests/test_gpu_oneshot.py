@@ -10,40 +10,18 @@ import pytest
 import npvi_models as nm
 import oneshot_models as om
 import test_oneshot_host as th
-from lhvi import mixture
-from lhvi.graph import RV, F
+from lhvi import _abi, mixture
 from lhvi.mixture import MixtureBelief
 from lhvi.oneshot import OneShot, LiftedOneShot
-from lhvi.potentials import QuadraticPotential
 
 pytestmark = pytest.mark.gpu
 U = 2.0 ** -53
 
 
-def long_chain(n=1025):
-    """1 025 continuous variables of degree 2 and 3: at K = 2 the variable kernel takes 128 variables a block -- nine blocks, the
-    last one holding a single group -- and the column sums five blocks of 256"""
-    rvs = [RV(nm.cdom()) for _ in range(n)]
-    unary = [QuadraticPotential(np.array([[-0.5 - 0.05 * i]]), np.array([0.3 * i - 0.6]), 0.0) for i in range(5)]
-    pair = [QuadraticPotential(np.array([[-0.4, a], [a, -0.6]]), np.array([0.1, -0.1]), 0.0) for a in (0.25, -0.2, 0.1)]
-    fs = [F(unary[i % 5], nb=[rvs[i]]) for i in range(n)] + [F(pair[i % 3], nb=[rvs[i], rvs[i + 1]]) for i in range(n - 1)]
-    return nm._graph(rvs, fs)
-
-
-def hub_graph(deg=70):
-    """one variable of degree 70 (> LHVI_HUB_DEGREE = 64, kappa = -69): its gather takes the wavefront path; the leaves have
-    degree 1 and are skipped"""
-    hub = RV(nm.cdom())
-    leaves = [RV(nm.cdom()) for _ in range(deg - 1)]
-    pair = QuadraticPotential(np.array([[-0.05, 0.02], [0.02, -0.6]]), np.array([0.01, -0.2]), 0.0)
-    fs = [F(pair, nb=[hub, x]) for x in leaves] + [F(QuadraticPotential(np.array([[-0.4]]), np.array([0.2]), 0.0), nb=[hub])]
-    return nm._graph([hub] + leaves, fs)
-
-
 SHAPES = {
-    'chain1025': (long_chain, 2, 3),
-    'hub70': (hub_graph, 3, 3),                     # K = 3: an idle lane in a KP = 4 group
-    'chain67-K16': (lambda: long_chain(67), 16, 3),          # five blocks of 16 groups, the last one of three
+    'chain1025': (nm.long_chain, 2, 3),
+    'hub70': (nm.hub_graph, 3, 3),                     # K = 3: an idle lane in a KP = 4 group
+    'chain67-K16': (lambda: nm.long_chain(67), 16, 3),          # five blocks of 16 groups, the last one of three
     'hybrid-T1': (lambda: nm.hybrid_graph(seed=5), 3, 1),
     'leaves_only': (om.leaves_only_graph, 2, 3),    # every hidden variable has degree 1: all rows skipped
     'isolated': (om.isolated_graph, 3, 3),
@@ -112,6 +90,37 @@ def test_gaussian_optimum_on_the_device():
                                                     np.max(np.abs(res['Var'][:, 0] - 1 / np.diag(J)))))
     np.testing.assert_allclose(res['Mu'][:, 0], np.linalg.solve(J, h), rtol=0, atol=1e-8)
     np.testing.assert_allclose(res['Var'][:, 0], 1 / np.diag(J), rtol=0, atol=1e-8)
+
+
+def test_one_workspace_sized_by_the_solvers_own_entry_point():
+    s = OneShot(nm.gaussian_chain(5), 2, 3)
+    d = s._ensure_dev()
+    import torch
+    need = int(_abi.lib().lhvi_oneshot_workspace_bytes(s.dg.g, s._struct()))
+    assert need > int(_abi.lib().lhvi_npvi_workspace_bytes(s.dg.g, s._struct())) > 0
+    byte_tensors = [n for n, a in d.items() if isinstance(a, torch.Tensor) and a.dtype == torch.uint8]
+    assert byte_tensors == ['ws'] and d['ws'].numel() == max(need, 256) and d['ws_bytes'] == need
+    assert np.array_equal(d['var_coef'].cpu().numpy(), s.var_coef)
+
+
+def test_device_entry_points_refuse_bad_arguments_before_any_launch():
+    """lhvi_oneshot_grad and lhvi_oneshot_run with ws_bytes one short, and with a null var_coef: LHVI_E_ARG, and no array of the
+    solver has changed"""
+    s = OneShot(nm.gaussian_chain(5), 2, 3, seed=3)
+    d = s._ensure_dev()
+    before = nm.device_bits(s)
+    coef = d['var_coef']
+    for break_it, mend in ((lambda: d.update(ws_bytes=d['ws_bytes'] - 1), lambda: d.update(ws_bytes=d['ws_bytes'] + 1)),
+                           (lambda: d.update(var_coef=None), lambda: d.update(var_coef=coef))):
+        break_it()
+        with pytest.raises(_abi.LhviError):
+            s.grad()
+        with pytest.raises(_abi.LhviError):
+            s.run(its=2, lr=0.05)
+        mend()
+        assert nm.device_bits(s) == before
+    assert len(s.run(its=2, lr=0.05)['record']['obj']) == 2 and s.t == 2
+    assert nm.device_bits(s) != before
 
 
 def fitted_hybrid(its=30):

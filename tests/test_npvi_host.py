@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import npvi_models as nm
+from npvi_models import assert_close, param_diff
 from lhvi import _abi
 from lhvi.npvi import NPVI, LiftedNPVI
 
@@ -41,12 +42,6 @@ def build(name, K, T):
     tw = nm.Twin(g, K, T, **kw)
     s = NPVI(g, K, T, **kw)
     return g, tw, s
-
-
-def assert_close(got, want, tol, what):
-    scale = max(float(np.max(np.abs(want))), 1e-300)
-    err = float(np.max(np.abs(np.asarray(got) - np.asarray(want)))) / scale
-    assert err <= tol, '%s: %.3g of the largest entry %.3g' % (what, err, scale)
 
 
 def compare_grad(s, tw, host, tol=GRAD_TOL):
@@ -90,15 +85,6 @@ def run_case():
     tau, Mu, lVar, Rho = nm.start_params(tw, 3)
     Mu = Mu + 6.0                       # outside the domain [-4, 4]: the clip acts
     return g, tw, s, (tau, Mu, lVar, Rho)
-
-
-def param_diff(s, tw):
-    h = s._h
-    cont, mask = s._cont[:, None], s._mask_d[:, None, :]
-    return max(float(np.max(np.abs(h['tau'] - tw.tau.detach().numpy()))),
-               float(np.max(np.abs(np.where(cont, h['theta_c'][:, :, 0] - tw.Mu.detach().numpy(), 0.0)))),
-               float(np.max(np.abs(np.where(cont, h['theta_c'][:, :, 1] - tw.lVar.detach().numpy(), 0.0)))),
-               float(np.max(np.abs(np.where(mask, h['rho'] - tw.Rho.detach().numpy(), 0.0)))))
 
 
 def test_run_host_follows_the_twins_adam():
