@@ -81,8 +81,11 @@ __global__ void __launch_bounds__(BLOCK) gabp_v2f_kernel(lhvi_graph_t g, const d
 
 // Variables with more than GABP_HUB_DEGREE incident factors (the template variables of a relational model): one wavefront
 // per variable forms the information-form total once and every slot subtracts one copy of its own factor's term
-// ("total minus own": O(deg) instead of O(deg^2); costs a relative error of ~deg * 1e-16 in the hub's messages, which
-// the direct sum of the low-degree path avoids).
+// ("total minus own": O(deg) instead of O(deg^2).  The own term is added and taken out again, so a slot's precision P carries
+// an absolute error of up to (n + 4) u sum |p_i c_i| over ALL n entries of the row, its own included (u = 2^-53): relative
+// (n + 4) u sum |p c| / |P|.  That is ~deg * 1e-16 only while no entry dominates the row; the slot of an entry that holds
+// 1e9 times the precision of all the others can lose nine digits (held to the bound in tests/test_gpu_gabp_kernels.py,
+// `dominant`; figures in docs/kernels_gaussian.md), which the direct sum of the low-degree path avoids).
 __global__ void __launch_bounds__(BLOCK) gabp_v2f_hub_kernel(lhvi_graph_t g, const double* __restrict__ f2v,
                                                             double* __restrict__ v2f) {
     const int lane = threadIdx.x & 63;
@@ -520,7 +523,8 @@ __global__ void __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(LHVI
         } else {
             // a long row: the row's total less the slot's own chunk, plus that chunk's other entries (the chunks' sums and the
             // total are intermediate results: O(8) additions per slot instead of O(len); differs from the reference's
-            // left-to-right sum by rounding only: asserted at 1e-13 on the fixtures)
+            // left-to-right sum by rounding only -- like the hub kernels' total minus own, within (n + 4) u sum |p| / |P| relative,
+            // the sum over the whole row: 1e-13 on the fixtures, far more where one entry dominates the row's precision)
             const int nc = n / GABP_ROW_CHUNK, q = min(own / GABP_ROW_CHUNK, nc - 1);
             const double2 tot = sht[(lo - lo_ext) / (GABP_ROW_DIRECT + 1)], mine = shc[(lo - lo_ext) / GABP_ROW_CHUNK + q];
             H = tot.x - mine.x; P = tot.y - mine.y;
